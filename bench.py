@@ -83,6 +83,35 @@ def measured_traffic(kind, config, side, points, dtype):
     return None
 
 
+DUMP_MAX_VALUES = 1 << 23  # --dump-outputs: a larger field is cut to a seeded sample of at most this many values (32 MiB)
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, x, first, n, iterations, rel_residual, dist=None, rank=0):
+    """--dump-outputs: what the last timed step handed its caller -- solve_cg's solution field (float32,
+    flattened with the first axis fastest), iteration count and relative residual -- as <out_dir>/<name>.npy.  x: this
+    rank's part of the field, the global values [first, first + len(x)) of n.  A field of more than DUMP_MAX_VALUES values
+    is cut to the values at the sorted, de-duplicated draws of np.random.default_rng(DUMP_SEED).integers(0, n,
+    DUMP_MAX_VALUES): the same indices for the same lattice in every run, whatever the number of ranks."""
+    import numpy as np
+    if n > DUMP_MAX_VALUES:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_MAX_VALUES))
+        idx = idx[(idx >= first) & (idx < first + len(x))]
+        x = x[idx - first]
+    piece = (first, np.asarray(x, np.float32))
+    if dist is not None:
+        pieces = [None] * dist.get_world_size()
+        dist.all_gather_object(pieces, piece)
+    else:
+        pieces = [piece]
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "solution.npy"), np.concatenate([p for _, p in sorted(pieces, key=lambda p: p[0])]))
+    np.save(os.path.join(out_dir, "iterations.npy"), np.float64(iterations))
+    np.save(os.path.join(out_dir, "rel_residual.npy"), np.float64(rel_residual))
+
+
 def host_cores():
     """Cores this process may really use: the affinity mask, cut by the cgroup CPU quota, at most 16 (a GPU box gives
     one GPU's job a 16-core share of a 256-thread host; more OpenMP threads than that only fight each other)."""
@@ -293,7 +322,12 @@ def main():
     ap.add_argument("--datasets", type=int, default=3,
                     help="config 4: the timed steps walk through this many seeds of the workload (1-3; every one has an oracle "
                          "golden at 256^3): a re-solve on changed data each step.  1: the same points every step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the solution field, its iteration count and "
+                         "relative residual) as DIR/<name>.npy; a field of more than %d values as a fixed seeded sample" % DUMP_MAX_VALUES)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -464,6 +498,10 @@ def main():
     true_rel = field.true_residual()
 
     replicas = not parallelism.startswith("slab")
+    if args.dump_outputs:
+        # d_out still holds the last timed step's solution: the accuracy legs below solve into it again
+        dump_outputs(args.dump_outputs, d_out.cpu().numpy(), field.slab[0] * int(np.prod(wl["sizes"][:-1])),
+                     int(np.prod(wl["sizes"])), iters, rel, dist=None if replicas else dist, rank=rank)
     n_global = int(np.prod(wl["sizes"])) * (world if replicas else 1)
     value = n_global * args.steps / elapsed
     spmv_avg_ms = acc["spmv_ms"] / max(acc["spmv_n"], 1)

@@ -46,10 +46,11 @@ def test_struct_mirrors_match_the_header():
 
 
 def test_no_device_is_a_status_code_not_a_crash():
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("a GPU is present")
     from field_interpolation_amd import _capi
+    # asked of the library, not of torch: torch brings its own HIP runtime, and once that one has opened the device
+    # the library's runtime finds none for the rest of the process (every later GPU test of the same run)
+    if _capi.device_count() > 0:
+        pytest.skip("a GPU is present")
     lib = _capi.lib()
     h = C.c_void_p()
     sizes = (C.c_int * 2)(8, 8)

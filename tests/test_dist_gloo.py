@@ -113,16 +113,36 @@ def _worker(rank, world, port, sizes, kw, max_it, out_path):
     dist.destroy_process_group()
 
 
+def _spawn(fn, args, nprocs):
+    """fn(rank, *args) in nprocs fresh processes, as torch.multiprocessing.spawn but without torch in THIS process: torch
+    brings its own HIP runtime and RCCL, and once they are loaded here the GPU tests later in the same run get them in
+    place of the library's (libamdhip64.so, librccl.so.1) and find no device."""
+    import multiprocessing
+    from multiprocessing.connection import wait
+    ctx = multiprocessing.get_context("spawn")
+    procs = [ctx.Process(target=fn, args=(rank,) + tuple(args)) for rank in range(nprocs)]
+    for p in procs:
+        p.start()
+    live = list(procs)
+    # the first rank that fails ends the others, which would wait for it in a collective
+    while live and all(p.exitcode in (None, 0) for p in procs):
+        wait([p.sentinel for p in live])
+        live = [p for p in live if p.is_alive()]
+    for p in procs:
+        p.terminate()
+        p.join()
+    assert [p.exitcode for p in procs] == [0] * nprocs, [p.exitcode for p in procs]
+
+
 @pytest.mark.parametrize("world,sizes,kw", [
     (2, [10, 16], dict()),                                   # model_2: two ghost planes
     (3, [6, 5, 12], dict(model_2=0.0, model_1=0.5)),         # model_1: one ghost plane
     (2, [5, 4, 14], dict(model_4=0.3, model_2=0.2)),         # model_4: four ghost planes
 ])
 def test_slab_pcg_over_gloo_matches_single_process(oracle, tmp_path, world, sizes, kw):
-    import torch.multiprocessing as mp
     out = str(tmp_path / "x.npy")
     max_it = 25
-    mp.spawn(_worker, args=(world, _free_port(), sizes, kw, max_it, out), nprocs=world, join=True)
+    _spawn(_worker, (world, _free_port(), sizes, kw, max_it, out), world)
     x = np.load(out)
     f, _ = _problem(oracle, sizes, kw)
     x_ref, it, _ = f.solve_pcg(np.zeros(f.num_unknowns), max_it, 1e-300, use_double=True)
