@@ -462,6 +462,14 @@ class LatticeGroup:
         for m in self.members:
             m.set_mg_smoother(polynomial, safe_factor, terms, ratio)
 
+    def set_cheb_smoother(self, degree=0, ratio=0.0):
+        for m in self.members:
+            m.set_cheb_smoother(degree, ratio)
+
+    def set_kcycle(self, levels):
+        for m in self.members:
+            m.set_kcycle(levels)
+
     def assemble(self):
         check(_capi.lib().fi_group_assemble(self._g))
         for m in self.members:

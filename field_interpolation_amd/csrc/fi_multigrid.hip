@@ -1031,17 +1031,9 @@ struct KcScalars {
 	double s1;            // a1 / rho1
 	double coef1, coef2;  // e = coef1 c1 + coef2 c2
 };
-// step 1: partials of c1 . b and c1 . w1 -> s1;  step 2: of c2 . b, c2 . w1, c2 . r1, c2 . w2 -> coef1, coef2
-__global__ __launch_bounds__(kThreads) void k_kc_coef(KcScalars* kc, const double* __restrict__ partial, int stride, int count, int step)
+// step 1: out = c1 . b, c1 . w1 -> s1;  step 2: out = c2 . b, c2 . w1, c2 . r1, c2 . w2 -> coef1, coef2
+__device__ inline void kc_coef(KcScalars* kc, const double* out, int step)
 {
-	double acc[4] = {0, 0, 0, 0};
-	const int nv = step == 1 ? 2 : 4;
-	for (int v = 0; v < nv; ++v) {
-		for (int i = threadIdx.x; i < count; i += kThreads) { acc[v] += partial[static_cast<size_t>(v) * stride + i]; }
-	}
-	double out[4];
-	block_sum<4>(acc, out);
-	if (threadIdx.x != 0) { return; }
 	if (step == 1) {
 		kc->a1   = out[0];
 		kc->rho1 = out[0] - out[1];  // c1 . (b - w1)
@@ -1064,6 +1056,31 @@ __global__ __launch_bounds__(kThreads) void k_kc_coef(KcScalars* kc, const doubl
 		kc->coef1 = s1;
 		kc->coef2 = 0.0;
 	}
+}
+// ... from the step's per-block partials (an undivided lattice)
+__global__ __launch_bounds__(kThreads) void k_kc_coef(KcScalars* kc, const double* __restrict__ partial, int stride, int count, int step)
+{
+	double acc[4] = {0, 0, 0, 0};
+	const int nv = step == 1 ? 2 : 4;
+	for (int v = 0; v < nv; ++v) {
+		for (int i = threadIdx.x; i < count; i += kThreads) { acc[v] += partial[static_cast<size_t>(v) * stride + i]; }
+	}
+	double out[4];
+	block_sum<4>(acc, out);
+	if (threadIdx.x != 0) { return; }
+	kc_coef(kc, out, step);
+}
+// ... from the step's sums over all slabs (CgScalars::sums of scalar slot 2: reduce_to_slot2) -- every member forms the same
+// coefficients from the same numbers
+__global__ void k_kc_coef_summed(KcScalars* kc, const double* __restrict__ sums, int step)
+{
+	if (threadIdx.x != 0 || blockIdx.x != 0) { return; }
+	double out[4] = {sums[0], sums[1], 0.0, 0.0};
+	if (step == 2) {
+		out[2] = sums[2];
+		out[3] = sums[3];
+	}
+	kc_coef(kc, out, step);
 }
 // the dot products of one step in ONE pass over the vectors: a . b0, a . b1 (step 1), ... a . b3 (step 2) -> partial[v * stride + block]
 template <typename T, int NV>
@@ -1106,15 +1123,111 @@ __global__ __launch_bounds__(kThreads) void k_kc_combine(int64_t n, const KcScal
 		c1[i] = a * c1[i] + b * c2[i];
 	}
 }
+// Which levels are K-levels.  A slab decomposition must pick the undivided lattice's levels, and every rank the same ones: a
+// slab level decides from facts all ranks share -- would the small-level engine run it on the undivided lattice
+// (tail_level_undivided: <= 4 096 unknowns, fp32, the engine's LDS bound, ...), would the fused recurrence step exist there
+// (stencil_full_epi_available) -- never from its own slab (fi_ctx::tail_ok is false on every slab level; a slab without data
+// cells has a fused step where its neighbour has not).  What the slab rule deliberately does not see: whether the undivided
+// lattice has data cells at all -- under the test switch FI_NO_FUSE an undivided lattice WITHOUT cells keeps its fused step
+// and its K-levels, the slabs do not --, and the first cycle of an undivided lattice whose tail program does not fit the LDS
+// (tail_ok is dropped only when the engine first tries it; the slabs decide as from the second cycle on).
+// Whole lattices -- an undivided one, a replicated level's copies -- decide as before.
 bool kcycle_level(const RankSet& Rc)
 {
 	const fi_ctx* c = Rc[0];
-	return Rc.size() == 1 && c->nranks == 1 && c->mg_kcycle > 0 && c->level >= 1 && c->level <= c->mg_kcycle && c->coarse != nullptr && !c->lumped &&
-	       !c->tail_ok && !c->replicated && smooth_fused_ok(Rc) && !test_switch("FI_NO_KCYCLE");
+	if (c->mg_kcycle <= 0 || c->level < 1 || c->level > c->mg_kcycle || c->coarse == nullptr || c->lumped || test_switch("FI_NO_KCYCLE")) {
+		return false;
+	}
+	if (c->nranks == 1) { return !c->tail_ok && smooth_fused_ok(Rc); }
+	const bool fused_step = !test_switch("FI_NO_FUSED_SMOOTHER") && !test_switch("FI_NO_FUSE") && !c->any_trip &&
+	                        (c->g.ndim == 2 ? c->tile2.valid : (c->march.valid && !c->march.wide && c->dtype == FI_F32));
+	return fused_step && !tail_level_undivided(c);
+}
+// does the cycle that starts at `top` (a finest level) correct any of its levels by the K-cycle?
+bool any_kcycle_level(const RankSet& top)
+{
+	if (top[0]->mg_kcycle <= 0) { return false; }
+	for (RankSet lev = coarse_of(top); lev[0]; lev = coarse_of(lev)) {
+		if (kcycle_level(lev)) { return true; }
+	}
+	return false;
+}
+// The same correction over a slab level (the members of a loop-back group, or this process's slab): the residuals need the
+// ghost planes of c1 and c2; the dot products of a step are taken over each member's owned points and summed over the slabs
+// in ONE collective (2 values after step 1, 4 after step 2: reduce_to_slot2), and every member forms the same coefficients.
+template <typename T>
+void kcycle_correction_slabs(RankSet& Rc)
+{
+	const Vec B = &fi_ctx::mg_b, C1 = &fi_ctx::mg_x, W1 = &fi_ctx::r, R1 = &fi_ctx::x, C2 = &fi_ctx::p, W2 = &fi_ctx::q;
+	for (fi_ctx* c : Rc) {
+		ensure_vectors(c);
+		c->kc.alloc(sizeof(KcScalars));
+	}
+	auto nb     = [](fi_ctx* c) { return stream_blocks(c->g.nown); };
+	auto stride = [](fi_ctx* c) { return c->max_blocks; };
+	const bool fused = smooth_fused_ok(Rc);
+	auto residual = [&](Vec x, Vec rhs, Vec w) {  // w = rhs - A x (the V-cycle's two forms: ChebEpi mode 3, or apply + k_sub)
+		if (fused) {
+			halo_exchange(Rc, x);
+			for (fi_ctx* c : Rc) { stencil_full_step(c, (c->*x).p, nullptr, (c->*rhs).p, true, (c->*w).p, 0.0, 0.0, 0.0); }
+			return;
+		}
+		apply_all(Rc, x, &fi_ctx::mg_r, false);  // (mg_r: the cycle's own residual, free between cycles)
+		for (fi_ctx* c : Rc) {
+			hipLaunchKernelGGL((k_sub<T>), dim3(nb(c)), dim3(kThreads), 0, c->stream, c->g.nown, vown<T>(c, rhs), vown<T>(c, &fi_ctx::mg_r),
+			                   vown<T>(c, w));
+		}
+	};
+	auto coefficients = [&](int step) {
+		reduce_to_slot2(Rc, step == 1 ? 2 : 4, nb, stride, +[](fi_ctx* c) -> const double* { return c->partial.as<double>(); });
+		for (fi_ctx* c : Rc) {
+			hipLaunchKernelGGL(k_kc_coef_summed, dim3(1), dim3(64), 0, c->stream, c->kc.as<KcScalars>(), (c->scal.as<CgScalars>() + 2)->sums, step);
+		}
+	};
+	vcycle<T>(Rc, B, C1);
+	residual(C1, B, W1);  // w1 = b - A c1
+	for (fi_ctx* c : Rc) {
+		hipLaunchKernelGGL((k_kc_dots<T, 2>), dim3(nb(c)), dim3(kThreads), 0, c->stream, c->g.nown, vown<T>(c, C1), vown<T>(c, B), vown<T>(c, W1),
+		                   static_cast<const T*>(nullptr), static_cast<const T*>(nullptr), c->partial.as<double>(), c->max_blocks);
+	}
+	coefficients(1);
+	if (const char* e = tuning_switch("FI_KC_STEPS")) {  // (timing builds: ONE step, as in kcycle_correction)
+		if (atoi(e) == 1) {
+			for (fi_ctx* c : Rc) {
+				hipLaunchKernelGGL((k_kc_combine<T>), dim3(nb(c)), dim3(kThreads), 0, c->stream, c->g.nown, c->kc.as<KcScalars>(), vown<T>(c, C1),
+				                   vown<T>(c, C1));
+			}
+			return;
+		}
+	}
+	for (fi_ctx* c : Rc) {
+		hipLaunchKernelGGL((k_kc_r1<T>), dim3(nb(c)), dim3(kThreads), 0, c->stream, c->g.nown, c->kc.as<KcScalars>(), vown<T>(c, B), vown<T>(c, W1),
+		                   vown<T>(c, R1));
+	}
+	vcycle<T>(Rc, R1, C2);
+	residual(C2, R1, W2);  // w2 = r1 - A c2
+	for (fi_ctx* c : Rc) {
+		hipLaunchKernelGGL((k_kc_dots<T, 4>), dim3(nb(c)), dim3(kThreads), 0, c->stream, c->g.nown, vown<T>(c, C2), vown<T>(c, B), vown<T>(c, W1),
+		                   vown<T>(c, R1), vown<T>(c, W2), c->partial.as<double>(), c->max_blocks);
+	}
+	coefficients(2);
+	for (fi_ctx* c : Rc) {
+		hipLaunchKernelGGL((k_kc_combine<T>), dim3(nb(c)), dim3(kThreads), 0, c->stream, c->g.nown, c->kc.as<KcScalars>(), vown<T>(c, C1),
+		                   vown<T>(c, C2));
+	}
+	FI_HIP_TRY(hipGetLastError());
 }
 template <typename T>
 void kcycle_correction(RankSet& Rc)
 {
+	if (replicated_copies(Rc)) {  // a replicated level's copies: each the undivided correction on its own, no collective
+		for_each_copy(Rc, [&](RankSet& one) { kcycle_correction<T>(one); });
+		return;
+	}
+	if (Rc.size() > 1 || Rc[0]->nranks > 1) {
+		kcycle_correction_slabs<T>(Rc);
+		return;
+	}
 	fi_ctx* c = Rc[0];
 	ensure_vectors(c);
 	c->kc.alloc(sizeof(KcScalars));
@@ -1486,7 +1599,7 @@ void cg_run_mg(RankSet& R, int max_iterations, float tol)
 	auto nb_apply = [](fi_ctx* c) { return apply_num_partials(c); };
 	// (the step kernels' workgroup maxima: behind the r.r partials -- the array holds 4 x max_blocks doubles)
 	auto field_part = [&](fi_ctx* c) -> double* { return by_field ? c->partial.as<double>() + static_cast<size_t>(c->max_blocks) : nullptr; };
-	const Vec X = &fi_ctx::x, Rv = &fi_ctx::r, P = &fi_ctx::p, Q = &fi_ctx::q, Z = &fi_ctx::mg_x, B = &fi_ctx::atb;
+	const Vec X = &fi_ctx::x, Rv = &fi_ctx::r, P = &fi_ctx::p, Z = &fi_ctx::mg_x, B = &fi_ctx::atb;
 	while (static_cast<int>(c0->ev.size()) < 2 * kMaxSamples) {
 		hipEvent_t e;
 		FI_HIP_TRY(hipEventCreate(&e));
@@ -1494,9 +1607,18 @@ void cg_run_mg(RankSet& R, int max_iterations, float tol)
 	}
 	int samples = 0;
 	const bool mixed = !Tw.empty();
-	// FI_OPT_MG_KCYCLE: the cycle then depends on its argument and CG takes the flexible beta (one undivided context)
-	const bool flexible = (mixed ? Tw[0] : c0)->mg_kcycle > 0 && (mixed ? Tw[0] : c0)->coarse != nullptr && R.size() == 1 && c0->nranks == 1 &&
-	                      !test_switch("FI_NO_KCYCLE");
+	// FI_OPT_MG_KCYCLE: where a level of the hierarchy IS a K-level the cycle depends on its argument and CG takes the flexible beta.
+	// q = A p.  The flexible beta reads A p_k AFTER the cycle; a cycle on R itself (no fp32 replica) takes R's q as scratch (the 3-D
+	// restriction's intermediate, the unfused residual, a smoother work vector), so A p then lives in mg_b, which the top level's
+	// cycle never touches (mg_b is the right-hand side of a COARSE level's cycle).  With the replica the cycle runs on Tw: q stays.
+	// The coarse-to-fine start's level solves (level > 0) keep the form bench_settings' configurations were tuned with: the
+	// flexible beta whenever the option is set, from q as the cycle left it (config 5 with it corrected there: 14 iterations
+	// instead of 12 -- a change of the measured start, left to a measurement of its own).
+	const bool start_level = c0->level > 0;
+	const bool flexible = start_level ? (mixed ? Tw[0] : c0)->mg_kcycle > 0 && (mixed ? Tw[0] : c0)->coarse != nullptr && !test_switch("FI_NO_KCYCLE")
+	                                  : any_kcycle_level(mixed ? Tw : R);
+	const bool undivided = R.size() == 1 && c0->nranks == 1;
+	const Vec Q = flexible && !mixed && !start_level ? &fi_ctx::mg_b : &fi_ctx::q;
 	fi_ctx* const prec_ctx = mixed ? Tw[0] : c0;  // the context whose finest-level smoother chains are timed (vcycle)
 	if (prec_ctx->level == 0 && !(mixed ? replicated_copies(Tw) : replicated_copies(R))) {
 		while (static_cast<int>(prec_ctx->ev_prec.size()) < 2 * kPolySamples) {
@@ -1680,7 +1802,7 @@ void cg_run_mg(RankSet& R, int max_iterations, float tol)
 		const bool sample = samples < 2;
 		halo_exchange(R, P);
 		if (sample) { FI_HIP_TRY(hipEventRecord(c0->ev[2 * samples], st)); }
-		for (fi_ctx* c : R) { apply_AtA(c, c->p.p, c->q.p, c->partial.as<double>()); }
+		for (fi_ctx* c : R) { apply_AtA(c, c->p.p, (c->*Q).p, c->partial.as<double>()); }
 		if (sample) {
 			FI_HIP_TRY(hipEventRecord(c0->ev[2 * samples + 1], st));
 			++samples;
@@ -1741,6 +1863,34 @@ void cg_run_mg(RankSet& R, int max_iterations, float tol)
 		if (mixed) { Tw[0]->bx_dot_done = false; }
 		precondition<T>(R, Tw, Rv, Z, stepped);
 		dot_rz();
+		if (flexible && !undivided) {
+			// over slabs: z_(k+1) . q_k (q: still A p_k) per member behind the r . z partials, both summed over the slabs in ONE
+			// collective (sums[0], sums[1]) -- no more collectives per iteration than the V-cycle's
+			for (size_t i = 0; i < R.size(); ++i) {
+				fi_ctx* c = R[i];
+				double* part_qz = c->partial.as<double>() + static_cast<size_t>(c->max_blocks);
+				bool done_qz = false;
+				if constexpr (std::is_same<T, double>::value) {
+					if (mixed) {
+						hipLaunchKernelGGL(c->g.nown >= kStreamMin ? k_dot_mixed<true> : k_dot_mixed<false>, dim3(nbv(c)), dim3(kThreads), 0, c->stream, c->g.nown,
+						                   c->scal.as<CgScalars>(), vown<double>(c, Q), vown<float>(Tw[i], &fi_ctx::mg_x), part_qz);
+						done_qz = true;
+					}
+				}
+				if (!done_qz) {
+					hipLaunchKernelGGL((k_dot<T>), dim3(nbv(c)), dim3(kThreads), 0, c->stream, c->g.nown, vown<T>(c, Q), vown<T>(c, Z), part_qz);
+				}
+			}
+			reduce_phase(R, 2, nbv, [](fi_ctx* c) { return c->max_blocks; }, -1);
+			for (fi_ctx* c : R) {
+				CgScalars* sc = c->scal.as<CgScalars>();
+				hipLaunchKernelGGL(k_mg_logic, dim3(1), dim3(kThreads), 0, c->stream, sc, static_cast<const double*>(nullptr), 0, kMgBeta);
+				hipLaunchKernelGGL(k_mg_logic, dim3(1), dim3(kThreads), 0, c->stream, sc, static_cast<const double*>(sc->sums + 1), 1, kMgFlex);
+			}
+			direction(0);
+			FI_HIP_TRY(hipGetLastError());
+			continue;
+		}
 		reduce_rz(kMgBeta);
 		if (flexible) {  // z_(k+1) . q_k for the flexible beta (q: still A p_k)
 			if constexpr (std::is_same<T, double>::value) {

@@ -65,6 +65,9 @@ struct TailOp {
 };
 
 bool tail_level_supported(const fi_ctx* c);   // a level the engine can run (size, geometry, model rows, no triplet rows)
+// would the engine run this level and every one below it on the UNDIVIDED lattice (fi_ctx::tail_ok there)?  Over slabs: from
+// facts every rank shares
+bool tail_level_undivided(const fi_ctx* c);
 void tail_build_operator(fi_ctx* c);          // `dia` of an assembled level, on the level's stream
 TailLevel tail_level_of(const fi_ctx* c);
 // runs the program (device array of `nops` stages over `nlev` levels, both in `prog`: TailLevel[kTailMaxLevels] then the ops):

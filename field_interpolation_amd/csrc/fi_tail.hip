@@ -371,16 +371,33 @@ __global__ __launch_bounds__(kThreads) void k_tail_dia(Geom g, int nn, const uin
 
 }  // namespace
 
-bool tail_level_supported(const fi_ctx* c)
+// whole: the answer for the undivided lattice of a slab level, from facts every rank shares (the lattice, the weights, the
+// agreed data facts) -- which levels the K-cycle corrects over slabs (fi_multigrid.hip, kcycle_level)
+static bool tail_level_rule(const fi_ctx* c, bool whole)
 {
 	const fi_weights& w = c->w;
 	if (test_switch("FI_NO_TAIL")) { return false; }  // tests: the tiled kernels run every level
-	if (c->dtype != FI_F32 || c->nranks != 1 || (c->g.ndim != 2 && c->g.ndim != 3)) { return false; }
+	if (c->dtype != FI_F32 || (!whole && c->nranks != 1) || (c->g.ndim != 2 && c->g.ndim != 3)) { return false; }
 	if (w.model_3 > 0 || w.model_4 > 0 || w.gradient_smoothness > 0 || !(w.model_1 > 0 || w.model_2 > 0)) { return false; }
-	if (c->generic.ntrip != 0 || c->any_trip) { return false; }
+	if ((!whole && c->generic.ntrip != 0) || c->any_trip) { return false; }
 	int64_t nn = 1;
 	for (int d = 0; d < c->g.ndim; ++d) { nn *= c->g.gn[d]; }
-	return nn <= kTailMaxPoints && c->g.nown == c->g.nloc;
+	return nn <= kTailMaxPoints && (whole || c->g.nown == c->g.nloc);
+}
+bool tail_level_supported(const fi_ctx* c) { return tail_level_rule(c, false); }
+
+// (build_levels' tail_ok of the undivided lattice, and the LDS bound under which tail_vcycle drops it at the first cycle --
+// tail_level_floats of the global extents; the program's other refusals depend on settings every rank shares: a lumped
+// level, a smoother of degree < 2)
+bool tail_level_undivided(const fi_ctx* c)
+{
+	int depth = 0, floats = 0;
+	for (const fi_ctx* l = c; l; l = l->coarse) {
+		if (!tail_level_rule(l, l->nranks > 1) || l->lumped) { return false; }
+		++depth;
+		floats += tail_level_floats(l->g.ndim, l->g.gn);
+	}
+	return depth <= kTailMaxLevels && floats * sizeof(float) <= 160u * 1024u;
 }
 
 void tail_build_operator(fi_ctx* c)

@@ -287,13 +287,21 @@ int fi_solve_cg(fi_ctx* ctx, const float* guess, int max_iterations, float tol, 
  * but for warm starts on hierarchies whose cold solves take a thousand iterations (2 cases, 15 x); the goldens of configs 2 to 5 end 8 to 100 x
  * below it.  fi_stats: field_estimate, field_per_residual. */
 #define FI_OPT_FIELD_TOLERANCE 12
-/* FI_OPT_MG_KCYCLE (default 0 = off; V-cycle PCG on an undivided lattice, fp32 levels): a K-cycle -- the correction of the
+/* FI_OPT_MG_KCYCLE (default 0 = off; V-cycle PCG, fp32 levels): a K-cycle -- the correction of the
  * first `value` coarse levels is not one application of the coarser level's cycle but TWO steps of flexible CG on that
  * level's system, each preconditioned by the level's cycle (Notay & Vassilevski: the lengths of the two corrections come from
  * a line search in the energy norm, so a level whose own cycle overcorrects -- the re-discretised coarse levels of
  * oriented-point data do, profiles/r6_ablation.md section 11 -- cannot make the preconditioner indefinite the way a W-cycle
- * does).  The preconditioner then depends on its argument: the outer CG takes the flexible beta, -alpha z_(k+1) . A p_k /
- * (z_k . r_k), one more dot product per iteration.  Set before fi_assemble. */
+ * does).  Levels the small-level engine runs (<= 4 096 unknowns at the bottom of the hierarchy) keep their V-cycle.  The
+ * preconditioner then depends on its argument: the outer CG takes the flexible beta, -alpha z_(k+1) . A p_k / (z_k . r_k),
+ * one more dot product per iteration.
+ * Over slabs (a loop-back group, or one slab per process) the same algorithm: the same K-levels -- chosen on the undivided
+ * lattice, alike on every rank -- and the same steps; only the order of the sums and the collectives differ.  A visit of a
+ * slab K-level costs TWO all-reduces (the two dot products of step 1, the four of step 2, each set in one); a K-level's
+ * coarser levels are visited twice as often, so the K-levels below the first cost 2, 4, ... per outer iteration, and a
+ * junction sum above the replicated tail is made once per visit of its level.  Replicated levels (whole lattices below the
+ * slabs) correct on every rank on their own: no collective.  The outer CG's extra dot product travels in the r . z sum: no
+ * collective of its own.  fi_stats.reductions counts them all.  Set before fi_assemble. */
 #define FI_OPT_MG_KCYCLE 13
 /* FI_OPT_MG_CHEB_DEGREE (0 or 2..16) and FI_OPT_MG_CHEB_RATIO (0 or (1, 1000]): degree and interval [lambda / ratio, 1.1 lambda] of
  * the Chebyshev smoother in the full operator (2-D lattices, oriented points, fp64 levels).  0 (default): by the lattice's
