@@ -10,6 +10,7 @@ forces are stated where they occur:
     169-181, 402-405).
 Buffers may be numpy arrays (host) or torch CUDA tensors (device pointers are passed through).
 """
+import collections
 import ctypes as C
 import enum
 import math
@@ -79,6 +80,43 @@ def _same_memory(*kinds):
     if len(ks) > 1:
         raise ValueError("all buffers of one call must live in the same memory (all host or all device)")
     return ks.pop() if ks else FI_HOST
+
+
+IsoMesh = collections.namedtuple("IsoMesh", ["vertices", "normals", "indices", "keys"])
+IsoMesh.__doc__ = """An iso-contour (2-D: segments, indices (P, 2)) or iso-surface (3-D: triangles, indices (P, 3)) in lattice units:
+vertices (V, ndim) float32, normals (V, ndim) float32 or None, indices int32, keys (V,) int64 = ndim * index(p) + axis of
+the lattice edge (p, p + e_axis) each vertex lies on, ascending (include/fi_hip.h, fi_iso_extract)."""
+
+
+def _take_mesh(h, ndim, normals=True):
+    """IsoMesh of a device mesh handle, which is destroyed."""
+    try:
+        nv, np_, vpp = C.c_long(0), C.c_long(0), C.c_int(0)
+        check(_capi.lib().fi_mesh_info(h, C.byref(nv), C.byref(np_), C.byref(vpp)))
+        v = np.empty((nv.value, ndim), np.float32)
+        n = np.empty((nv.value, ndim), np.float32) if normals else None
+        i = np.empty((np_.value, vpp.value or ndim), np.int32)
+        k = np.empty(nv.value, np.int64)
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+        check(_capi.lib().fi_mesh_copy(h, ptr(v), ptr(n), ptr(i), ptr(k), FI_HOST))
+        return IsoMesh(v, n, i, k)
+    finally:
+        _capi.lib().fi_mesh_destroy(h)
+
+
+def merge_meshes(pieces):
+    """The pieces of a slab decomposition (rank order) as one mesh: vertices de-duplicated by key, indices remapped."""
+    pieces = list(pieces)
+    keys = np.concatenate([p.keys for p in pieces])
+    uniq, first = np.unique(keys, return_index=True)
+    verts = np.concatenate([p.vertices for p in pieces])[first]
+    normals = None
+    if all(p.normals is not None for p in pieces):
+        normals = np.concatenate([p.normals for p in pieces])[first]
+    idx = [np.searchsorted(uniq, p.keys)[p.indices].astype(np.int32) for p in pieces]
+    vpp = pieces[0].indices.shape[1] if pieces else 3
+    idx = np.concatenate(idx) if idx else np.empty((0, vpp), np.int32)
+    return IsoMesh(verts, normals, idx.reshape(-1, vpp), uniq.astype(np.int64))
 
 
 class LatticeField:
@@ -273,6 +311,18 @@ class LatticeField:
                 return None
             raise
         return out, it.value, rel.value
+
+    def iso_surface(self, solution=None, iso=0.0, normals=True):
+        """The iso-contour (2-D) / iso-surface (3-D) f = iso of `solution` (this context's owned values, host or device) or,
+        with None, of the last solve's solution where it lives on the device -- the step src/sdf_field.cpp:605-613 takes
+        after the solve.  A slab context returns its piece (merge_meshes joins them).  -> IsoMesh"""
+        h = C.c_void_p()
+        if solution is None:
+            check(_capi.lib().fi_iso_extract(self._h, None, float(iso), FI_HOST, C.byref(h)))
+        else:
+            s, mem, _keep = _buf(solution)
+            check(_capi.lib().fi_iso_extract(self._h, s, float(iso), mem, C.byref(h)))
+        return _take_mesh(h, len(self.sizes), normals)
 
     def set_verify_residual(self, on):
         """FI_OPT_VERIFY_RESIDUAL: True (default) checks b - A x at convergence and restarts CG if fp32 drift
@@ -523,6 +573,23 @@ class LatticeGroup:
         check(_capi.lib().fi_group_true_residual(self._g, C.byref(r)))
         return r.value
 
+    def iso_surface(self, field=None, iso=0.0, normals=True):
+        """The pieces (one IsoMesh per slab, rank order) of the iso-contour of `field` (the WHOLE lattice, host) or, with
+        None, of the members' last solution.  merge_meshes(pieces) is the undivided mesh."""
+        hs = (C.c_void_p * len(self.members))()
+        f = None if field is None else np.ascontiguousarray(field, np.float32).reshape(-1)
+        check(_capi.lib().fi_group_iso_extract(self._g, None if f is None else C.c_void_p(f.ctypes.data), float(iso), hs))
+        out = []
+        try:
+            for r in range(len(self.members)):
+                h, hs[r] = hs[r], None
+                out.append(_take_mesh(C.c_void_p(h), len(self.sizes), normals))
+        finally:
+            for h in hs:
+                if h:
+                    _capi.lib().fi_mesh_destroy(C.c_void_p(h))
+        return out
+
 
 # ---- free functions with the reference's names ---------------------------------------------------
 
@@ -611,3 +678,13 @@ def upscale_field(field, small_sizes, large_sizes):
         o = C.c_void_p(out.ctypes.data)
     check(_capi.lib().fi_upscale_field(src, len(small_sizes), ss, ls, o, mem))
     return out
+
+
+def iso_surface(field, sizes, iso=0.0, normals=True):
+    """The iso-contour (2-D) / iso-surface (3-D) f = iso of a whole lattice field (numpy array or torch CUDA tensor, x
+    fastest), e.g. the output of upscale_field.  -> IsoMesh"""
+    src, mem, _keep = _buf(field)
+    sz = (C.c_int * len(sizes))(*[int(s) for s in sizes])
+    h = C.c_void_p()
+    check(_capi.lib().fi_iso_extract_field(src, len(sizes), sz, float(iso), mem, C.byref(h)))
+    return _take_mesh(h, len(sizes), normals)

@@ -2,6 +2,7 @@
 // model, points, assemble, the solver entry points and their options, statistics.  Nothing throws or aborts across it.
 #include "fi_solver_internal.h"
 #include "fi_workers.h"
+#include "fi_iso.h"
 
 namespace fi {
 
@@ -1012,6 +1013,78 @@ int fi_upscale_field(const float* small_field, int ndim, const int* small_sizes,
 	FI_HIP_TRY(hipDeviceSynchronize());
 	if (memory == FI_HOST) { FI_HIP_TRY(hipMemcpy(out, dl.p, sizeof(float) * nl, hipMemcpyDeviceToHost)); }
 	FI_API_END
+}
+
+
+// ---- iso-contours (fi_iso.hip) ------------------------------------------------------------------
+int fi_iso_extract(fi_ctx* c, const float* field, float iso, int memory, fi_mesh** out)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	FI_REQUIRE(out != nullptr, FI_ERR_INVALID, "out is null");
+	*out = nullptr;
+	fi::bind_device(c);
+	fi::iso_extract_ctx(c, field, iso, memory, out);
+	FI_API_END
+}
+
+int fi_iso_extract_field(const float* field, int ndim, const int* sizes, float iso, int memory, fi_mesh** out)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(field && sizes && out, FI_ERR_INVALID, "null argument");
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	*out = nullptr;
+	FI_REQUIRE(ndim != 1, FI_ERR_UNSUPPORTED, "iso-contours of a 1-D lattice are not supported");
+	FI_REQUIRE(ndim == 2 || ndim == 3, FI_ERR_INVALID, "ndim must be 2 or 3 (got %d)", ndim);
+	int64_t n = 1;
+	for (int d = 0; d < ndim; ++d) {
+		FI_REQUIRE(sizes[d] >= 1, FI_ERR_INVALID, "sizes[%d] = %d", d, sizes[d]);
+		n *= sizes[d];
+	}
+	fi::DevBuf df;
+	const float* f = field;
+	if (memory == FI_HOST) {
+		df.alloc(sizeof(float) * n);
+		FI_HIP_TRY(hipMemcpy(df.p, field, sizeof(float) * n, hipMemcpyHostToDevice));
+		f = df.as<float>();
+	}
+	fi::iso_extract_whole(f, ndim, sizes, iso, 1, nullptr, nullptr, nullptr, out);
+	FI_API_END
+}
+
+int fi_mesh_info(const fi_mesh* m, long* num_vertices, long* num_primitives, int* vertices_per_primitive)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(m != nullptr, FI_ERR_INVALID, "null mesh");
+	if (num_vertices) { *num_vertices = static_cast<long>(m->nv); }
+	if (num_primitives) { *num_primitives = static_cast<long>(m->np); }
+	if (vertices_per_primitive) { *vertices_per_primitive = m->ndim; }
+	FI_API_END
+}
+
+int fi_mesh_copy(const fi_mesh* m, float* vertices, float* normals, int* indices, long long* keys, int memory)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(m != nullptr, FI_ERR_INVALID, "null mesh");
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	FI_HIP_TRY(hipSetDevice(m->device));
+	const hipMemcpyKind kind = memory == FI_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+	const size_t nv = static_cast<size_t>(m->nv), np = static_cast<size_t>(m->np), D = static_cast<size_t>(m->ndim);
+	if (vertices && nv) { FI_HIP_TRY(hipMemcpy(vertices, m->pos.p, sizeof(float) * D * nv, kind)); }
+	if (normals && nv) { FI_HIP_TRY(hipMemcpy(normals, m->nrm.p, sizeof(float) * D * nv, kind)); }
+	if (indices && np) { FI_HIP_TRY(hipMemcpy(indices, m->idx.p, sizeof(int) * D * np, kind)); }
+	if (keys && nv) { FI_HIP_TRY(hipMemcpy(keys, m->key.p, sizeof(int64_t) * nv, kind)); }
+	FI_API_END
+}
+
+int fi_mesh_destroy(fi_mesh* m)
+{
+	if (!m) { return FI_OK; }
+	int dev = 0;
+	const bool switched = hipGetDevice(&dev) == hipSuccess && dev != m->device && hipSetDevice(m->device) == hipSuccess;
+	delete m;
+	if (switched) { (void)hipSetDevice(dev); }
+	return FI_OK;
 }
 
 

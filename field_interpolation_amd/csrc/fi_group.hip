@@ -1,6 +1,7 @@
 // fi_group.hip -- the loop-back group: all slabs of a decomposition in one process on one device (tests of the slab
 // geometry, halo widths and ownership rules against the undivided solve on a one-GPU machine).
 #include "fi_solver_internal.h"
+#include "fi_iso.h"
 
 extern "C" {
 
@@ -236,6 +237,16 @@ int fi_group_get_solution_f64(fi_group* g, double* out)
 		g->dtype == FI_F64 ? fi::get_vec_f64_t<double>(c, c->x, out + at) : fi::get_vec_f64_t<float>(c, c->x, out + at);
 		at += c->g.nown;
 	}
+	FI_API_END
+}
+
+int fi_group_iso_extract(fi_group* g, const float* whole_or_null, float iso, fi_mesh** out)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(g != nullptr && out != nullptr, FI_ERR_INVALID, "null argument");
+	for (size_t r = 0; r < g->members.size(); ++r) { out[r] = nullptr; }
+	fi::bind_device(g->members[0]);
+	fi::iso_extract_group(g->members, whole_or_null, iso, out);
 	FI_API_END
 }
 

@@ -224,6 +224,30 @@ std::vector<float> GpuLatticeField::generate_error_map(const std::vector<float>&
 	return out;
 }
 
+bool GpuLatticeField::iso_surface(float iso, std::vector<float>* vertices, std::vector<int>* indices,
+                                  std::vector<float>* normals) const
+{
+	fi_mesh* m = nullptr;
+	if (fi_iso_extract(ctx_, nullptr, iso, FI_DEVICE, &m) != FI_OK) {
+		warn("iso_surface");
+		return false;
+	}
+	long nv = 0, np = 0;
+	int  vpp = 0;
+	bool ok = fi_mesh_info(m, &nv, &np, &vpp) == FI_OK;
+	const size_t D = sizes_.size();
+	if (ok) {
+		if (vertices) { vertices->resize(D * static_cast<size_t>(nv)); }
+		if (normals) { normals->resize(D * static_cast<size_t>(nv)); }
+		if (indices) { indices->resize(static_cast<size_t>(vpp) * static_cast<size_t>(np)); }
+		ok = fi_mesh_copy(m, vertices ? vertices->data() : nullptr, normals ? normals->data() : nullptr,
+		                  indices ? indices->data() : nullptr, nullptr, FI_HOST) == FI_OK;
+	}
+	if (!ok) { warn("iso_surface"); }
+	fi_mesh_destroy(m);
+	return ok;
+}
+
 std::unique_ptr<GpuLatticeField> gpu_sdf_from_points(const std::vector<int>& sizes, const Weights& weights,
                                                      int num_points, const float positions[], const float* normals,
                                                      const float* point_weights)

@@ -358,6 +358,7 @@ int fi_time_apply(fi_ctx* ctx, int reps, double* ms_per_launch);
  * undivided one.  Per-rank assembly goes through fi_group_rank(g, r) and the fi_set_model / fi_add_points
  * calls above; vectors passed to the group calls are host buffers holding the WHOLE lattice. */
 typedef struct fi_group fi_group;
+typedef struct fi_mesh fi_mesh;
 int     fi_group_create(fi_group** out, int ndim, const int* sizes, int dtype, int nranks);
 int     fi_group_destroy(fi_group* g);
 int     fi_group_size(const fi_group* g);
@@ -370,11 +371,41 @@ int     fi_group_true_residual(fi_group* g, double* rel_residual);
 int     fi_group_get_solution_f64(fi_group* g, double* out);
 int     fi_group_tile_pass(fi_group* g, const float* guess, int tile_size, float* out);
 int     fi_group_error_map(fi_group* g, const float* solution, float* out);
+/* iso-contours of the group's field (see fi_iso_extract below): whole_or_null is the WHOLE lattice on the host, or NULL for
+ * the members' last solution; out receives nranks meshes, piece r holding the cells of slab r (see fi_iso_extract). */
+int     fi_group_iso_extract(fi_group* g, const float* whole_or_null, float iso, fi_mesh** out);
 
 /* ---- helpers either side of the path ---------------------------------------------------------
  * Replaces upscale_field (field_interpolation.cpp:431-485): multilinear resampling small -> large. */
 int fi_upscale_field(const float* small_field, int ndim, const int* small_sizes, const int* large_sizes,
                      float* out, int memory);
+
+/* ---- iso-contours and iso-surfaces -----------------------------------------------------------
+ * After the solve, what src/sdf_field.cpp:605-613 (iso_surface) does on the host: the lattice's iso-contour, extracted on the
+ * device.  2-D: marching squares, line segments; 3-D: marching cubes, triangles; 1-D: FI_ERR_UNSUPPORTED.  The contract
+ * ("Iso-contours and iso-surfaces") is this project's own:
+ *   - inside is f < iso; one vertex per lattice edge (p, p + e_a) whose ends differ in inside-ness, at coordinate
+ *     p_a + t along a, t = dp / (dp - dq), dp = f(p) - iso, dq = f(q) - iso in fp32; key ndim * index(p) + a, vertices in
+ *     ascending key order; positions in lattice units;
+ *   - normal: (1 - t) g(p) + t g(q) normalised, g = central differences (one-sided at the border), towards increasing f;
+ *   - cells (all corners in the lattice) in ascending linear index; a face with two diagonal inside corners cuts each off
+ *     by its own segment (the 3-D mesh is watertight); 2-D segments have the inside on their left, 3-D triangles
+ *     (a, b, c) have (b - a) x (c - a) pointing from inside to outside;
+ *   - a non-finite value: FI_ERR_INVALID and no mesh; a mesh of >= 2^31 vertices: FI_ERR_UNSUPPORTED (int32 indices).
+ * The mesh stays on the device until fi_mesh_copy; the caller destroys it with fi_mesh_destroy.
+ *
+ * field: the context's owned values (host or device per `memory`); NULL = the context's last solution, read where it lives
+ * (an FI_F64 solution is rounded to fp32 first, exactly as fi_solve_cg's `out` is).  A slab context (nranks > 1, with its
+ * transport) exchanges the ghost planes it needs and returns its piece: the cells whose slowest coordinate lies in its
+ * slab, with every vertex they use (seam vertices too, under their global keys).  Pieces concatenated in rank order and
+ * de-duplicated by key give the undivided mesh. */
+int fi_iso_extract(fi_ctx* ctx, const float* field, float iso, int memory, fi_mesh** out);
+/* the same without a context: any whole field (e.g. the output of fi_upscale_field) */
+int fi_iso_extract_field(const float* field, int ndim, const int* sizes, float iso, int memory, fi_mesh** out);
+int fi_mesh_info(const fi_mesh* m, long* num_vertices, long* num_primitives, int* vertices_per_primitive);
+/* any output may be NULL; vertices / normals are ndim floats per vertex, indices vertices_per_primitive int32 per primitive */
+int fi_mesh_copy(const fi_mesh* m, float* vertices, float* normals, int* indices, long long* keys, int memory);
+int fi_mesh_destroy(fi_mesh* m);
 
 #ifdef __cplusplus
 }

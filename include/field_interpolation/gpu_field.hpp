@@ -56,6 +56,13 @@ public:
 	// generate_error_map(field.eq.triplets, solution, field.eq.rhs) of the reference, from the rows on the device.
 	std::vector<float> generate_error_map(const std::vector<float>& solution);
 
+	// The iso-contour (2-D: segments, 2 indices each) or iso-surface (3-D: triangles, 3 indices each) f = iso of the last
+	// solution, extracted where it lives on the device -- what src/sdf_field.cpp:605-613 (iso_surface) does on the host.
+	// vertices: ndim floats per vertex in lattice units; normals (optional): ndim floats per vertex, towards increasing f.
+	// The contract is include/fi_hip.h fi_iso_extract.  false: no solution yet, or the library refused (non-finite values).
+	bool iso_surface(float iso, std::vector<float>* vertices, std::vector<int>* indices,
+	                 std::vector<float>* normals = nullptr) const;
+
 	int    last_iterations() const { return iterations_; }
 	float  last_error() const { return error_; }
 	size_t num_data_rows() const;   // rows accepted from points (what eq.rhs.size() would have grown by)
