@@ -22,6 +22,7 @@ SYMBOLS = [
     "fi_group_create", "fi_group_destroy", "fi_group_size", "fi_group_rank", "fi_group_assemble",
     "fi_group_solve_cg", "fi_group_apply_AtA_f64", "fi_group_true_residual", "fi_group_get_solution_f64", "fi_group_tile_pass", "fi_group_error_map",
     "fi_group_iso_extract", "fi_iso_extract", "fi_iso_extract_field", "fi_mesh_info", "fi_mesh_copy", "fi_mesh_destroy",
+    "fi_group_sample", "fi_sample", "fi_sample_field",
 ]
 
 
@@ -124,6 +125,9 @@ def lib():
     L.fi_mesh_info.argtypes = [vp, C.POINTER(C.c_long), C.POINTER(C.c_long), ip]
     L.fi_mesh_copy.argtypes = [vp, fp, fp, vp, vp, C.c_int]
     L.fi_mesh_destroy.argtypes = [vp]
+    L.fi_group_sample.argtypes = [vp, fp, C.c_long, fp, C.c_int, C.c_float, fp, fp]
+    L.fi_sample.argtypes = [vp, fp, C.c_long, fp, C.c_int, C.c_float, fp, fp, C.c_int]
+    L.fi_sample_field.argtypes = [fp, C.c_int, ip, C.c_long, fp, C.c_int, C.c_float, fp, fp, C.c_int]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError if the .so lacks a declared symbol
     _LIB = L

@@ -119,6 +119,30 @@ def merge_meshes(pieces):
     return IsoMesh(verts, normals, idx.reshape(-1, vpp), uniq.astype(np.int64))
 
 
+def _sample(call, ndim, positions, other_memory, gradients, cubic, fill):
+    """Shared body of the point queries: call(n, positions, mode, fill, values, gradients, memory) is the C entry point.
+    Outputs live where `positions` lives: numpy in, numpy out; a torch tensor in, torch tensors out on its device."""
+    p, pmem, pkeep = _buf(positions)
+    count = pkeep.numel() if hasattr(pkeep, "numel") else pkeep.size
+    if count % ndim:
+        raise ValueError("positions: %d values, not a multiple of ndim = %d (x fastest)" % (count, ndim))
+    n = count // ndim
+    mem = _same_memory(pmem, *other_memory)
+    if hasattr(pkeep, "data_ptr"):
+        import torch
+        vals = torch.empty(n, dtype=torch.float32, device=pkeep.device)
+        grads = torch.empty((n, ndim), dtype=torch.float32, device=pkeep.device) if gradients else None
+        if n == 0:      # (an empty tensor has no storage to point at)
+            return (vals, grads) if gradients else vals
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    else:
+        vals = np.empty(n, np.float32)
+        grads = np.empty((n, ndim), np.float32) if gradients else None
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+    check(call(n, p, 1 if cubic else 0, float(fill), ptr(vals), ptr(grads), mem))
+    return (vals, grads) if gradients else vals
+
+
 class LatticeField:
     """field_interpolation.hpp:97-114 `LatticeField{sizes}`: sizes[0] (x) is the fastest axis.
 
@@ -323,6 +347,17 @@ class LatticeField:
             s, mem, _keep = _buf(solution)
             check(_capi.lib().fi_iso_extract(self._h, s, float(iso), mem, C.byref(h)))
         return _take_mesh(h, len(self.sizes), normals)
+
+    def sample(self, positions, solution=None, gradients=False, cubic=False, fill=float("nan")):
+        """Values (n,) -- and with gradients=True also gradients (n, ndim) -- of `solution` (this context's owned values) or,
+        with None, of the last solve's solution where it lives on the device, at `positions` (n x ndim, global lattice
+        coordinates, x fastest).  Multilinear, or Catmull-Rom with cubic=True; points outside the lattice get `fill`.  A slab
+        context's call is collective and every rank receives every point (include/fi_hip.h fi_sample)."""
+        s, smem, _keep = _buf(solution)
+
+        def call(n, p, mode, fl, v, g, mem):
+            return _capi.lib().fi_sample(self._h, s, n, p, mode, fl, v, g, mem)
+        return _sample(call, len(self.sizes), positions, [smem], gradients, cubic, fill)
 
     def set_verify_residual(self, on):
         """FI_OPT_VERIFY_RESIDUAL: True (default) checks b - A x at convergence and restarts CG if fp32 drift
@@ -590,6 +625,16 @@ class LatticeGroup:
                     _capi.lib().fi_mesh_destroy(C.c_void_p(h))
         return out
 
+    def sample(self, positions, field=None, gradients=False, cubic=False, fill=float("nan")):
+        """LatticeField.sample of `field` (the WHOLE lattice) or, with None, of the members' last solution; host arrays only.
+        The results are those of the undivided lattice."""
+        f = None if field is None else np.ascontiguousarray(field, np.float32).reshape(-1)
+        pos = np.ascontiguousarray(positions, np.float32)
+
+        def call(n, p, mode, fl, v, g, mem):
+            return _capi.lib().fi_group_sample(self._g, None if f is None else C.c_void_p(f.ctypes.data), n, p, mode, fl, v, g)
+        return _sample(call, len(self.sizes), pos, [], gradients, cubic, fill)
+
 
 # ---- free functions with the reference's names ---------------------------------------------------
 
@@ -688,3 +733,14 @@ def iso_surface(field, sizes, iso=0.0, normals=True):
     h = C.c_void_p()
     check(_capi.lib().fi_iso_extract_field(src, len(sizes), sz, float(iso), mem, C.byref(h)))
     return _take_mesh(h, len(sizes), normals)
+
+
+def sample_field(field, sizes, positions, gradients=False, cubic=False, fill=float("nan")):
+    """LatticeField.sample of a whole lattice field (numpy array or torch CUDA tensor, x fastest), e.g. the output of
+    upscale_field; field and positions live in the same memory."""
+    src, mem, _keep = _buf(field)
+    sz = (C.c_int * len(sizes))(*[int(s) for s in sizes])
+
+    def call(n, p, mode, fl, v, g, m):
+        return _capi.lib().fi_sample_field(src, len(sizes), sz, n, p, mode, fl, v, g, m)
+    return _sample(call, len(sizes), positions, [mem], gradients, cubic, fill)

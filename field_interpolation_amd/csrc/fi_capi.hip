@@ -3,6 +3,7 @@
 #include "fi_solver_internal.h"
 #include "fi_workers.h"
 #include "fi_iso.h"
+#include "fi_sample.h"
 
 namespace fi {
 
@@ -1087,6 +1088,26 @@ int fi_mesh_destroy(fi_mesh* m)
 	return FI_OK;
 }
 
+
+
+// ---- point queries (fi_sample.hip) --------------------------------------------------------------
+int fi_sample(fi_ctx* c, const float* field, long n, const float* positions, int mode, float fill, float* values,
+              float* gradients, int memory)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	fi::sample_ctx(c, field, static_cast<int64_t>(n), positions, mode, fill, values, gradients, memory);
+	FI_API_END
+}
+
+int fi_sample_field(const float* field, int ndim, const int* sizes, long n, const float* positions, int mode, float fill,
+                    float* values, float* gradients, int memory)
+{
+	FI_API_BEGIN
+	fi::sample_field(field, ndim, sizes, static_cast<int64_t>(n), positions, mode, fill, values, gradients, memory);
+	FI_API_END
+}
 
 
 }  // extern "C"

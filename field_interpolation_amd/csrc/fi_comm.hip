@@ -196,7 +196,9 @@ void host_allreduce_vec(fi_ctx* c, void* dev, int64_t count, bool f64)
 		FI_HIP_TRY(hipMemcpyAsync(mine, static_cast<char*>(dev) + o * es, es * n, hipMemcpyDeviceToHost, c->stream));
 		FI_HIP_TRY(hipStreamSynchronize(c->stream));
 		host_barrier(h);
-		sum.assign(static_cast<size_t>(n), 0.0);
+		// from -0.0, the exact identity of IEEE addition: a sum whose terms are all -0.0 stays -0.0, as RCCL's does
+		// (fi_sample's slabs write -0.0 for the points they do not own)
+		sum.assign(static_cast<size_t>(n), -0.0);
 		for (int r = 0; r < c->nranks; ++r) {  // rank order: every rank forms the same bits
 			const char* v = h->slot(r) + 64;
 			for (int64_t k = 0; k < n; ++k) {

@@ -2,6 +2,7 @@
 // geometry, halo widths and ownership rules against the undivided solve on a one-GPU machine).
 #include "fi_solver_internal.h"
 #include "fi_iso.h"
+#include "fi_sample.h"
 
 extern "C" {
 
@@ -247,6 +248,16 @@ int fi_group_iso_extract(fi_group* g, const float* whole_or_null, float iso, fi_
 	for (size_t r = 0; r < g->members.size(); ++r) { out[r] = nullptr; }
 	fi::bind_device(g->members[0]);
 	fi::iso_extract_group(g->members, whole_or_null, iso, out);
+	FI_API_END
+}
+
+int fi_group_sample(fi_group* g, const float* whole_or_null, long n, const float* positions, int mode, float fill,
+                    float* values, float* gradients)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(g != nullptr, FI_ERR_INVALID, "null group");
+	fi::bind_device(g->members[0]);
+	fi::sample_group(g->members, whole_or_null, static_cast<int64_t>(n), positions, mode, fill, values, gradients);
 	FI_API_END
 }
 

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <limits>
 
 #include <fi_hip.h>
 
@@ -246,6 +247,27 @@ bool GpuLatticeField::iso_surface(float iso, std::vector<float>* vertices, std::
 	if (!ok) { warn("iso_surface"); }
 	fi_mesh_destroy(m);
 	return ok;
+}
+
+bool GpuLatticeField::sample(const std::vector<float>& positions, std::vector<float>* values, std::vector<float>* gradients,
+                             bool cubic) const
+{
+	const size_t D = sizes_.size();
+	if (!values || positions.size() % D != 0) {
+		warn("sample");
+		return false;
+	}
+	const size_t n = positions.size() / D;
+	values->resize(n);
+	if (gradients) { gradients->resize(D * n); }
+	// (data() of an empty vector may be null: the library would refuse it, and there is nothing to sample)
+	if (n == 0) { return true; }
+	if (fi_sample(ctx_, nullptr, static_cast<long>(n), positions.data(), cubic ? FI_SAMPLE_CUBIC : FI_SAMPLE_LINEAR,
+	              std::numeric_limits<float>::quiet_NaN(), values->data(), gradients ? gradients->data() : nullptr, FI_HOST) != FI_OK) {
+		warn("sample");
+		return false;
+	}
+	return true;
 }
 
 std::unique_ptr<GpuLatticeField> gpu_sdf_from_points(const std::vector<int>& sizes, const Weights& weights,

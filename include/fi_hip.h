@@ -42,6 +42,9 @@ extern "C" {
 
 #define FI_MAX_DIM 3 /* field_interpolation.hpp:44 */
 
+#define FI_SAMPLE_LINEAR 0 /* fi_sample*: multilinear (the reference's multilerp, field_interpolation.cpp:15-55) */
+#define FI_SAMPLE_CUBIC 1  /* fi_sample*: Catmull-Rom with clamped indices (the SDF app's bicubic_upsample) */
+
 /* field_interpolation.hpp:47-59 */
 #define FI_VALUE_NEAREST_NEIGHBOR 0
 #define FI_VALUE_LINEAR_INTERPOLATION 1
@@ -374,6 +377,10 @@ int     fi_group_error_map(fi_group* g, const float* solution, float* out);
 /* iso-contours of the group's field (see fi_iso_extract below): whole_or_null is the WHOLE lattice on the host, or NULL for
  * the members' last solution; out receives nranks meshes, piece r holding the cells of slab r (see fi_iso_extract). */
 int     fi_group_iso_extract(fi_group* g, const float* whole_or_null, float iso, fi_mesh** out);
+/* point queries of the group's field (see fi_sample below): whole_or_null is the WHOLE lattice, or NULL for the members' last
+ * solution; positions, values and gradients are host buffers, the results are those of the undivided lattice */
+int     fi_group_sample(fi_group* g, const float* whole_or_null, long n, const float* positions, int mode, float fill,
+                        float* values, float* gradients);
 
 /* ---- helpers either side of the path ---------------------------------------------------------
  * Replaces upscale_field (field_interpolation.cpp:431-485): multilinear resampling small -> large. */
@@ -406,6 +413,39 @@ int fi_mesh_info(const fi_mesh* m, long* num_vertices, long* num_primitives, int
 /* any output may be NULL; vertices / normals are ndim floats per vertex, indices vertices_per_primitive int32 per primitive */
 int fi_mesh_copy(const fi_mesh* m, float* vertices, float* normals, int* indices, long long* keys, int memory);
 int fi_mesh_destroy(fi_mesh* m);
+
+/* ---- point queries: values and gradients at arbitrary positions --------------------------------
+ * The contract ("Point queries") is this project's own:
+ *   - positions: n points of ndim fp32 values, interleaved, in global lattice coordinates (x fastest, as fi_add_points);
+ *     every axis needs size >= 2 (else FI_ERR_INVALID);
+ *   - inside: every p_d finite and 0 <= p_d <= n_d - 1; an outside point gets `fill` for its value and every gradient
+ *     component;
+ *   - cell c_d = min((int)floor(p_d), n_d - 2), offset t_d = p_d - c_d in fp32 (exact, in [0, 1]: the upper face uses the
+ *     last cell with t_d = 1);
+ *   - FI_SAMPLE_LINEAR: u_d(0) = 1 - t_d, u_d(1) = t_d; corner i (bit d: +1 along axis d) weighs
+ *     w_i = u_0(b_0) * u_1(b_1) * u_2(b_2), multiplied left to right -- for a point with every p_d < n_d - 1 these are the
+ *     coefficients of the reference's add_value_constraint, bit for bit; value = sum over ascending i of w_i f_i; gradient
+ *     component d = sum over ascending i with bit d clear of W_i^(not d) * (f_(i + 2^d) - f_i), W the product of the u_e,
+ *     e != d, in ascending e (1 in 1-D).  Every sum starts from its first term;
+ *   - FI_SAMPLE_CUBIC: samples c - 1 .. c + 2 along each axis, indices clamped to [0, n_d - 1]; Catmull-Rom
+ *     a = p2 - p0, b = ((2 p0 - 5 p1) + 4 p2) - p3, e = (3 (p1 - p2) + p3) - p0, value p1 + (0.5 t) (a + t (b + t e)),
+ *     derivative 0.5 (a + t (2 b + (3 t) e)); rows reduced along x, then y, then z; gradient component d takes the
+ *     derivative along d and the value along the other axes;
+ *   - fp32 with one rounding per operation; an FI_F64 context sampling its own solution computes in fp64 (t from the
+ *     widened position) and rounds each output to fp32 once.  Non-finite field values propagate.
+ * values: float[n]; gradients: float[n * ndim] or NULL; outputs in input order.  n = 0 is fine; n < 0, NULL positions or
+ * values, a bad mode: FI_ERR_INVALID; n >= 2^31: FI_ERR_UNSUPPORTED.  `memory` applies to every buffer of the call.
+ *
+ * field: the context's owned values in fp32, or NULL for its last solution, read where it lives (FI_ERR_STATE before the first
+ * solve).  On a slab context (nranks > 1, with its transport) the call is collective: every rank passes the same n and
+ * positions and receives every point's result.  Each slab exchanges the ghost planes the mode reads (1 linear, 2 cubic;
+ * FI_ERR_UNSUPPORTED where the context stores fewer, or a cubic call meets slabs thinner than 2 planes) and samples the
+ * points whose slowest cell index c_(ndim-1) lies in its slab; the results are bit-identical to the undivided field's. */
+int fi_sample(fi_ctx* ctx, const float* field, long n, const float* positions, int mode, float fill, float* values,
+              float* gradients, int memory);
+/* the same without a context: any whole field (e.g. the output of fi_upscale_field), fp32, x fastest */
+int fi_sample_field(const float* field, int ndim, const int* sizes, long n, const float* positions, int mode, float fill,
+                    float* values, float* gradients, int memory);
 
 #ifdef __cplusplus
 }

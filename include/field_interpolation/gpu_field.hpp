@@ -63,6 +63,13 @@ public:
 	bool iso_surface(float iso, std::vector<float>* vertices, std::vector<int>* indices,
 	                 std::vector<float>* normals = nullptr) const;
 
+	// Values (and, if asked, gradients: ndim floats per point) of the last solution at `positions` (ndim floats per point,
+	// global lattice coordinates, x fastest), sampled where the solution lives on the device: multilinear, or Catmull-Rom
+	// with cubic = true; points outside the lattice get NaN.  The contract is include/fi_hip.h fi_sample.  false: no
+	// solution yet, or the library refused the call.
+	bool sample(const std::vector<float>& positions, std::vector<float>* values, std::vector<float>* gradients = nullptr,
+	            bool cubic = false) const;
+
 	int    last_iterations() const { return iterations_; }
 	float  last_error() const { return error_; }
 	size_t num_data_rows() const;   // rows accepted from points (what eq.rhs.size() would have grown by)
