@@ -14,7 +14,7 @@ Workloads (--config, named in config.workload; SURVEY.md 8(d) recipes, field_int
     inputs (tests/golden/config4_256*_oracle_f64.npz).  Over slabs (--gpus N > 1) the same rule: every slab's two maxima
     travel with the r . r sum of the iteration's all-reduce (no collective of their own).
     --fast: the fp32 mode of rounds 1-3 as the line's value (coarse-to-fine start + CG preconditioned by a Chebyshev
-    polynomial to residual 1e-5, field error 2e-3); the default run reports it in the `fast` sub-object.
+    polynomial to residual 1e-5, field error 2e-3); a --full run reports it in the `fast` sub-object.
   5: 3-D 512^3 SDF from 5 M oriented points, tol 1e-6: fp64 CG with the V-cycle preconditioner in fp32 (mixed)
   3: 2-D 4096^2 SDF from 200 k oriented points, tol 1e-5: the same solver
   2: 2-D 1024^2, 10 k noisy value constraints, model_2 = 10, tol 1e-5: the same solver
@@ -24,7 +24,8 @@ planes and dot products over RCCL.  --scaling strong (default): the lattice of t
 256 x 256 x (256 N) with N x 1 M points of the same density.  If the slab exchange cannot be set up the run FAILS (exit 3)
 unless --allow-replicas is given; the line then says "replicasN" and its value is not the metric.
 
-Prints ONE JSON line on rank 0 (see the task contract), including
+Prints ONE JSON line on rank 0 (see the task contract).  A plain run does only what its headline needs: it sets up, warms
+up, times --steps steps, writes --dump-outputs and prints the line, which includes
   "roofline"       the dominant kernel of the timed region (largest share of GPU time): algorithmic bytes per launch
                     / mean launch duration measured with HIP events on the solver stream inside
                    the timed region: the Chebyshev steps of the polynomial (k_apply_march3d<..., EPI>: the model-operator
@@ -32,20 +33,24 @@ Prints ONE JSON line on rank 0 (see the task contract), including
                    in the headline solver, the preconditioner in --fast
   "roofline_apply" the same for the full operator apply with fused data cells (the CG SpMV the north-star names; fp64 in
                    the headline solver)
+  "roofline_assembly" SURVEY 8(d)'s assembly bytes (points in, occupied cells' blocks out, diag and Atb out) over the
+                   time of fi_assemble (ALL levels of the hierarchy are built in that time)
+--full (off by default) adds what takes solves, sizes or host work of its own, after the timed steps (--no-accuracy,
+--no-cold, --no-host-io, --no-roofline-512 and --cpu-side 0 leave parts of it out):
+  "solution_rel_err" ||x - x*||_inf / ||x*||_inf against the oracle's fp64 solution where the committed sample covers the
+                   workload (config 4 at 256^3), else against an fp64 GPU solve to 1e-10 (said in config.solution_check);
+                   config.field_accuracy_against_oracle (configs 2, 3, 5): the same settings on the oracle's size
+  "fast"           config 4, N = 1: the fp32 / residual-1e-5 mode: value, ms_per_step, iterations, solution_rel_err
+  "calibrated_residual_r5" config 4 at 256^3, N = 1: the same steps to the residual rounds 4-5 had calibrated (3e-7)
+  "cold_ms_per_step" one step on a fresh context (allocation, power method, first assemble, first solve);
+  "cold_pooled_ms_per_step" the same with the device blocks of a destroyed context (fi_memory_pool)
+  "host_io"        (N = 1) the same step through the boundary's HOST buffers (field_interpolation.hpp:153-173: positions and
+                   values as const float[], the solution as std::vector<float>): pinned staging, the upload of the next data
+                   set and the download of the solution included in the timed region
   "roofline_512"   (N = 1, config 4) that fp64 apply ISOLATED at 512^3 -- the size the north-star's ">= 60 % of the HBM
                    roofline on the CG SpMV" is stated for -- on config 4's value data (8 M points) and on config 5's oriented
                    points (5 M), timed live by fi_time_apply (HIP events around 20 launches), with a plain device copy of a
                    512^3 fp64 vector timed the same way beside it: what one read stream + one write stream reach on this GPU
-  "host_io"        (N = 1) the same step through the boundary's HOST buffers (field_interpolation.hpp:153-173: positions and
-                   values as const float[], the solution as std::vector<float>): pinned staging, the upload of the next data
-                   set and the download of the solution included in the timed region
-  "roofline_assembly" SURVEY 8(d)'s assembly bytes (points in, occupied cells' blocks out, diag and Atb out) over the
-                   time of fi_assemble (ALL levels of the hierarchy are built in that time)
-  "solution_rel_err" ||x - x*||_inf / ||x*||_inf against the oracle's fp64 solution where the committed sample covers the
-                   workload (config 4 at 256^3), else against an fp64 GPU solve to 1e-10 (said in config.solution_check)
-  "fast"           config 4, N = 1: the fp32 / residual-1e-5 mode: value, ms_per_step, iterations, solution_rel_err
-  "cold_ms_per_step" one step on a fresh context (allocation, power method, first assemble, first solve);
-  "cold_pooled_ms_per_step" the same with the device blocks of a destroyed context (fi_memory_pool)
   "cpu_baseline"   the C++ oracle (restatement of the reference's triplets -> AtA -> BiCGSTAB path, fp32, one thread)
                    timed on the same workload at --cpu-side (default: the metric's own 256^3, about a minute; rank 0, N = 1)
   "cpu_best_effort" the same rows solved by a matrix-free Jacobi-PCG with OpenMP on all host cores
@@ -302,8 +307,12 @@ def main():
     ap.add_argument("--points", type=int, default=0, help="data points (default: the configuration's, scaled with the side)")
     ap.add_argument("--dtype", default=None, choices=["f32", "f64"])
     ap.add_argument("--tol", type=float, default=0.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what takes runs of its own: the comparison with the "
+                         "reference solution and the `fast` mode, cold steps, the step through host buffers, the isolated 512^3 "
+                         "apply and the CPU baseline (the --no-* options and --cpu-side 0 leave parts out)")
     ap.add_argument("--cpu-side", type=int, default=256,
-                    help="lattice side of the CPU baseline (default: the metric's own 256^3, about a minute of host time; 0: skip)")
+                    help="--full: lattice side of the CPU baseline (default: the metric's own 256^3, about a minute of host time; 0: skip)")
     ap.add_argument("--fast", action="store_true",
                     help="config 4: the fp32 / residual-1e-5 mode of rounds 1-3 as the line's value (field error 2e-3: outside "
                          "the north-star's tolerance); the default is the solver that meets it")
@@ -315,10 +324,10 @@ def main():
     ap.add_argument("--poly", type=int, default=4, help="terms of the Chebyshev polynomial preconditioner (0: Jacobi-PCG)")
     ap.add_argument("--poly-ratio", type=float, default=30.0)
     ap.add_argument("--no-accuracy", action="store_true",
-                    help="skip the comparison with the reference solution (solution_rel_err) and the `fast` sub-object")
-    ap.add_argument("--no-cold", action="store_true", help="skip the cold-step figure (fresh context)")
-    ap.add_argument("--no-roofline-512", action="store_true", help="skip the isolated 512^3 apply (roofline_512)")
-    ap.add_argument("--no-host-io", action="store_true", help="skip the step through host buffers (host_io)")
+                    help="--full: skip the comparison with the reference solution (solution_rel_err) and the `fast` sub-object")
+    ap.add_argument("--no-cold", action="store_true", help="--full: skip the cold-step figure (fresh context)")
+    ap.add_argument("--no-roofline-512", action="store_true", help="--full: skip the isolated 512^3 apply (roofline_512)")
+    ap.add_argument("--no-host-io", action="store_true", help="--full: skip the step through host buffers (host_io)")
     ap.add_argument("--datasets", type=int, default=3,
                     help="config 4: the timed steps walk through this many seeds of the workload (1-3; every one has an oracle "
                          "golden at 256^3): a re-solve on changed data each step.  1: the same points every step")
@@ -605,7 +614,7 @@ def main():
         if st["iterations"] > 0:
             line["config"]["halo_exchanges_per_iteration"] = st["halo_exchanges"] / float(st["iterations"])
             line["config"]["allreduces_per_iteration"] = st["reductions"] / float(st["iterations"])
-    if world == 1 and not args.no_cold:
+    if args.full and world == 1 and not args.no_cold:
         # Cold step: a FRESH context -- hipMalloc of every vector and list, the power method of the polynomial's bound
         # (fi_set_model: 16 marching launches + 2 host reads per level), the first assemble and a solve whose first look at
         # the stop flag is not scheduled by a previous solve of the same problem.  The timed steps above amortise all
@@ -630,7 +639,7 @@ def main():
         line["cold_note"] = ("fresh context: allocation, the polynomial's power method, first assemble and first solve "
                              "(cold_pooled: the device blocks come from the pool a destroyed context leaves); "
                              "ms_per_step is the steady state of a caller that re-solves on one context")
-    if world == 1 and not args.no_accuracy:
+    if args.full and world == 1 and not args.no_accuracy:
         from field_interpolation_amd import bench_settings as bs
         from field_interpolation_amd import synth
         gdir = os.path.join(ROOT, "tests", "golden")
@@ -772,7 +781,7 @@ def main():
                 "roofline_apply": roof("k_apply_march3d<float>: AtA apply with fused data cells", fst["spmv_bytes"],
                                        fst["spmv_ms_avg"], fst["spmv_samples"], (None, None))}
             del ff, f_out
-    if world == 1 and args.config == 4 and wl.get("by_field") and not args.no_accuracy and not args.side:
+    if args.full and world == 1 and args.config == 4 and wl.get("by_field") and not args.no_accuracy and not args.side:
         # Beside the rule: the residual rounds 4-5 had calibrated against the oracle for exactly this workload (3e-7: five
         # iterations, field 2.9e-6 off) -- what the headline cost before round 6 made the stop rule the same for every
         # workload.  Same steps, same data sets, the field rule switched off.
@@ -791,7 +800,7 @@ def main():
             "note": "the stop rule of rounds 4-5 for THIS workload only (a residual calibrated against the oracle's solution of it); "
                     "not the line's value: the rule above is the same for every configuration and knows no workload"}
         field.set_field_tolerance(wl["field_tol"])
-    if world == 1 and not args.no_host_io:
+    if args.full and world == 1 and not args.no_host_io:
         # The boundary hands over HOST buffers (field_interpolation.hpp:153-173: `const float positions[]`, the solution a
         # std::vector<float>; the C ABI takes either kind).  The same step with its host traffic inside the timed region:
         # every data set lives in pinned host memory, is uploaded for its step, and the solution comes back into pinned host
@@ -877,9 +886,9 @@ def main():
             line["host_io"] = host_io()
         except Exception as e:      # noqa: BLE001 -- a diagnostic leg must not cost the measurement
             line["host_io"] = {"error": "%s: %s" % (type(e).__name__, e)}
-    if rank == 0 and world == 1 and args.config == 4 and not args.no_roofline_512 and not args.side:
+    if args.full and rank == 0 and world == 1 and args.config == 4 and not args.no_roofline_512 and not args.side:
         line["roofline_512"] = roofline_512(fi, torch, dev)
-    if rank == 0 and world == 1 and args.cpu_side > 0 and args.config == 4:
+    if args.full and rank == 0 and world == 1 and args.cpu_side > 0 and args.config == 4:
         line["cpu_baseline"], best_effort = cpu_baseline(args.cpu_side, 1e-5)
         if best_effort:
             line["cpu_best_effort"] = best_effort

@@ -205,15 +205,16 @@ def test_config5_over_eight_slabs_keeps_all_levels(fi):
 
 
 def test_bench_line_contract_single_gpu():
-    """The one JSON line of bench.py at N = 1 (a reduced lattice so that the CPU baseline takes seconds): every field of
-    the measurement contract, the `roofline*` and `cpu_baseline` objects included; the headline is the solver that meets
+    """The one JSON line of bench.py --full at N = 1 (a reduced lattice so that the CPU baseline takes seconds): every field
+    of the measurement contract, the `roofline*` and `cpu_baseline` objects included; the headline is the solver that meets
     the field tolerance (fp64 CG + fp32 V-cycle), the fp32 residual-1e-5 mode sits in `fast`; and the cold figures."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--side", "96", "--cpu-side", "32"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--side", "96", "--cpu-side", "32",
+                        "--full"],
                        cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -249,3 +250,35 @@ def test_bench_line_contract_single_gpu():
     assert d["fast"]["dtype"] == "f32" and d["fast"]["value"] > 0 and d["fast"]["true_rel_residual"] <= 1.5e-5
     assert d["fast"]["solution_rel_err"] > d["solution_rel_err"]
     assert d["cold_ms_per_step"] > 0 and d["cold_pooled_ms_per_step"] > 0
+
+
+def test_bench_plain_line_single_gpu(tmp_path):
+    """A plain run of bench.py (no --full) at N = 1: the headline fields of the contract, the figures of the timed region,
+    the outputs of the last timed step, and none of what takes runs of its own."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = str(tmp_path / "dump")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--side", "96",
+                        "--dump-outputs", out], cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config",
+              "roofline", "roofline_apply", "roofline_assembly"):
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["unit"] == "lattice points/s" and d["metric"].startswith("solved lattice points/sec")
+    assert abs(d["value"] - 96 ** 3 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert "V-cycle PCG" in d["config"]["solver"] and d["config"]["true_rel_residual"] <= 1e-6
+    for k in ("solution_rel_err", "fast", "calibrated_residual_r5", "cold_ms_per_step", "cold_pooled_ms_per_step", "host_io",
+              "roofline_512", "cpu_baseline", "cpu_best_effort"):
+        assert k not in d, k
+    assert "solution_check" not in d["config"] and "field_tolerance_met" not in d["config"]
+    x = np.load(os.path.join(out, "solution.npy"))
+    assert x.dtype == np.float32 and x.shape == (96 ** 3,) and np.isfinite(x).all()
+    assert int(np.load(os.path.join(out, "iterations.npy"))) == d["config"]["iterations"]
+    assert float(np.load(os.path.join(out, "rel_residual.npy"))) == d["config"]["rel_residual"]

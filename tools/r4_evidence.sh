@@ -16,7 +16,7 @@ case $part in
   c3)      ARGS="--cpu-side 0 --config 3 --no-accuracy"; PMC=0 ;;
   c2)      ARGS="--cpu-side 0 --config 2 --no-accuracy"; PMC=0 ;;
 esac
-python bench.py --steps 3 --warmup 1 $ARGS > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+python bench.py --full --steps 3 --warmup 1 $ARGS > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --steps 3 --warmup 1 $ARGS --no-accuracy --no-cold > $O/trace.log 2>&1; echo "trace rc=$?"
 python3 $R/tools/trace_by_grid.py $O/trace > $O/by_grid.md

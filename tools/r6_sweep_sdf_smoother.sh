@@ -9,7 +9,7 @@ cfg=${CONFIG:-5}
 for deg in ${DEGREES:-3 4 5 6}; do
   for ratio in ${RATIOS:-10 20 40}; do
     out=gpurun_out/r6/smoother_c${cfg}_d${deg}_r${ratio}.json
-    FI_MG_DEGREE=$deg FI_MG_RATIO=$ratio python bench.py --config $cfg --steps 2 --warmup 1 --no-cold --cpu-side 0 "$@" > $out 2>/dev/null || { echo "config $cfg degree $deg ratio $ratio failed"; continue; }
+    FI_MG_DEGREE=$deg FI_MG_RATIO=$ratio python bench.py --full --config $cfg --steps 2 --warmup 1 --no-cold --cpu-side 0 "$@" > $out 2>/dev/null || { echo "config $cfg degree $deg ratio $ratio failed"; continue; }
     echo -n "config $cfg degree $deg ratio $ratio: "; python3 tools/bench_brief.py $out
   done
 done
