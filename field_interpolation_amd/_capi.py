@@ -23,6 +23,7 @@ SYMBOLS = [
     "fi_group_solve_cg", "fi_group_apply_AtA_f64", "fi_group_true_residual", "fi_group_get_solution_f64", "fi_group_tile_pass", "fi_group_error_map",
     "fi_group_iso_extract", "fi_iso_extract", "fi_iso_extract_field", "fi_mesh_info", "fi_mesh_copy", "fi_mesh_destroy",
     "fi_group_sample", "fi_sample", "fi_sample_field",
+    "fi_nearest", "fi_distance_field", "fi_points_create", "fi_points_nearest", "fi_points_distance_field", "fi_points_destroy",
 ]
 
 
@@ -128,6 +129,12 @@ def lib():
     L.fi_group_sample.argtypes = [vp, fp, C.c_long, fp, C.c_int, C.c_float, fp, fp]
     L.fi_sample.argtypes = [vp, fp, C.c_long, fp, C.c_int, C.c_float, fp, fp, C.c_int]
     L.fi_sample_field.argtypes = [fp, C.c_int, ip, C.c_long, fp, C.c_int, C.c_float, fp, fp, C.c_int]
+    L.fi_nearest.argtypes = [vp, C.c_long, fp, C.c_float, fp, vp, C.c_int]
+    L.fi_distance_field.argtypes = [vp, C.c_float, fp, vp, C.c_int]
+    L.fi_points_create.argtypes = [C.POINTER(vp), C.c_int, C.c_long, fp, C.c_int]
+    L.fi_points_nearest.argtypes = [vp, C.c_long, fp, C.c_float, fp, vp, C.c_int]
+    L.fi_points_distance_field.argtypes = [vp, ip, C.c_float, fp, vp, C.c_int]
+    L.fi_points_destroy.argtypes = [vp]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError if the .so lacks a declared symbol
     _LIB = L

@@ -143,6 +143,87 @@ def _sample(call, ndim, positions, other_memory, gradients, cubic, fill):
     return (vals, grads) if gradients else vals
 
 
+def _nearest(call, ndim, queries, max_distance, indices):
+    """Shared body of the nearest-point queries: call(n, queries, max_distance, distances, indices, memory) is the C entry
+    point.  Outputs live where `queries` lives: numpy in, numpy out; a torch tensor in, torch tensors out on its device."""
+    q, qmem, qkeep = _buf(queries)
+    count = qkeep.numel() if hasattr(qkeep, "numel") else qkeep.size
+    if count % ndim:
+        raise ValueError("queries: %d values, not a multiple of ndim = %d (x fastest)" % (count, ndim))
+    n = count // ndim
+    if hasattr(qkeep, "data_ptr"):
+        import torch
+        dist = torch.empty(n, dtype=torch.float32, device=qkeep.device)
+        idx = torch.empty(n, dtype=torch.int64, device=qkeep.device) if indices else None
+        if n == 0:      # (an empty tensor has no storage to point at)
+            return (dist, idx) if indices else dist
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    else:
+        dist = np.empty(n, np.float32)
+        idx = np.empty(n, np.int64) if indices else None
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+    check(call(n, q, float(max_distance), ptr(dist), ptr(idx), qmem))
+    return (dist, idx) if indices else dist
+
+
+def _distance_field(call, total, indices, device):
+    """Shared body of the distance fields: call(distances, indices, memory); numpy arrays of `total` values (x fastest), or
+    torch tensors on the current GPU with device=True."""
+    if device:
+        import torch
+        dist = torch.empty(total, dtype=torch.float32, device="cuda")
+        idx = torch.empty(total, dtype=torch.int64, device="cuda") if indices else None
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        mem = FI_DEVICE
+    else:
+        dist = np.empty(total, np.float32)
+        idx = np.empty(total, np.int64) if indices else None
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+        mem = FI_HOST
+    check(call(ptr(dist), ptr(idx), mem))
+    return (dist, idx) if indices else dist
+
+
+class PointIndex:
+    """Exact nearest points of a point set of its own, searched on the device (include/fi_hip.h fi_points_create; the
+    contract is fi_nearest's).  positions: (n, ndim) -- or (n,) in 1-D -- numpy array or torch tensor, x fastest; a point's
+    index is its row."""
+
+    def __init__(self, positions, ndim=None):
+        p, mem, keep = _buf(positions)
+        shape = tuple(keep.shape)
+        self.ndim = int(ndim) if ndim is not None else (shape[-1] if len(shape) == 2 else 1)
+        count = keep.numel() if hasattr(keep, "numel") else keep.size
+        if count % self.ndim:
+            raise ValueError("positions: %d values, not a multiple of ndim = %d (x fastest)" % (count, self.ndim))
+        self.num_points = count // self.ndim
+        self._h = C.c_void_p()
+        check(_capi.lib().fi_points_create(C.byref(self._h), self.ndim, self.num_points, p if count else None, mem))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _capi._LIB is not None:
+            _capi._LIB.fi_points_destroy(h)
+        self._h = None
+
+    def nearest(self, queries, max_distance=math.inf, indices=False):
+        """Distances (n,) float32 -- and with indices=True also the indices (n,) int64 -- of the nearest point of the set to
+        each of `queries` (n x ndim): +inf / -1 beyond max_distance or with no finite point, NaN / -1 for a non-finite query."""
+        def call(n, q, md, d, i, mem):
+            return _capi.lib().fi_points_nearest(self._h, n, q, md, d, i, mem)
+        return _nearest(call, self.ndim, queries, max_distance, indices)
+
+    def distance_field(self, sizes, max_distance=math.inf, indices=False, device=False):
+        """PointIndex.nearest of every point of a lattice of `sizes` (x fastest), flat."""
+        if len(sizes) != self.ndim:
+            raise ValueError("sizes: %d extents for a %d-D point set" % (len(sizes), self.ndim))
+        sz = (C.c_int * len(sizes))(*[int(s) for s in sizes])
+
+        def call(d, i, mem):
+            return _capi.lib().fi_points_distance_field(self._h, sz, float(max_distance), d, i, mem)
+        return _distance_field(call, int(np.prod(sizes)), indices, device)
+
+
 class LatticeField:
     """field_interpolation.hpp:97-114 `LatticeField{sizes}`: sizes[0] (x) is the fastest axis.
 
@@ -358,6 +439,20 @@ class LatticeField:
         def call(n, p, mode, fl, v, g, mem):
             return _capi.lib().fi_sample(self._h, s, n, p, mode, fl, v, g, mem)
         return _sample(call, len(self.sizes), positions, [smem], gradients, cubic, fill)
+
+    def nearest(self, queries, max_distance=math.inf, indices=False):
+        """PointIndex.nearest over the data points of this context: every add_points batch in call order, the border prior's
+        rows left out (include/fi_hip.h fi_nearest).  The search structure is built at the first query and kept until the
+        next add_points / clear_points."""
+        def call(n, q, md, d, i, mem):
+            return _capi.lib().fi_nearest(self._h, n, q, md, d, i, mem)
+        return _nearest(call, len(self.sizes), queries, max_distance, indices)
+
+    def distance_field(self, max_distance=math.inf, indices=False, device=False):
+        """LatticeField.nearest of every lattice point (x fastest), flat: numpy arrays, or torch tensors with device=True."""
+        def call(d, i, mem):
+            return _capi.lib().fi_distance_field(self._h, float(max_distance), d, i, mem)
+        return _distance_field(call, self.num_unknowns, indices, device)
 
     def set_verify_residual(self, on):
         """FI_OPT_VERIFY_RESIDUAL: True (default) checks b - A x at convergence and restarts CG if fp32 drift

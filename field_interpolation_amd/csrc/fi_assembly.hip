@@ -22,6 +22,7 @@
 
 #include "fi_internal.h"
 #include "fi_sort.h"
+#include "fi_nearest.h"
 
 namespace fi {
 
@@ -1256,8 +1257,9 @@ void assemble_dim(fi_ctx* c)
 // Every lattice point on the border of the lattice gets the value row [1] * w = d * w, d = the distance to the nearest
 // data point -- "far from the surface the field is positive and about the distance".  The reference loops over the
 // border points and, for each, over all points (O(border x points), fp32: dx*dx + dy*dy, min, sqrt).  Here: the border
-// points are enumerated in lattice order by a stream compaction of the index range (no lattice-sized buffer), one
-// thread per border point walks the point batches in LDS tiles of 256 positions with the same fp32 arithmetic, and
+// points are enumerated in lattice order by a stream compaction of the index range (no lattice-sized buffer), each finds
+// its nearest data point by the exact tree search of fi_nearest.hip (the same fp32 sums, the same minimum; FI_BORDER_BRUTE:
+// one thread per border point walks the point batches in LDS tiles of 256 positions, as the reference loops), and
 // the rows enter the assembly as a batch of nearest-neighbour value constraints AT the lattice points
 // (field_interpolation.cpp:82-107 with a zero gradient gives exactly the row [1] * w, rhs value * w).
 namespace {
@@ -1363,14 +1365,36 @@ int64_t border_prior_points(fi_ctx* c, DevBuf& pos, DevBuf& val)
 	pos.alloc(sizeof(float) * nb * D);
 	val.alloc(sizeof(float) * nb);
 	const int blocks = static_cast<int>((nb + 255) / 256);
-	hipLaunchKernelGGL(k_fill_f32, dim3(blocks), dim3(256), 0, st, static_cast<int64_t>(nb), INFINITY, d2.as<float>());
-	for (const PointBatch* b : c->batches) {
-		if (b->n <= 0 || b->prior) { continue; }
-		switch (D) {
-		case 1: hipLaunchKernelGGL(k_border_min_dist<1>, dim3(blocks), dim3(256), 0, st, static_cast<int64_t>(nb), idx.as<uint32_t>(), pred, b->n, b->pos.as<float>(), d2.as<float>()); break;
-		case 2: hipLaunchKernelGGL(k_border_min_dist<2>, dim3(blocks), dim3(256), 0, st, static_cast<int64_t>(nb), idx.as<uint32_t>(), pred, b->n, b->pos.as<float>(), d2.as<float>()); break;
-		default: hipLaunchKernelGGL(k_border_min_dist<3>, dim3(blocks), dim3(256), 0, st, static_cast<int64_t>(nb), idx.as<uint32_t>(), pred, b->n, b->pos.as<float>(), d2.as<float>()); break;
+	if (test_switch("FI_BORDER_BRUTE")) {  // the reference's loop over every (border point, data point) pair
+		hipLaunchKernelGGL(k_fill_f32, dim3(blocks), dim3(256), 0, st, static_cast<int64_t>(nb), INFINITY, d2.as<float>());
+		for (const PointBatch* b : c->batches) {
+			if (b->n <= 0 || b->prior) { continue; }
+			switch (D) {
+			case 1: hipLaunchKernelGGL(k_border_min_dist<1>, dim3(blocks), dim3(256), 0, st, static_cast<int64_t>(nb), idx.as<uint32_t>(), pred, b->n, b->pos.as<float>(), d2.as<float>()); break;
+			case 2: hipLaunchKernelGGL(k_border_min_dist<2>, dim3(blocks), dim3(256), 0, st, static_cast<int64_t>(nb), idx.as<uint32_t>(), pred, b->n, b->pos.as<float>(), d2.as<float>()); break;
+			default: hipLaunchKernelGGL(k_border_min_dist<3>, dim3(blocks), dim3(256), 0, st, static_cast<int64_t>(nb), idx.as<uint32_t>(), pred, b->n, b->pos.as<float>(), d2.as<float>()); break;
+			}
 		}
+	} else {
+		// the exact search of fi_nearest.hip: the same minimum of the same fp32 sums (a non-finite point is never below +inf
+		// in the loop above and is left out of the search).  The context's cached structure if a query built one, else one
+		// for this call alone: the prior keeps no buffers behind it.
+		NearestIndex        own;
+		const NearestIndex* t = c->nearest;
+		if (!t) {
+			std::vector<const float*> seg;
+			std::vector<int64_t>      cnt;
+			int64_t                   npts = 0;
+			for (const PointBatch* b : c->batches) {
+				if (b->n <= 0 || b->prior) { continue; }
+				seg.push_back(b->pos.as<float>());
+				cnt.push_back(b->n);
+				npts += b->n;
+			}
+			nearest_build(own, D, npts, seg.data(), cnt.data(), static_cast<int>(seg.size()), st);
+			t = &own;
+		}
+		nearest_lattice_list_d2(*t, pred.n, nb, idx.as<uint32_t>(), d2.as<float>(), st);
 	}
 	switch (D) {
 	case 1: hipLaunchKernelGGL(k_border_finish<1>, dim3(blocks), dim3(256), 0, st, static_cast<int64_t>(nb), idx.as<uint32_t>(), pred, d2.as<float>(), pos.as<float>(), val.as<float>()); break;

@@ -4,6 +4,9 @@
 #include "fi_workers.h"
 #include "fi_iso.h"
 #include "fi_sample.h"
+#include "fi_nearest.h"
+
+#include <memory>
 
 namespace fi {
 
@@ -209,6 +212,7 @@ int fi_ctx_destroy(fi_ctx* c)
 		(void)hipEventDestroy(c->ev_asm1);
 	}
 	if (c->stream && c->owns_stream) { fi::stream_give(c->stream, drained); }
+	fi::nearest_release(c);
 	delete c;
 	return FI_OK;
 }
@@ -328,6 +332,7 @@ int fi_add_points(fi_ctx* c, long n, const float* positions, const float* normal
 		w = up(dpw, point_weights, static_cast<size_t>(n));
 		v = up(dval, values, static_cast<size_t>(n));
 	}
+	fi::nearest_release(c);  // (a new point set)
 	fi::add_points_device(c, n, p, g, w, v, value_weight, value_kernel, gradient_weight, gradient_kernel);
 	c->assembled = false;
 	FI_API_END
@@ -428,6 +433,7 @@ int fi_clear_points(fi_ctx* c)
 	c->pending.clear();
 	for (auto* b : c->batches) { c->batches_pool.push_back(b); }
 	c->batches.clear();
+	fi::nearest_release(c);
 	fi::generic_clear(c);
 	c->assembled = false;
 	FI_API_END
@@ -1107,6 +1113,118 @@ int fi_sample_field(const float* field, int ndim, const int* sizes, long n, cons
 	FI_API_BEGIN
 	fi::sample_field(field, ndim, sizes, static_cast<int64_t>(n), positions, mode, fill, values, gradients, memory);
 	FI_API_END
+}
+
+
+// ---- nearest data points (fi_nearest.hip) -------------------------------------------------------
+namespace {
+void check_nearest(long n, const float* queries, float max_distance, const float* distances, int memory)
+{
+	FI_REQUIRE(n >= 0, FI_ERR_INVALID, "n = %ld", n);
+	FI_REQUIRE(queries != nullptr && distances != nullptr, FI_ERR_INVALID, "null queries or distances");
+	FI_REQUIRE(max_distance >= 0.0f, FI_ERR_INVALID, "max_distance must be >= 0 (got %g)", static_cast<double>(max_distance));  // (NaN fails)
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	// (one thread per query, 32-bit counts)
+	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld queries in one call", n);
+}
+
+void check_field_out(float max_distance, const float* out, int memory)
+{
+	FI_REQUIRE(out != nullptr, FI_ERR_INVALID, "out is null");
+	FI_REQUIRE(max_distance >= 0.0f, FI_ERR_INVALID, "max_distance must be >= 0 (got %g)", static_cast<double>(max_distance));
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+}
+
+// the border prior's reason: a slab context holds only the points near its slab
+void check_undivided(const fi_ctx* c)
+{
+	FI_REQUIRE(c->nranks == 1, FI_ERR_UNSUPPORTED, "nearest points on a slab context: a rank sees only its own points");
+}
+
+void check_points(const fi_points* h)
+{
+	FI_REQUIRE(h != nullptr, FI_ERR_INVALID, "point set is null");
+	FI_HIP_TRY(hipSetDevice(h->device));
+}
+}  // namespace
+
+int fi_nearest(fi_ctx* c, long n, const float* queries, float max_distance, float* distances, long long* indices, int memory)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	check_nearest(n, queries, max_distance, distances, memory);
+	check_undivided(c);
+	if (n == 0) { return FI_OK; }
+	fi::nearest_query(fi::nearest_of(c), n, queries, max_distance, distances, indices, memory, c->stream);
+	FI_API_END
+}
+
+int fi_distance_field(fi_ctx* c, float max_distance, float* out, long long* indices, int memory)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	check_field_out(max_distance, out, memory);
+	check_undivided(c);
+	fi::nearest_lattice(fi::nearest_of(c), c->g.gn, max_distance, out, indices, memory, c->stream);
+	FI_API_END
+}
+
+int fi_points_create(fi_points** out, int ndim, long n, const float* positions, int memory)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(out != nullptr, FI_ERR_INVALID, "out is null");
+	*out = nullptr;
+	FI_REQUIRE(1 <= ndim && ndim <= FI_MAX_DIM, FI_ERR_INVALID, "ndim must be 1..%d (got %d)", FI_MAX_DIM, ndim);
+	FI_REQUIRE(n >= 0, FI_ERR_INVALID, "n = %ld", n);
+	FI_REQUIRE(n == 0 || positions != nullptr, FI_ERR_INVALID, "positions is null");
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld points: nearest-point indices are 32-bit", n);
+	std::unique_ptr<fi_points> h(new fi_points());
+	FI_HIP_TRY(hipGetDevice(&h->device));
+	fi::DevBuf   buf;
+	const float* p = positions;
+	if (n > 0 && memory == FI_HOST) {
+		buf.alloc(sizeof(float) * ndim * n);
+		FI_HIP_TRY(hipMemcpy(buf.p, positions, sizeof(float) * ndim * n, hipMemcpyHostToDevice));
+		p = buf.as<float>();
+	}
+	const int64_t cnt = n;
+	fi::nearest_build(h->t, ndim, cnt, &p, &cnt, 1, nullptr);
+	*out = h.release();
+	FI_API_END
+}
+
+int fi_points_nearest(fi_points* h, long n, const float* queries, float max_distance, float* distances, long long* indices,
+                      int memory)
+{
+	FI_API_BEGIN
+	check_points(h);
+	check_nearest(n, queries, max_distance, distances, memory);
+	fi::nearest_query(h->t, n, queries, max_distance, distances, indices, memory, nullptr);
+	FI_API_END
+}
+
+int fi_points_distance_field(fi_points* h, const int* sizes, float max_distance, float* out, long long* indices, int memory)
+{
+	FI_API_BEGIN
+	check_points(h);
+	FI_REQUIRE(sizes != nullptr, FI_ERR_INVALID, "sizes is null");
+	for (int d = 0; d < h->t.D; ++d) { FI_REQUIRE(sizes[d] >= 1, FI_ERR_INVALID, "sizes[%d] = %d", d, sizes[d]); }
+	check_field_out(max_distance, out, memory);
+	fi::nearest_lattice(h->t, sizes, max_distance, out, indices, memory, nullptr);
+	FI_API_END
+}
+
+int fi_points_destroy(fi_points* h)
+{
+	if (!h) { return FI_OK; }
+	int dev = 0;
+	const bool switched = hipGetDevice(&dev) == hipSuccess && dev != h->device && hipSetDevice(h->device) == hipSuccess;
+	delete h;
+	if (switched) { (void)hipSetDevice(dev); }
+	return FI_OK;
 }
 
 

@@ -17,7 +17,7 @@ namespace fi {
 
 // ---- environment switches ------------------------------------------------------------------------------
 // test_switch: alternative code paths the test-suite compares with each other (FI_NO_FUSE, FI_NO_MARCH, FI_NO_TILE2D,
-// FI_NO_GATHER, FI_NO_PACK, FI_NO_OVERLAP, FI_ZC) -- every one of them computes the same answers; present in the shipped
+// FI_NO_GATHER, FI_NO_PACK, FI_NO_OVERLAP, FI_ZC, FI_BORDER_BRUTE) -- every one of them computes the same answers; present in the shipped
 // library.  tuning_switch: experiment knobs of the ablations in profiles/ (chunk shapes, smoother degrees, launch
 // structure) and the FI_DBG timing modes whose results are wrong by construction: compiled in only with
 // -DFI_TIMING_BUILD (tools/build_variant.sh); the shipped library never reads them.
@@ -308,6 +308,7 @@ struct PointBatch {
 };
 
 struct Comm;  // RCCL state (fi_comm.cpp)
+struct NearestIndex;  // the nearest-point search structure of a context's points (fi_nearest.h)
 
 struct CgScalars {  // lives in device memory; kernels read/write it, the host polls it
 	double rz, rz_new, pq, rr, bb, tol2, alpha, beta, true_rr;
@@ -357,6 +358,7 @@ struct fi_ctx {
 	std::vector<fi::Pending*> pending;
 	std::vector<fi::Pending*> pending_pool;  // buffers of cleared batches, reused by the next fi_add_points
 	std::vector<fi::PointBatch*> batches, batches_pool;  // the points themselves (for coarser levels)
+	fi::NearestIndex* nearest = nullptr;  // built by the first nearest-point query, dropped by fi_add_points / fi_clear_points
 
 	// multilevel: coarser replicas of this problem (lattice halved per level), owned by the finest context
 	int        levels_wanted = 0;

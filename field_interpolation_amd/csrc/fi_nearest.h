@@ -1,0 +1,44 @@
+// fi_nearest.h -- exact nearest data points on the device (fi_nearest.hip), shared by the C ABI unit (fi_capi.hip) and the
+// border prior (fi_assembly.hip).
+#pragma once
+
+#include "fi_internal.h"
+
+namespace fi {
+
+// The search structure over one point set: the finite points sorted by their Morton code (over their own bounding box),
+// float4 each (x, y, z, the point's index as bits), and an implicit balanced binary tree over leaves of kNearestLeaf
+// consecutive points: node k (root 1, children 2k and 2k + 1) keeps its box as two float4 (lo, hi) at box[2k], box[2k + 1];
+// leaf j is node P + j.  Built once, read by any number of queries.
+struct NearestIndex {
+	int     D  = 0;
+	int64_t n  = 0;   // points of the set (finite or not)
+	int64_t nf = 0;   // finite points: the tree's
+	int     H  = 0;   // tree depth: P = 2^H leaves (the last ones may be empty)
+	DevBuf  pts, box;
+};
+
+// the set of a context: its fi_add_points batches in call order, the border prior's left out (PointBatch::prior); built on
+// the context's stream, kept in c->nearest until the next fi_add_points / fi_clear_points
+const NearestIndex& nearest_of(fi_ctx* c);
+void                nearest_release(fi_ctx* c);
+// a set built from n positions of ndim floats already on the device
+void nearest_build(NearestIndex& t, int ndim, int64_t n, const float* const* seg_pos, const int64_t* seg_n, int nseg, hipStream_t st);
+
+// The queries of the C ABI (include/fi_hip.h fi_nearest): queries / distances / indices in `memory`; indices may be null.
+void nearest_query(const NearestIndex& t, int64_t n, const float* queries, float max_distance, float* distances,
+                   long long* indices, int memory, hipStream_t st);
+// every point of a lattice (x fastest) as a query
+void nearest_lattice(const NearestIndex& t, const int* sizes, float max_distance, float* distances, long long* indices, int memory,
+                     hipStream_t st);
+// the border prior: the lattice points idx[0 .. nb) (linear indices of the lattice n[0 .. D)) as queries; d2 receives the
+// SQUARED distance (the minimum of s, +inf with no finite point) on the device, enqueued on st
+void nearest_lattice_list_d2(const NearestIndex& t, const int* n, int64_t nb, const uint32_t* idx, float* d2, hipStream_t st);
+
+}  // namespace fi
+
+// a point set of its own (fi_points_create, include/fi_hip.h): its search structure on the device it was created on
+struct fi_points {
+	int              device = 0;
+	fi::NearestIndex t;
+};

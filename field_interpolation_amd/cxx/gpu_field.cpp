@@ -270,6 +270,42 @@ bool GpuLatticeField::sample(const std::vector<float>& positions, std::vector<fl
 	return true;
 }
 
+bool GpuLatticeField::nearest(const std::vector<float>& queries, std::vector<float>* distances, std::vector<long long>* indices,
+                              float max_distance) const
+{
+	const size_t D = sizes_.size();
+	if (!distances || queries.size() % D != 0) {
+		warn("nearest");
+		return false;
+	}
+	const size_t n = queries.size() / D;
+	distances->resize(n);
+	if (indices) { indices->resize(n); }
+	// (data() of an empty vector may be null: the library would refuse it, and there is nothing to search)
+	if (n == 0) { return true; }
+	if (fi_nearest(ctx_, static_cast<long>(n), queries.data(), max_distance, distances->data(), indices ? indices->data() : nullptr,
+	               FI_HOST) != FI_OK) {
+		warn("nearest");
+		return false;
+	}
+	return true;
+}
+
+bool GpuLatticeField::distance_field(std::vector<float>* distances, std::vector<long long>* indices, float max_distance) const
+{
+	if (!distances) {
+		warn("distance_field");
+		return false;
+	}
+	distances->resize(num_unknowns());
+	if (indices) { indices->resize(num_unknowns()); }
+	if (fi_distance_field(ctx_, max_distance, distances->data(), indices ? indices->data() : nullptr, FI_HOST) != FI_OK) {
+		warn("distance_field");
+		return false;
+	}
+	return true;
+}
+
 std::unique_ptr<GpuLatticeField> gpu_sdf_from_points(const std::vector<int>& sizes, const Weights& weights,
                                                      int num_points, const float positions[], const float* normals,
                                                      const float* point_weights)

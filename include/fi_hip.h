@@ -195,8 +195,9 @@ int fi_add_points(fi_ctx* ctx, long n, const float* positions, const float* norm
 /* The border prior of the reference's SDF application (src/sdf_field.cpp:218-246, generate_sdf_field with
  * boundary_weight > 0): every lattice point on the border of the lattice gets the row [1] * weight = d * weight, d = its
  * distance to the nearest data point given to fi_add_points so far (fp32: sum of squared coordinate differences, min,
- * sqrt -- the reference's arithmetic).  Brute force O(border x points) like the reference, on the device; the rows join the
- * data rows (and the coarser levels).  Call it after fi_add_points, before fi_assemble.  weight == 0 adds nothing. */
+ * sqrt -- the reference's arithmetic).  The distance is fi_nearest's (an exact tree search, bit-identical to the reference's
+ * O(border x points) loop, which the environment switch FI_BORDER_BRUTE still runs); a slab context: FI_ERR_UNSUPPORTED.  The
+ * rows join the data rows (and the coarser levels).  Call it after fi_add_points, before fi_assemble.  weight == 0 adds nothing. */
 int fi_add_border_prior(fi_ctx* ctx, float weight);
 
 /* Generic rows: replaces handing an arbitrary `LinearEquation` (sparse_linear.hpp:18-22) to the solvers,
@@ -362,6 +363,7 @@ int fi_time_apply(fi_ctx* ctx, int reps, double* ms_per_launch);
  * calls above; vectors passed to the group calls are host buffers holding the WHOLE lattice. */
 typedef struct fi_group fi_group;
 typedef struct fi_mesh fi_mesh;
+typedef struct fi_points fi_points;
 int     fi_group_create(fi_group** out, int ndim, const int* sizes, int dtype, int nranks);
 int     fi_group_destroy(fi_group* g);
 int     fi_group_size(const fi_group* g);
@@ -446,6 +448,35 @@ int fi_sample(fi_ctx* ctx, const float* field, long n, const float* positions, i
 /* the same without a context: any whole field (e.g. the output of fi_upscale_field), fp32, x fastest */
 int fi_sample_field(const float* field, int ndim, const int* sizes, long n, const float* positions, int mode, float fill,
                     float* values, float* gradients, int memory);
+
+/* ---- nearest data points ------------------------------------------------------------------------
+ * The contract ("Nearest data points") is this project's own:
+ *   - the point set of a context: the positions of every fi_add_points batch in call order (fi_add_border_prior's rows are
+ *     not data points); points outside the lattice count.  A point's index is its position in that concatenation.  A point
+ *     with a non-finite coordinate is never nearest;
+ *   - s(p, q): an fp32 sum from 0.0f of (p_d - q_d)^2 for d = 0, 1, 2 in ascending order, one rounding per operation (no FMA
+ *     contraction) -- the arithmetic of the reference's border-prior loop;
+ *   - a query q: best = the minimum of s over the finite points, distance = sqrtf(best), index = the smallest index with
+ *     s == best.  No finite point: +inf and index -1; a query with a non-finite coordinate: NaN and index -1;
+ *     sqrtf(best) > max_distance (>= 0, may be +inf): +inf and index -1;
+ *   - results in input order: distances float[n], indices long long[n] (or NULL); they depend neither on the launch shape
+ *     nor on timing.
+ * n = 0 is fine.  n < 0, NULL queries or distances, a NaN or negative max_distance, a bad memory kind: FI_ERR_INVALID;
+ * n >= 2^31 (queries or points): FI_ERR_UNSUPPORTED.  `memory` applies to every buffer of the call.
+ *
+ * A context builds its search structure at its first query and keeps it until the next fi_add_points or fi_clear_points.  A
+ * slab context (nranks > 1) holds only the points near its slab: FI_ERR_UNSUPPORTED, as for fi_add_border_prior. */
+int fi_nearest(fi_ctx* ctx, long n, const float* queries, float max_distance, float* distances, long long* indices, int memory);
+/* every lattice point of the context (x fastest) as a query: out float[total], indices long long[total] or NULL */
+int fi_distance_field(fi_ctx* ctx, float max_distance, float* out, long long* indices, int memory);
+
+/* The same without a context: a point set of n positions (ndim = 1..3 floats each, interleaved, host or device), searched
+ * on the current device.  A lattice of `sizes` (ndim extents >= 1, fewer than 2^31 points) for the distance field. */
+int fi_points_create(fi_points** out, int ndim, long n, const float* positions, int memory);
+int fi_points_nearest(fi_points* points, long n, const float* queries, float max_distance, float* distances, long long* indices,
+                      int memory);
+int fi_points_distance_field(fi_points* points, const int* sizes, float max_distance, float* out, long long* indices, int memory);
+int fi_points_destroy(fi_points* points);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,7 @@
 // everything goes straight to libfi_hip (include/fi_hip.h).
 #pragma once
 
+#include <limits>
 #include <memory>
 #include <vector>
 
@@ -69,6 +70,16 @@ public:
 	// solution yet, or the library refused the call.
 	bool sample(const std::vector<float>& positions, std::vector<float>* values, std::vector<float>* gradients = nullptr,
 	            bool cubic = false) const;
+
+	// Exact nearest data points: for each of `queries` (ndim floats per point, lattice units, x fastest) the distance to the
+	// nearest point given to add_points so far (the border prior's rows are not data points) and, if asked, that point's index
+	// in the order the points were added; +inf / -1 beyond max_distance or without points, NaN / -1 for a non-finite query.
+	// The contract is include/fi_hip.h fi_nearest.  false: the library refused the call.
+	bool nearest(const std::vector<float>& queries, std::vector<float>* distances, std::vector<long long>* indices = nullptr,
+	             float max_distance = std::numeric_limits<float>::infinity()) const;
+	// nearest() of every lattice point (x fastest): num_unknowns() distances (and indices)
+	bool distance_field(std::vector<float>* distances, std::vector<long long>* indices = nullptr,
+	                    float max_distance = std::numeric_limits<float>::infinity()) const;
 
 	int    last_iterations() const { return iterations_; }
 	float  last_error() const { return error_; }
