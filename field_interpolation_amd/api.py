@@ -481,7 +481,10 @@ class LatticeField:
         """FI_OPT_FIELD_TOLERANCE (V-cycle PCG; undivided lattices and up to 16 slabs): stop when the field is within `tol` (relative, maximum
         norm) of the converged solution by the solver's own measure -- the last step times sigma / (1 - sigma), sigma the
         slowest mean decay of the residual norm over the recent windows and the whole solve, doubled (include/fi_hip.h) --
-        instead of at a residual; the `tol` of solve_cg is then ignored.  0: the residual rule.  stats(): field_estimate, field_per_residual, stop_residual."""
+        instead of at a residual; the `tol` of solve_cg is then ignored.  0: the residual rule.  stats(): field_estimate, field_per_residual,
+        stop_residual, field_rounds (1 only when the field test ended the solve).  Where the rule cannot run -- multigrid off,
+        no coarser level built (a small lattice, add_rows_coo rows), more than 16 slabs, a finest level of replicated copies --
+        the solve stops by the residual at solve_cg's `tol` and stats() says so: field_estimate -1, field_rounds 0."""
         check(_capi.lib().fi_set_option(self._h, 12, float(tol)))
 
     def set_cheb_smoother(self, degree=0, ratio=0.0):

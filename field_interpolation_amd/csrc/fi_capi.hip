@@ -105,6 +105,7 @@ fi_ctx* create_ctx(int ndim, const int* sizes, int dtype, int rank, int nranks)
 		FI_HIP_TRY(hipGetDevice(&c->device));
 		c->stream = stream_take();
 		c->halo = 1;
+		c->stats.field_estimate = -1.0;  // (fi_stats: no solve yet, and none by the field)
 		compute_geom(c, ndim, sizes);
 		c->scal.alloc(3 * sizeof(CgScalars));  // [0]: the state every kernel and the host look at, [1]: mid-iteration copy,
 		                                       // [2]: landing place of the dot products summed over slabs (rank sets)

@@ -851,6 +851,7 @@ void cg_run(RankSet& R, int max_iterations, float tol)
 		c->stats.rel_residual = h.bb > 0 ? std::sqrt(h.rr / h.bb) : 0.0;
 		c->stats.restarts     = h.restarts;
 		c->stats.verified_residual = (h.restarts > 0 && h.bb > 0) ? std::sqrt(h.true_rr / h.bb) : -1.0;
+		residual_rule_stats(c->stats);
 		if (h.done == 4) {  // rhs == 0  ->  x = 0 (Eigen's early return)
 			FI_HIP_TRY(hipMemsetAsync(c->x.p, 0, sizeof(T) * c->g.nloc, c->stream));
 		}

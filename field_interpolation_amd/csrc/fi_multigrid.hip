@@ -1966,7 +1966,7 @@ void cg_run_mg(RankSet& R, int max_iterations, float tol)
 		c->stats.field_estimate     = by_field ? h.field_est : -1.0;
 		c->stats.field_per_residual = by_field ? h.field_kappa : 0.0;
 		c->stats.stop_residual      = c->stats.rel_residual;
-		c->stats.field_rounds       = by_field ? 1 : 0;
+		c->stats.field_rounds       = (by_field && !timed_out && h.done == 1 && h.field_stopped) ? 1 : 0;  // (not the floor, not max_iter)
 		if (h.done == 4) { FI_HIP_TRY(hipMemsetAsync(c->x.p, 0, sizeof(T) * c->g.nloc, c->stream)); }
 	}
 	FI_REQUIRE(h.done != 2, FI_ERR_BREAKDOWN, "CG breakdown: non-finite or non-positive curvature (p.AtA p = %g)", h.pq);

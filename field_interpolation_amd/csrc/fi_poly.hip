@@ -729,6 +729,7 @@ void cg_run_poly(RankSet& R, int max_iterations, float tol)
 		c->stats.rel_residual = h.bb > 0 ? std::sqrt(h.rr / h.bb) : 0.0;
 		c->stats.restarts     = h.restarts;
 		c->stats.verified_residual = (h.restarts > 0 && h.bb > 0) ? std::sqrt(h.true_rr / h.bb) : -1.0;
+		residual_rule_stats(c->stats);
 		if (h.done == 4) { FI_HIP_TRY(hipMemsetAsync(c->x.p, 0, sizeof(T) * c->g.nloc, c->stream)); }
 	}
 	FI_REQUIRE(h.done != 2, FI_ERR_BREAKDOWN, "CG breakdown: non-finite or non-positive curvature (p.AtA p = %g)", h.pq);
@@ -1057,6 +1058,7 @@ void cg_run_poly_sr(RankSet& R, int max_iterations, float tol)
 		c->stats.rel_residual = h.bb > 0 ? std::sqrt(h.rr / h.bb) : 0.0;
 		c->stats.restarts     = h.restarts;
 		c->stats.verified_residual = (h.restarts > 0 && h.bb > 0) ? std::sqrt(h.true_rr / h.bb) : -1.0;
+		residual_rule_stats(c->stats);
 		if (h.done == 4) { FI_HIP_TRY(hipMemsetAsync(c->x.p, 0, sizeof(T) * c->g.nloc, c->stream)); }
 	}
 	FI_REQUIRE(h.done != 2, FI_ERR_BREAKDOWN, "CG breakdown in the single-reduction recurrence (r.M r or p.A p not positive)");

@@ -512,6 +512,7 @@ __global__ __launch_bounds__(kThreads) void k_mg_logic(CgScalars* sc, const doub
 			sc->done = 2;
 		} else if (field_met || !(s > sc->tol2)) {
 			sc->done = 1;
+			sc->field_stopped = field_met ? 1 : 0;
 		} else if (sc->iter >= sc->max_iter) {
 			sc->done = 3;
 		}
@@ -566,6 +567,16 @@ inline int64_t global_first(const fi_ctx* c)
 	int64_t plane = 1;
 	for (int d = 0; d < a; ++d) { plane *= g.gn[d]; }
 	return plane * (g.off[a] + g.own_lo[a]);
+}
+
+// fi_stats of a solve the residual rule ended -- every path but V-cycle PCG under FI_OPT_FIELD_TOLERANCE, which falls back
+// here where it cannot run (include/fi_hip.h): no field estimate, the stop residual is the recurrence's
+inline void residual_rule_stats(fi_stats& s)
+{
+	s.field_estimate     = -1.0;
+	s.field_per_residual = 0.0;
+	s.field_rounds       = 0;
+	s.stop_residual      = s.rel_residual;
 }
 
 }  // namespace

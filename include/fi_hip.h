@@ -111,12 +111,15 @@ typedef struct fi_stats {
 	int    coarse_unconverged; /* levels of the coarse-to-fine start that had NOT met their tolerance after the iterations their
 	                              previous solve had needed (no look at the flag in between): the finest level then started from a
 	                              poorer guess and still converged to ITS tolerance; those levels watch their flag again next time */
-	double field_estimate;     /* FI_OPT_FIELD_TOLERANCE: bound on ||x - x*||_inf / ||x||_inf of the returned field (-1: the
-	                              residual rule ran) */
+	double field_estimate;     /* FI_OPT_FIELD_TOLERANCE: estimate of ||x - x*||_inf / ||x||_inf of the returned field at the last
+	                              iteration of a solve the rule ran (it may have ended at the floor or max_iterations: see
+	                              field_rounds); -1: the residual rule ran -- the option unset, a path without the rule (see
+	                              FI_OPT_FIELD_TOLERANCE), or no solve yet */
 	double field_per_residual; /* ... change of the field (relative, maximum norm) per unit of relative residual dropped over the
-	                              last iteration */
-	double stop_residual;      /* the relative residual the last solve ended at */
-	int    field_rounds;       /* 1: the last solve stopped by the field; 0: by the residual */
+	                              last iteration; 0 when the residual rule ran */
+	double stop_residual;      /* the relative residual the last solve ended at (= rel_residual) */
+	int    field_rounds;       /* 1: the field test ended the last solve; 0: anything else -- the residual rule, the precision's
+	                              floor or max_iterations under FI_OPT_FIELD_TOLERANCE, a path without the rule */
 } fi_stats;
 
 const char* fi_last_error(void);
@@ -289,7 +292,11 @@ int fi_solve_cg(fi_ctx* ctx, const float* guess, int max_iterations, float tol, 
  * problems (tests/stress_field_rule.py: value data and oriented points, 1 to 5 levels, 6 to 650 iterations) the true error
  * exceeded the tolerance in 3, 7 and 0 cases (warm starts included; 3 and 9 of 150 + 150 with FI_OPT_MG_KCYCLE), by at most 1.5 x and 2.4 x --
  * but for warm starts on hierarchies whose cold solves take a thousand iterations (2 cases, 15 x); the goldens of configs 2 to 5 end 8 to 100 x
- * below it.  fi_stats: field_estimate, field_per_residual. */
+ * below it.  fi_stats: field_estimate, field_per_residual, field_rounds.
+ * Paths without the rule stop by the residual at the `tol` of fi_solve_cg, as with the option unset, and report
+ * field_estimate = -1, field_per_residual = 0, field_rounds = 0: FI_OPT_MULTIGRID off (Jacobi or polynomial PCG), no coarser
+ * level built (a lattice too small to halve, rows from fi_add_rows_coo), more than 16 slabs, and a finest level held as
+ * replicated copies. */
 #define FI_OPT_FIELD_TOLERANCE 12
 /* FI_OPT_MG_KCYCLE (default 0 = off; V-cycle PCG, fp32 levels): a K-cycle -- the correction of the
  * first `value` coarse levels is not one application of the coarser level's cycle but TWO steps of flexible CG on that
