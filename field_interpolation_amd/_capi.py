@@ -22,6 +22,7 @@ SYMBOLS = [
     "fi_group_create", "fi_group_destroy", "fi_group_size", "fi_group_rank", "fi_group_assemble",
     "fi_group_solve_cg", "fi_group_apply_AtA_f64", "fi_group_true_residual", "fi_group_get_solution_f64", "fi_group_tile_pass", "fi_group_error_map",
     "fi_group_iso_extract", "fi_iso_extract", "fi_iso_extract_field", "fi_mesh_info", "fi_mesh_copy", "fi_mesh_destroy",
+    "fi_dual_contour", "fi_dual_contour_field",
     "fi_group_sample", "fi_sample", "fi_sample_field",
     "fi_nearest", "fi_distance_field", "fi_points_create", "fi_points_nearest", "fi_points_distance_field", "fi_points_destroy",
 ]
@@ -123,6 +124,8 @@ def lib():
     L.fi_group_iso_extract.argtypes = [vp, fp, C.c_float, C.POINTER(vp)]
     L.fi_iso_extract.argtypes = [vp, fp, C.c_float, C.c_int, C.POINTER(vp)]
     L.fi_iso_extract_field.argtypes = [fp, C.c_int, ip, C.c_float, C.c_int, C.POINTER(vp)]
+    L.fi_dual_contour.argtypes = [vp, fp, fp, C.c_float, C.c_int, C.POINTER(vp)]
+    L.fi_dual_contour_field.argtypes = [fp, fp, C.c_int, ip, C.c_float, C.c_int, C.POINTER(vp)]
     L.fi_mesh_info.argtypes = [vp, C.POINTER(C.c_long), C.POINTER(C.c_long), ip]
     L.fi_mesh_copy.argtypes = [vp, fp, fp, vp, vp, C.c_int]
     L.fi_mesh_destroy.argtypes = [vp]

@@ -429,6 +429,19 @@ class LatticeField:
             check(_capi.lib().fi_iso_extract(self._h, s, float(iso), mem, C.byref(h)))
         return _take_mesh(h, len(self.sizes), normals)
 
+    def dual_contour(self, solution=None, iso=0.0, gradients=None, normals=True):
+        """The dual contour (2-D: segments, 3-D: triangles) of `solution` (this context's owned values, host or device) or,
+        with None, of the last solve's solution where it lives on the device: one vertex per crossed cell, fitted to the
+        corner gradients so that sharp corners survive (include/fi_hip.h fi_dual_contour).  gradients: (num_owned, ndim)
+        in the same memory as `solution`, or None for central differences of f - iso.  Undivided contexts only.  -> IsoMesh
+        (keys: the lattice index of each vertex's cell)"""
+        s, smem, _ks = _buf(solution)
+        g, gmem, _kg = _buf(gradients)
+        mem = _same_memory(smem, gmem)
+        h = C.c_void_p()
+        check(_capi.lib().fi_dual_contour(self._h, s, g, float(iso), mem, C.byref(h)))
+        return _take_mesh(h, len(self.sizes), normals)
+
     def sample(self, positions, solution=None, gradients=False, cubic=False, fill=float("nan")):
         """Values (n,) -- and with gradients=True also gradients (n, ndim) -- of `solution` (this context's owned values) or,
         with None, of the last solve's solution where it lives on the device, at `positions` (n x ndim, global lattice
@@ -830,6 +843,18 @@ def iso_surface(field, sizes, iso=0.0, normals=True):
     sz = (C.c_int * len(sizes))(*[int(s) for s in sizes])
     h = C.c_void_p()
     check(_capi.lib().fi_iso_extract_field(src, len(sizes), sz, float(iso), mem, C.byref(h)))
+    return _take_mesh(h, len(sizes), normals)
+
+
+def dual_contour(field, sizes, iso=0.0, gradients=None, normals=True):
+    """LatticeField.dual_contour of a whole lattice field (numpy array or torch CUDA tensor, x fastest); gradients:
+    (prod(sizes), ndim) in the same memory, or None.  -> IsoMesh"""
+    src, mem, _keep = _buf(field)
+    g, gmem, _kg = _buf(gradients)
+    mem = _same_memory(mem, gmem)
+    sz = (C.c_int * len(sizes))(*[int(s) for s in sizes])
+    h = C.c_void_p()
+    check(_capi.lib().fi_dual_contour_field(src, g, len(sizes), sz, float(iso), mem, C.byref(h)))
     return _take_mesh(h, len(sizes), normals)
 
 

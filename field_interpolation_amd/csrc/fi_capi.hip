@@ -3,6 +3,7 @@
 #include "fi_solver_internal.h"
 #include "fi_workers.h"
 #include "fi_iso.h"
+#include "fi_dual.h"
 #include "fi_sample.h"
 #include "fi_nearest.h"
 
@@ -1057,6 +1058,49 @@ int fi_iso_extract_field(const float* field, int ndim, const int* sizes, float i
 		f = df.as<float>();
 	}
 	fi::iso_extract_whole(f, ndim, sizes, iso, 1, nullptr, nullptr, nullptr, out);
+	FI_API_END
+}
+
+// ---- dual contouring (fi_dual.hip) --------------------------------------------------------------
+int fi_dual_contour(fi_ctx* c, const float* field, const float* gradients, float iso, int memory, fi_mesh** out)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	FI_REQUIRE(out != nullptr, FI_ERR_INVALID, "out is null");
+	*out = nullptr;
+	fi::bind_device(c);
+	fi::dual_contour_ctx(c, field, gradients, iso, memory, out);
+	FI_API_END
+}
+
+int fi_dual_contour_field(const float* field, const float* gradients, int ndim, const int* sizes, float iso, int memory,
+                          fi_mesh** out)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(field && sizes && out, FI_ERR_INVALID, "null argument");
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	*out = nullptr;
+	FI_REQUIRE(ndim != 1, FI_ERR_UNSUPPORTED, "dual contouring of a 1-D lattice is not supported");
+	FI_REQUIRE(ndim == 2 || ndim == 3, FI_ERR_INVALID, "ndim must be 2 or 3 (got %d)", ndim);
+	int64_t n = 1;
+	for (int d = 0; d < ndim; ++d) {
+		FI_REQUIRE(sizes[d] >= 1, FI_ERR_INVALID, "sizes[%d] = %d", d, sizes[d]);
+		n *= sizes[d];
+	}
+	fi::DevBuf   df, dg;
+	const float* f = field;
+	const float* g = gradients;
+	if (memory == FI_HOST) {
+		df.alloc(sizeof(float) * n);
+		FI_HIP_TRY(hipMemcpy(df.p, field, sizeof(float) * n, hipMemcpyHostToDevice));
+		f = df.as<float>();
+		if (gradients) {
+			dg.alloc(sizeof(float) * ndim * n);
+			FI_HIP_TRY(hipMemcpy(dg.p, gradients, sizeof(float) * ndim * n, hipMemcpyHostToDevice));
+			g = dg.as<float>();
+		}
+	}
+	fi::dual_contour_whole(f, g, ndim, sizes, iso, nullptr, out);
 	FI_API_END
 }
 

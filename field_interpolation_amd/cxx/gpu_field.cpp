@@ -249,6 +249,35 @@ bool GpuLatticeField::iso_surface(float iso, std::vector<float>* vertices, std::
 	return ok;
 }
 
+bool GpuLatticeField::dual_contour(float iso, std::vector<float>* vertices, std::vector<int>* indices, std::vector<float>* normals,
+                                   const std::vector<float>* gradients) const
+{
+	const size_t D = sizes_.size();
+	if (gradients && gradients->size() != D * num_unknowns()) {
+		std::fprintf(stderr, "field_interpolation: dual_contour: %zu gradient values for %zu points\n", gradients->size(),
+		             num_unknowns());
+		return false;
+	}
+	fi_mesh* m = nullptr;
+	if (fi_dual_contour(ctx_, nullptr, gradients ? gradients->data() : nullptr, iso, FI_HOST, &m) != FI_OK) {
+		warn("dual_contour");
+		return false;
+	}
+	long nv = 0, np = 0;
+	int  vpp = 0;
+	bool ok = fi_mesh_info(m, &nv, &np, &vpp) == FI_OK;
+	if (ok) {
+		if (vertices) { vertices->resize(D * static_cast<size_t>(nv)); }
+		if (normals) { normals->resize(D * static_cast<size_t>(nv)); }
+		if (indices) { indices->resize(static_cast<size_t>(vpp) * static_cast<size_t>(np)); }
+		ok = fi_mesh_copy(m, vertices ? vertices->data() : nullptr, normals ? normals->data() : nullptr,
+		                  indices ? indices->data() : nullptr, nullptr, FI_HOST) == FI_OK;
+	}
+	if (!ok) { warn("dual_contour"); }
+	fi_mesh_destroy(m);
+	return ok;
+}
+
 bool GpuLatticeField::sample(const std::vector<float>& positions, std::vector<float>* values, std::vector<float>* gradients,
                              bool cubic) const
 {

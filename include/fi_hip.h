@@ -418,6 +418,48 @@ int fi_upscale_field(const float* small_field, int ndim, const int* small_sizes,
 int fi_iso_extract(fi_ctx* ctx, const float* field, float iso, int memory, fi_mesh** out);
 /* the same without a context: any whole field (e.g. the output of fi_upscale_field) */
 int fi_iso_extract_field(const float* field, int ndim, const int* sizes, float iso, int memory, fi_mesh** out);
+
+/* ---- dual contouring ------------------------------------------------------------------------
+ * The same kind of mesh, but with one vertex per crossed cell, placed by the least-squares fit of the reference's
+ * src/dual_contouring_2d.cpp (which its app never calls), so that sharp corners and edges survive.  The contract (DESIGN.md
+ * 4.8, "Dual contouring") -- everything is computed from d = f - iso in fp32, one rounding per operation:
+ *   - inside is d <= 0 (the reference's rule; fi_iso_extract's is f < iso).  A non-finite d: FI_ERR_INVALID; a 1-D lattice:
+ *     FI_ERR_UNSUPPORTED; an extent < 2: an empty mesh and FI_OK;
+ *   - gradients: ndim floats per lattice point, interleaved, x fastest (the reference's Vec2*), used as given; NULL: the
+ *     reference's calculate_gradients per axis, (d[+1] - d[-1]) / 2, one-sided at that axis's own border (the reference tests
+ *     y == width - 1 for the y border and so reads out of bounds on non-square lattices; parity with it is claimed on square
+ *     lattices, or with gradients passed in);
+ *   - cells (all corners in the lattice) in ascending linear index, x fastest; corner i steps +1 along axis k where bit k of i
+ *     is set.  A cell has a vertex unless its corners are all inside or all outside; crossing[i]: some cell edge at corner i
+ *     joins corners of different inside-ness;
+ *   - the fit: 2^D + D rows.  Corner rows first, in corner order: A_i = g(corner_i), b_i = ((bit_0 g_0 + bit_1 g_1)
+ *     [+ bit_2 g_2]) - d_i, a zero row where crossing[i] is not set; then D rows r e_k with right-hand side 0.5f r.  A^T A and
+ *     A^T b accumulate over the rows in order.  2-D: solve_lin_eq_2d, det = M0 M3 - M1 M2, x = (b0 M3 - M1 b1) / det,
+ *     y = (b1 M0 - M2 b0) / det.  3-D: Cramer's rule, x_k = det3(M with column k replaced by A^T b) / det3(M), with
+ *     det3(a) = (a0 c0 - a1 c1) + a2 c2, c0 = a4 a8 - a5 a7, c1 = a3 a8 - a5 a6, c2 = a3 a7 - a4 a6 (row-major).  r starts at
+ *     0.001f and doubles while any coordinate is < 0 or > 1 (a NaN ends the loop, as the reference's do ... while), for at most
+ *     32 solves; a vertex that is then non-finite or outside [0, 1]^D is the cell centre.  Position (float)cell_k + v_k, key
+ *     the lattice index of the cell's lowest corner (ascending);
+ *   - normal: the corner gradients weighted as fi_sample's FI_SAMPLE_LINEAR weighs corner values at the offset v, summed in
+ *     ascending corner order, then normalised (a zero gradient stays zero); it points towards increasing f;
+ *   - primitives: the lattice edge (p, p + e_a) gives one when its ends differ in inside-ness and every cell around it exists
+ *     (2 in 2-D, 4 in 3-D).  Its lowest cell p - sum_(k != a) e_k emits it; cells emit in ascending index, within a cell by
+ *     axis a from D - 1 down to 0.  2-D: the reference's order and orientation (the inside on the left): a = 1, the +x
+ *     neighbour, (this, it) when p + e_a is inside, else (it, this); a = 0, the +y neighbour, (it, this) when p + e_a is inside,
+ *     else (this, it).  3-D: the cells q0 .. q3 at offsets (0,0), (1,0), (1,1), (0,1) along b = (a+1)%3, c = (a+2)%3 from the
+ *     lowest form a quad with normal +a, reversed to (q0, q3, q2, q1) when p is outside; triangles (q0, q1, q2), (q0, q2, q3)
+ *     of the quad so ordered, so that (b - a) x (c - a) points from inside to outside;
+ *   - int32 indices (>= 2^31 vertices: FI_ERR_UNSUPPORTED); no atomics in the outputs: the bytes do not depend on the run or
+ *     the launch shape.
+ * field NULL: the context's last solution where it lives (an FI_F64 solution is rounded to fp32 once, as fi_iso_extract
+ * does); `memory` applies to field and gradients.  Slab contexts (nranks > 1): FI_ERR_UNSUPPORTED -- the vertices of a slab's
+ * first cell plane above it need field planes hi .. hi + 2 (the last for the central differences), one more than the two
+ * ghost planes of the iso path, so slabs need a vertex exchange; there is no group entry either. */
+int fi_dual_contour(fi_ctx* ctx, const float* field, const float* gradients, float iso, int memory, fi_mesh** out);
+/* the same without a context: any whole field, fp32, x fastest */
+int fi_dual_contour_field(const float* field, const float* gradients, int ndim, const int* sizes, float iso, int memory,
+                          fi_mesh** out);
+
 int fi_mesh_info(const fi_mesh* m, long* num_vertices, long* num_primitives, int* vertices_per_primitive);
 /* any output may be NULL; vertices / normals are ndim floats per vertex, indices vertices_per_primitive int32 per primitive */
 int fi_mesh_copy(const fi_mesh* m, float* vertices, float* normals, int* indices, long long* keys, int memory);

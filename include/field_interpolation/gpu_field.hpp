@@ -64,6 +64,13 @@ public:
 	bool iso_surface(float iso, std::vector<float>* vertices, std::vector<int>* indices,
 	                 std::vector<float>* normals = nullptr) const;
 
+	// The dual contour f = iso of the last solution, on the device (include/fi_hip.h fi_dual_contour): one vertex per crossed
+	// cell, fitted to the planes of the corner gradients so that sharp corners and edges survive; 2-D segments or 3-D
+	// triangles, vertices and normals as iso_surface.  gradients (optional): ndim floats per lattice point, interleaved, x
+	// fastest; without them, central differences of f - iso.  false: no solution yet, or the library refused the call.
+	bool dual_contour(float iso, std::vector<float>* vertices, std::vector<int>* indices, std::vector<float>* normals = nullptr,
+	                  const std::vector<float>* gradients = nullptr) const;
+
 	// Values (and, if asked, gradients: ndim floats per point) of the last solution at `positions` (ndim floats per point,
 	// global lattice coordinates, x fastest), sampled where the solution lives on the device: multilinear, or Catmull-Rom
 	// with cubic = true; points outside the lattice get NaN.  The contract is include/fi_hip.h fi_sample.  false: no
