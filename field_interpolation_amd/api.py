@@ -66,7 +66,7 @@ def _buf(a, dtype=np.float32):
         return None, None, None
     if hasattr(a, "data_ptr"):           # torch tensor
         import torch
-        want = {np.float32: torch.float32, np.float64: torch.float64}[dtype]
+        want = {np.float32: torch.float32, np.float64: torch.float64, np.int32: torch.int32}[dtype]
         t = a.contiguous()
         if t.dtype != want:
             t = t.to(want)
@@ -222,6 +222,99 @@ class PointIndex:
         def call(d, i, mem):
             return _capi.lib().fi_points_distance_field(self._h, sz, float(max_distance), d, i, mem)
         return _distance_field(call, int(np.prod(sizes)), indices, device)
+
+
+_SURFACE_METHODS = {"iso": 0, "dual": 1}     # FI_SURFACE_ISO, FI_SURFACE_DUAL
+
+
+def _surface_method(method):
+    if method not in _SURFACE_METHODS:
+        raise ValueError("method must be 'iso' (fi_iso_extract's mesh) or 'dual' (fi_dual_contour's), not %r" % (method,))
+    return _SURFACE_METHODS[method]
+
+
+def _redistance(call, total, primitives, device, ndim):
+    """Shared body of the redistancing calls: call(out, primitives, mesh handle pointer, memory).  -> distances, or with
+    primitives=True (distances, primitive indices, the IsoMesh they index)"""
+    if not primitives:
+        return _distance_field(lambda d, i, mem: call(d, None, None, mem), total, False, device)
+    h = C.c_void_p()
+    try:
+        d, i = _distance_field(lambda d, i, mem: call(d, i, C.byref(h), mem), total, True, device)
+    except BaseException:
+        if h:
+            _capi.lib().fi_mesh_destroy(h)
+        raise
+    return d, i, _take_mesh(h, ndim)
+
+
+class SurfaceIndex:
+    """Exact distances to a mesh of its own, searched on the device (include/fi_hip.h fi_surface_create): 2-D segments or 3-D
+    triangles.  vertices: (V, ndim) float32 in lattice units, indices: (P, ndim) int32 -- numpy arrays or torch tensors in
+    the same memory; a primitive's index is its row."""
+
+    def __init__(self, vertices, indices):
+        v, vmem, vkeep = _buf(vertices)
+        i, imem, ikeep = _buf(indices, np.int32)
+        mem = _same_memory(vmem, imem)
+        vshape, ishape = tuple(vkeep.shape), tuple(ikeep.shape)
+        self.ndim = int(ishape[-1]) if len(ishape) == 2 else int(vshape[-1])
+        vcount = vkeep.numel() if hasattr(vkeep, "numel") else vkeep.size
+        icount = ikeep.numel() if hasattr(ikeep, "numel") else ikeep.size
+        if vcount % self.ndim or icount % self.ndim:
+            raise ValueError("vertices / indices: %d / %d values, not multiples of ndim = %d" % (vcount, icount, self.ndim))
+        self.num_vertices, self.num_primitives = vcount // self.ndim, icount // self.ndim
+        self._h = C.c_void_p()
+        check(_capi.lib().fi_surface_create(C.byref(self._h), self.ndim, self.num_vertices, v if vcount else None,
+                                            self.num_primitives, i if icount else None, mem))
+
+    @classmethod
+    def from_mesh(cls, mesh):
+        """The surface of an IsoMesh (LatticeField.iso_surface / dual_contour, iso_surface, dual_contour)"""
+        return cls(mesh.vertices, mesh.indices)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _capi._LIB is not None:
+            _capi._LIB.fi_surface_destroy(h)
+        self._h = None
+
+    def distance(self, queries, max_distance=math.inf, primitives=False, closest=False):
+        """Distances (n,) float32 from each of `queries` (n x ndim) to the surface; with primitives=True also the nearest
+        primitive (n,) int64, with closest=True also the closest point (n, ndim) float32 -- a tuple in that order.  Beyond
+        max_distance or with no usable primitive: +inf, -1, NaN; a non-finite query: NaN, -1, NaN.  Outputs live where
+        `queries` lives (include/fi_hip.h fi_surface_distance)."""
+        q, qmem, qkeep = _buf(queries)
+        count = qkeep.numel() if hasattr(qkeep, "numel") else qkeep.size
+        if count % self.ndim:
+            raise ValueError("queries: %d values, not a multiple of ndim = %d (x fastest)" % (count, self.ndim))
+        n = count // self.ndim
+        if hasattr(qkeep, "data_ptr"):
+            import torch
+            dist = torch.empty(n, dtype=torch.float32, device=qkeep.device)
+            idx = torch.empty(n, dtype=torch.int64, device=qkeep.device) if primitives else None
+            cl = torch.empty((n, self.ndim), dtype=torch.float32, device=qkeep.device) if closest else None
+            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        else:
+            dist = np.empty(n, np.float32)
+            idx = np.empty(n, np.int64) if primitives else None
+            cl = np.empty((n, self.ndim), np.float32) if closest else None
+            ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+        if n:   # (an empty tensor has no storage to point at)
+            check(_capi.lib().fi_surface_distance(self._h, n, q, float(max_distance), ptr(dist), ptr(idx), ptr(cl), qmem))
+        out = tuple(a for a in (dist, idx, cl) if a is not None)
+        return out if len(out) > 1 else dist
+
+    def distance_field(self, sizes, max_distance=math.inf, primitives=False, device=False):
+        """SurfaceIndex.distance of every point of a lattice of `sizes` (x fastest), flat, unsigned: numpy arrays, or torch
+        tensors with device=True."""
+        if len(sizes) != self.ndim:
+            raise ValueError("sizes: %d extents for a %d-D surface" % (len(sizes), self.ndim))
+        sz = (C.c_int * len(sizes))(*[int(s) for s in sizes])
+
+        def call(d, i, mem):
+            return _capi.lib().fi_surface_distance_field(self._h, sz, float(max_distance), d, i, mem)
+        return _distance_field(call, int(np.prod(sizes)), primitives, device)
 
 
 class LatticeField:
@@ -466,6 +559,20 @@ class LatticeField:
         def call(d, i, mem):
             return _capi.lib().fi_distance_field(self._h, float(max_distance), d, i, mem)
         return _distance_field(call, self.num_unknowns, indices, device)
+
+    def redistance(self, solution=None, iso=0.0, method="iso", max_distance=math.inf, primitives=False, device=False):
+        """The signed distance of every lattice point (x fastest) to the iso-surface f = iso of `solution` (this context's
+        owned values, host or device) or, with None, of the last solve's solution where it lives: negative inside (method
+        "iso": fi_iso_extract's mesh, inside is f < iso; "dual": fi_dual_contour's, inside is f - iso <= 0), +-inf beyond
+        max_distance (include/fi_hip.h fi_redistance).  Undivided contexts only.  -> distances (numpy, or torch tensors with
+        device=True), or with primitives=True (distances, primitive indices, the IsoMesh they index)"""
+        s, smem, _keep = _buf(solution)
+        _same_memory(smem, FI_DEVICE if device else FI_HOST)
+        m = _surface_method(method)
+
+        def call(d, i, h, mem):
+            return _capi.lib().fi_redistance(self._h, s, float(iso), m, float(max_distance), d, i, h, mem)
+        return _redistance(call, self.num_unknowns, primitives, device, len(self.sizes))
 
     def set_verify_residual(self, on):
         """FI_OPT_VERIFY_RESIDUAL: True (default) checks b - A x at convergence and restarts CG if fp32 drift
@@ -856,6 +963,18 @@ def dual_contour(field, sizes, iso=0.0, gradients=None, normals=True):
     h = C.c_void_p()
     check(_capi.lib().fi_dual_contour_field(src, g, len(sizes), sz, float(iso), mem, C.byref(h)))
     return _take_mesh(h, len(sizes), normals)
+
+
+def redistance(field, sizes, iso=0.0, method="iso", max_distance=math.inf):
+    """LatticeField.redistance of a whole lattice field (numpy array or torch CUDA tensor, x fastest): the signed distances,
+    flat, where the field lives"""
+    src, mem, _keep = _buf(field)
+    sz = (C.c_int * len(sizes))(*[int(s) for s in sizes])
+    m = _surface_method(method)
+
+    def call(d, i, h, mm):
+        return _capi.lib().fi_redistance_field(src, len(sizes), sz, float(iso), m, float(max_distance), d, i, h, mm)
+    return _redistance(call, int(np.prod(sizes)), False, mem == FI_DEVICE, len(sizes))
 
 
 def sample_field(field, sizes, positions, gradients=False, cubic=False, fill=float("nan")):

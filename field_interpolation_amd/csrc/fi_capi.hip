@@ -6,6 +6,7 @@
 #include "fi_dual.h"
 #include "fi_sample.h"
 #include "fi_nearest.h"
+#include "fi_surface.h"
 
 #include <memory>
 
@@ -1270,6 +1271,137 @@ int fi_points_destroy(fi_points* h)
 	delete h;
 	if (switched) { (void)hipSetDevice(dev); }
 	return FI_OK;
+}
+
+
+// ---- distances to a surface; redistancing (fi_surface.hip) -------------------------------------
+namespace {
+void check_surface(const fi_surface* h)
+{
+	FI_REQUIRE(h != nullptr, FI_ERR_INVALID, "surface is null");
+	FI_HIP_TRY(hipSetDevice(h->device));
+}
+
+void check_redistance(int method, float max_distance, const float* out, int memory)
+{
+	FI_REQUIRE(method == FI_SURFACE_ISO || method == FI_SURFACE_DUAL, FI_ERR_INVALID, "unknown surface method %d", method);
+	check_field_out(max_distance, out, memory);
+}
+}  // namespace
+
+int fi_surface_create(fi_surface** out, int ndim, long num_vertices, const float* vertices, long num_primitives, const int* indices,
+                      int memory)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(out != nullptr, FI_ERR_INVALID, "out is null");
+	*out = nullptr;
+	FI_REQUIRE(ndim == 2 || ndim == 3, FI_ERR_UNSUPPORTED, "surfaces in %d-D are not supported (2-D segments, 3-D triangles)", ndim);
+	FI_REQUIRE(num_vertices >= 0 && num_primitives >= 0, FI_ERR_INVALID, "%ld vertices, %ld primitives", num_vertices, num_primitives);
+	FI_REQUIRE(num_vertices == 0 || vertices != nullptr, FI_ERR_INVALID, "vertices is null");
+	FI_REQUIRE(num_primitives == 0 || indices != nullptr, FI_ERR_INVALID, "indices is null");
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	FI_REQUIRE(num_primitives < (1L << 31), FI_ERR_UNSUPPORTED, "%ld primitives: primitive indices are 32-bit", num_primitives);
+	std::unique_ptr<fi_surface> h(new fi_surface());
+	FI_HIP_TRY(hipGetDevice(&h->device));
+	fi::DevBuf   bv, bi;
+	const float* v = vertices;
+	const int*   i = indices;
+	if (memory == FI_HOST) {
+		if (num_vertices > 0) {
+			bv.alloc(sizeof(float) * ndim * num_vertices);
+			FI_HIP_TRY(hipMemcpy(bv.p, vertices, sizeof(float) * ndim * num_vertices, hipMemcpyHostToDevice));
+			v = bv.as<float>();
+		}
+		if (num_primitives > 0) {
+			bi.alloc(sizeof(int) * ndim * num_primitives);
+			FI_HIP_TRY(hipMemcpy(bi.p, indices, sizeof(int) * ndim * num_primitives, hipMemcpyHostToDevice));
+			i = bi.as<int>();
+		}
+	}
+	fi::surface_build(h->t, ndim, num_vertices, v, num_primitives, i, nullptr);
+	*out = h.release();
+	FI_API_END
+}
+
+int fi_surface_from_mesh(fi_surface** out, const fi_mesh* mesh)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(out != nullptr && mesh != nullptr, FI_ERR_INVALID, "null argument");
+	*out = nullptr;
+	FI_HIP_TRY(hipSetDevice(mesh->device));
+	std::unique_ptr<fi_surface> h(new fi_surface());
+	h->device = mesh->device;
+	fi::surface_build(h->t, mesh->ndim, mesh->nv, mesh->pos.as<float>(), mesh->np, mesh->idx.as<int>(), nullptr);
+	*out = h.release();
+	FI_API_END
+}
+
+int fi_surface_distance(fi_surface* h, long n, const float* queries, float max_distance, float* distances, long long* primitives,
+                        float* closest, int memory)
+{
+	FI_API_BEGIN
+	check_surface(h);
+	check_nearest(n, queries, max_distance, distances, memory);
+	fi::surface_query(h->t, n, queries, max_distance, distances, primitives, closest, memory, nullptr);
+	FI_API_END
+}
+
+int fi_surface_distance_field(fi_surface* h, const int* sizes, float max_distance, float* out, long long* primitives, int memory)
+{
+	FI_API_BEGIN
+	check_surface(h);
+	FI_REQUIRE(sizes != nullptr, FI_ERR_INVALID, "sizes is null");
+	for (int d = 0; d < h->t.D; ++d) { FI_REQUIRE(sizes[d] >= 1, FI_ERR_INVALID, "sizes[%d] = %d", d, sizes[d]); }
+	check_field_out(max_distance, out, memory);
+	fi::surface_lattice(h->t, sizes, max_distance, out, primitives, memory, nullptr);
+	FI_API_END
+}
+
+int fi_surface_destroy(fi_surface* h)
+{
+	if (!h) { return FI_OK; }
+	int dev = 0;
+	const bool switched = hipGetDevice(&dev) == hipSuccess && dev != h->device && hipSetDevice(h->device) == hipSuccess;
+	delete h;
+	if (switched) { (void)hipSetDevice(dev); }
+	return FI_OK;
+}
+
+int fi_redistance(fi_ctx* c, const float* field, float iso, int method, float max_distance, float* out, long long* primitives,
+                  fi_mesh** mesh, int memory)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	if (mesh) { *mesh = nullptr; }
+	fi::bind_device(c);
+	check_redistance(method, max_distance, out, memory);
+	fi::redistance_ctx(c, field, iso, method, max_distance, out, primitives, mesh, memory);
+	FI_API_END
+}
+
+int fi_redistance_field(const float* field, int ndim, const int* sizes, float iso, int method, float max_distance, float* out,
+                        long long* primitives, fi_mesh** mesh, int memory)
+{
+	FI_API_BEGIN
+	if (mesh) { *mesh = nullptr; }
+	FI_REQUIRE(field && sizes, FI_ERR_INVALID, "null argument");
+	check_redistance(method, max_distance, out, memory);
+	FI_REQUIRE(ndim == 2 || ndim == 3, FI_ERR_UNSUPPORTED, "redistancing a %d-D lattice is not supported", ndim);
+	int64_t n = 1;
+	for (int d = 0; d < ndim; ++d) {
+		FI_REQUIRE(sizes[d] >= 1, FI_ERR_INVALID, "sizes[%d] = %d", d, sizes[d]);
+		n *= sizes[d];
+	}
+	FI_REQUIRE(n < (int64_t(1) << 31), FI_ERR_UNSUPPORTED, "a lattice of %lld points", static_cast<long long>(n));
+	fi::DevBuf   df;
+	const float* f = field;
+	if (memory == FI_HOST) {
+		df.alloc(sizeof(float) * n);
+		FI_HIP_TRY(hipMemcpy(df.p, field, sizeof(float) * n, hipMemcpyHostToDevice));
+		f = df.as<float>();
+	}
+	fi::redistance_whole(f, ndim, sizes, iso, method, max_distance, out, primitives, mesh, memory, nullptr);
+	FI_API_END
 }
 
 

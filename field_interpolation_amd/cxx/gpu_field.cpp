@@ -335,6 +335,23 @@ bool GpuLatticeField::distance_field(std::vector<float>* distances, std::vector<
 	return true;
 }
 
+bool GpuLatticeField::redistance(std::vector<float>* out, float iso, bool dual, float max_distance,
+                                 std::vector<long long>* primitives) const
+{
+	if (!out) {
+		warn("redistance");
+		return false;
+	}
+	out->resize(num_unknowns());
+	if (primitives) { primitives->resize(num_unknowns()); }
+	if (fi_redistance(ctx_, nullptr, iso, dual ? FI_SURFACE_DUAL : FI_SURFACE_ISO, max_distance, out->data(),
+	                  primitives ? primitives->data() : nullptr, nullptr, FI_HOST) != FI_OK) {
+		warn("redistance");
+		return false;
+	}
+	return true;
+}
+
 std::unique_ptr<GpuLatticeField> gpu_sdf_from_points(const std::vector<int>& sizes, const Weights& weights,
                                                      int num_points, const float positions[], const float* normals,
                                                      const float* point_weights)

@@ -527,6 +527,62 @@ int fi_points_nearest(fi_points* points, long n, const float* queries, float max
 int fi_points_distance_field(fi_points* points, const int* sizes, float max_distance, float* out, long long* indices, int memory);
 int fi_points_destroy(fi_points* points);
 
+/* ---- exact distances to a surface; redistancing ------------------------------------------------
+ * The contract ("Distances to a surface") is this project's own.  All arithmetic is fp32, one rounding per
+ * operation (no FMA contraction):
+ *   - primitives: 2-D segments (a, b), 3-D triangles (a, b, c); vertices ndim floats each, in lattice units, interleaved;
+ *     indices ndim int32 per primitive, as in fi_mesh.  A primitive with a non-finite vertex coordinate is never nearest; an
+ *     index outside [0, num_vertices): FI_ERR_INVALID; ndim other than 2 or 3: FI_ERR_UNSUPPORTED (in 1-D the surface is
+ *     points: fi_points_*);
+ *   - dot products sum in ascending axis order from the first term;
+ *   - segment: ab = b - a; t = dot(q - a, ab) / dot(ab, ab) when dot(ab, ab) > 0, else 0; t clamped to [0, 1];
+ *     c = a + t ab per axis;
+ *   - triangle: Ericson's ClosestPtPointTriangle (Real-Time Collision Detection 5.1.5), its Voronoi-region tests in its
+ *     order, its own expressions (edge AB: a + (d1 / (d1 - d3)) ab; AC: a + (d2 / (d2 - d6)) ac; BC: b + (e / (e + f)) (c - b)
+ *     with e = d4 - d3, f = d5 - d6; the face: (a + ab v) + ac w, v = vb r, w = vc r, r = 1 / ((va + vb) + vc)).  A triangle is
+ *     degenerate when the branch taken divides by a denominator that is not > 0: the face's (va + vb) + vc, or an edge
+ *     region's (Ericson's own code divides 0 / 0 in region AB when a == b, which marching cubes emits at t = 0).  It gives the
+ *     nearest of its three edges' segment points (before any clamp), edges ab, bc, ca, the first on ties;
+ *   - then c is clamped per axis into the primitive's vertex bounding box (c < lo: lo; c > hi: hi);
+ *   - s = 0.0f + (q_0 - c_0)^2 + ... in ascending axes (fi_nearest's s).  A query q: best = min s over the primitives,
+ *     distance sqrtf(best), primitive = the smallest index with s == best, closest point = its clamped c.  No usable
+ *     primitive or sqrtf(best) > max_distance: +inf, -1, NaN point; a non-finite query: NaN, -1, NaN point;
+ *   - results in input order: distances float[n], primitives long long[n] or NULL, closest float[n][ndim] or NULL; they
+ *     depend neither on the launch shape nor on timing.
+ * n = 0 is fine.  n < 0, NULL required buffers, a NaN or negative max_distance, a bad memory kind: FI_ERR_INVALID; n or the
+ * number of primitives >= 2^31: FI_ERR_UNSUPPORTED.  `memory` applies to every buffer of a call; a surface is searched on
+ * the device it was created on. */
+#define FI_SURFACE_ISO 0  /* the mesh of fi_iso_extract: inside is f < iso */
+#define FI_SURFACE_DUAL 1 /* the mesh of fi_dual_contour with central differences: inside is f - iso <= 0 */
+typedef struct fi_surface fi_surface;
+int fi_surface_create(fi_surface** out, int ndim, long num_vertices, const float* vertices, long num_primitives,
+                      const int* indices, int memory);
+/* the same from a mesh of fi_iso_extract* / fi_dual_contour* on the device (no host round trip) */
+int fi_surface_from_mesh(fi_surface** out, const fi_mesh* mesh);
+int fi_surface_distance(fi_surface* surface, long n, const float* queries, float max_distance, float* distances,
+                        long long* primitives, float* closest, int memory);
+/* every lattice point of `sizes` (ndim extents >= 1, fewer than 2^31 points, x fastest) as a query: unsigned */
+int fi_surface_distance_field(fi_surface* surface, const int* sizes, float max_distance, float* out, long long* primitives,
+                              int memory);
+int fi_surface_destroy(fi_surface* surface);
+
+/* Redistancing: the signed distance of every lattice point (x fastest) to the field's own iso-surface f = iso -- the mesh of
+ * fi_iso_extract (method FI_SURFACE_ISO) or of fi_dual_contour with central differences (FI_SURFACE_DUAL) -- searched as
+ * fi_surface_distance_field does.  out = +distance where the point is outside by that producer's rule, -distance (a
+ * negation: -0.0f at distance 0) where it is inside; beyond max_distance, or with an empty mesh, +-inf with the sign kept.
+ * primitives (NULL or long long[total]) index the mesh returned through `mesh` (NULL, or receives a mesh the caller
+ * destroys with fi_mesh_destroy).  A non-finite field value: FI_ERR_INVALID (from the mesh producers); a method other
+ * than the two: FI_ERR_INVALID; ndim other than 2 or 3: FI_ERR_UNSUPPORTED.
+ * fi_redistance: field = the context's owned values in `memory`, or NULL for the last solution where it lives (an FI_F64
+ * solution is rounded to fp32 once, as fi_iso_extract does, and the sign comes from that fp32 field); NULL before the first
+ * solve: FI_ERR_STATE.  A slab context (nranks > 1) holds only part of the surface: FI_ERR_UNSUPPORTED; there is no group
+ * entry.  `memory` applies to field, out and primitives. */
+int fi_redistance(fi_ctx* ctx, const float* field, float iso, int method, float max_distance, float* out, long long* primitives,
+                  fi_mesh** mesh, int memory);
+/* the same without a context: any whole field, fp32, x fastest */
+int fi_redistance_field(const float* field, int ndim, const int* sizes, float iso, int method, float max_distance, float* out,
+                        long long* primitives, fi_mesh** mesh, int memory);
+
 #ifdef __cplusplus
 }
 #endif

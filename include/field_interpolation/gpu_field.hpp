@@ -87,6 +87,12 @@ public:
 	// nearest() of every lattice point (x fastest): num_unknowns() distances (and indices)
 	bool distance_field(std::vector<float>* distances, std::vector<long long>* indices = nullptr,
 	                    float max_distance = std::numeric_limits<float>::infinity()) const;
+	// The signed distance of every lattice point (x fastest) to the last solution's own iso-surface f = iso, searched on the
+	// device: fi_iso_extract's mesh (inside f < iso) or, with dual = true, fi_dual_contour's (inside f - iso <= 0); negative
+	// inside, +-inf beyond max_distance.  primitives (optional): the nearest primitive of that mesh per point, -1 beyond
+	// max_distance.  The contract is include/fi_hip.h fi_redistance.  false: no solution yet, or the library refused the call.
+	bool redistance(std::vector<float>* out, float iso = 0, bool dual = false,
+	                float max_distance = std::numeric_limits<float>::infinity(), std::vector<long long>* primitives = nullptr) const;
 
 	int    last_iterations() const { return iterations_; }
 	float  last_error() const { return error_; }
