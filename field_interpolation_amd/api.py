@@ -446,7 +446,21 @@ class LatticeField:
 
     def add_rows_coo(self, rows, cols, values, rhs):
         """Arbitrary rows of a `LinearEquation` (sparse_linear.hpp:18-22): triplets (row, col, value) with rows
-        numbered from 0 within this call, and one rhs per row.  Duplicate (row, col) entries are summed."""
+        numbered from 0 within this call, and one rhs per row.  Duplicate (row, col) entries are summed in input order in
+        the context's precision.  numpy arrays, or torch tensors that all live on the GPU (FI_DEVICE: no host copy)."""
+        if hasattr(values, "data_ptr") and values.is_cuda:
+            import torch
+            if not all(hasattr(t, "data_ptr") and t.is_cuda for t in (rows, cols, rhs)):
+                raise ValueError("all buffers of one call must live in the same memory (all host or all device)")
+            trip = torch.empty((values.numel(), 3), dtype=torch.int32, device=values.device)    # fi_triplet: 12 bytes
+            trip[:, 0], trip[:, 1] = rows, cols
+            trip[:, 2] = values.to(torch.float32).contiguous().view(torch.int32)
+            b = rhs.to(torch.float32).contiguous()
+            torch.cuda.synchronize(values.device)                # the library works on a stream of its own
+            check(_capi.lib().fi_add_rows_coo(self._h, b.numel(), trip.shape[0], C.c_void_p(trip.data_ptr()),
+                                              C.c_void_p(b.data_ptr()), FI_DEVICE))
+            self._dirty = True
+            return
         trip = np.empty(len(values), dtype=[("row", np.int32), ("col", np.int32), ("value", np.float32)])
         trip["row"], trip["col"], trip["value"] = rows, cols, values
         b = np.ascontiguousarray(rhs, np.float32)

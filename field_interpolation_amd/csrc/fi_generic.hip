@@ -152,11 +152,20 @@ __global__ __launch_bounds__(kThreads) void k_emit_gradient_linear(Geom g, long 
 	}
 }
 
+// One thread per run of equal (row, col) keys of the sorted triplets: the run's values added left to right in T, i.e. in
+// input order (the sort is stable) -- what Eigen's setFromTriplets does.  (A reduction by key folds the partial sums of its
+// threads and blocks, a + (b + c): other bits.)  Runs are short but for degenerate inputs; a long one costs its length once.
 template <typename T>
-__global__ __launch_bounds__(kThreads) void k_widen(int64_t n, const float* __restrict__ in, T* __restrict__ out)
+__global__ __launch_bounds__(kThreads) void k_fold_runs(int64_t nruns, const uint32_t* __restrict__ start,
+                                                         const uint32_t* __restrict__ len, const float* __restrict__ val,
+                                                         T* __restrict__ out)
 {
-	const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
-	if (i < n) { out[i] = static_cast<T>(in[i]); }
+	const int64_t r = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+	if (r >= nruns) { return; }
+	const float* v = val + start[r];
+	T s = static_cast<T>(v[0]);
+	for (uint32_t k = 1; k < len[r]; ++k) { s += static_cast<T>(v[k]); }
+	out[r] = s;
 }
 
 __global__ __launch_bounds__(kThreads) void k_shift_cols(int64_t n, uint64_t* __restrict__ key, int64_t shift)
@@ -380,20 +389,25 @@ static void generic_assemble_t(fi_ctx* c)
 	}
 	// duplicates: summed in input order (stable sort) -- sparse_linear.hpp:43, Eigen setFromTriplets -- in the
 	// context's precision: fp32 like as_sparse_matrix_float (:59-70), fp64 like as_sparse_matrix_double (:72-93)
-	DevBuf vT;
-	vT.alloc(sizeof(T) * n);
-	hipLaunchKernelGGL((k_widen<T>), dim3(blocks_for(n)), dim3(kThreads), 0, st, static_cast<int64_t>(n), vsort.as<float>(),
-	                   vT.as<T>());
+	DevBuf runlen, runstart, tmp2;
+	runlen.alloc(sizeof(uint32_t) * n);
 	size_t tb2 = 0;
-	FI_HIP_TRY(prim::sum_by_key(nullptr, tb2, ksort.as<uint64_t>(), ukey.as<uint64_t>(), vT.as<T>(), G.csr_val.as<T>(), nruns.as<int>(),
-	                             static_cast<size_t>(n), st));
-	DevBuf tmp2;
+	FI_HIP_TRY(prim::run_length_encode(nullptr, tb2, ksort.as<uint64_t>(), ukey.as<uint64_t>(), runlen.as<uint32_t>(), nruns.as<int>(),
+	                                    static_cast<size_t>(n), st));
 	tmp2.alloc(tb2);
-	FI_HIP_TRY(prim::sum_by_key(tmp2.p, tb2, ksort.as<uint64_t>(), ukey.as<uint64_t>(), vT.as<T>(), G.csr_val.as<T>(), nruns.as<int>(),
-	                             static_cast<size_t>(n), st));
+	FI_HIP_TRY(prim::run_length_encode(tmp2.p, tb2, ksort.as<uint64_t>(), ukey.as<uint64_t>(), runlen.as<uint32_t>(), nruns.as<int>(),
+	                                    static_cast<size_t>(n), st));
 	int nnz = 0;
 	FI_HIP_TRY(hipMemcpyAsync(&nnz, nruns.p, sizeof(int), hipMemcpyDeviceToHost, st));
 	FI_HIP_TRY(hipStreamSynchronize(st));
+	runstart.alloc(sizeof(uint32_t) * nnz);
+	size_t tbs = 0;
+	FI_HIP_TRY(prim::exclusive_sum(nullptr, tbs, runlen.as<uint32_t>(), runstart.as<uint32_t>(), static_cast<size_t>(nnz), st));
+	DevBuf tmps;
+	tmps.alloc(tbs);
+	FI_HIP_TRY(prim::exclusive_sum(tmps.p, tbs, runlen.as<uint32_t>(), runstart.as<uint32_t>(), static_cast<size_t>(nnz), st));
+	hipLaunchKernelGGL((k_fold_runs<T>), dim3(blocks_for(nnz)), dim3(kThreads), 0, st, static_cast<int64_t>(nnz),
+	                   runstart.as<uint32_t>(), runlen.as<uint32_t>(), vsort.as<float>(), G.csr_val.as<T>());
 	G.nnz = nnz;
 	// CSR
 	G.csr_col.alloc(sizeof(uint32_t) * nnz);

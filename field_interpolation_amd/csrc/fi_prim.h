@@ -1,4 +1,4 @@
-// fi_prim.h -- the device-wide primitives of the assembly (scans, run-length encoding, selection, reductions by key, 64-bit
+// fi_prim.h -- the device-wide primitives of the assembly (scans, run-length encoding, selection, 64-bit
 // pair sorts) straight on rocPRIM, ROCm's own primitive library (rounds 1-4 went through hipCUB, the CUB-shaped layer over
 // it).  Same call shape as the library's: a first call with a null workspace returns the bytes it wants.
 #pragma once
@@ -33,15 +33,6 @@ template <typename Out, typename Count, typename Pred>
 inline hipError_t select_indices(void* tmp, size_t& bytes, Out out, Count count_out, size_t n, Pred pred, hipStream_t st)
 {
 	return rocprim::select(tmp, bytes, rocprim::counting_iterator<uint32_t>(0u), out, count_out, n, pred, st);
-}
-
-// sums of the values of every run of equal keys (keys sorted)
-template <typename K, typename V, typename Runs>
-inline hipError_t sum_by_key(void* tmp, size_t& bytes, const K* keys, K* unique_out, const V* values, V* sums_out, Runs runs_out, size_t n,
-                             hipStream_t st)
-{
-	return rocprim::reduce_by_key(tmp, bytes, keys, values, static_cast<unsigned int>(n), unique_out, sums_out, runs_out, rocprim::plus<V>(),
-	                              rocprim::equal_to<K>(), st);
 }
 
 // stable radix sort of (key, value) pairs over key bits [begin_bit, end_bit); 64-bit keys: Onesweep with the workgroup shape

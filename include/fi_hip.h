@@ -205,7 +205,9 @@ int fi_add_border_prior(fi_ctx* ctx, float weight);
 
 /* Generic rows: replaces handing an arbitrary `LinearEquation` (sparse_linear.hpp:18-22) to the solvers,
  * as src/bipolar_2d.cpp:177-302 and src/line_2d.cpp:49-104 do.  Duplicate (row, col) entries are summed
- * (sparse_linear.hpp:43).  Row indices are local to this call (0..nrows-1). */
+ * (sparse_linear.hpp:43) left to right in input order -- the order of the calls, then the order within a call -- in the
+ * context's precision (FI_F32: float additions, FI_F64: the float values widened, double additions), as Eigen's
+ * setFromTriplets does.  Row indices are local to this call (0..nrows-1).  memory: FI_HOST or FI_DEVICE, for both buffers. */
 int fi_add_rows_coo(fi_ctx* ctx, long nrows, long ntriplets, const fi_triplet* triplets, const float* rhs,
                     int memory);
 
