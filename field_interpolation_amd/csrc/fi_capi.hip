@@ -70,6 +70,39 @@ __global__ __launch_bounds__(kThreads) void k_upscale(UpscaleArgs a, int64_t nla
 	out[li] = (wsum == 0.0f) ? 0.0f : fsum / wsum;
 }
 
+// ---- whole fields and handles of their own (the *_field and *_destroy entry points) ----
+// the points of a lattice; every size at least 1
+int64_t lattice_points(int ndim, const int* sizes)
+{
+	int64_t n = 1;
+	for (int d = 0; d < ndim; ++d) {
+		FI_REQUIRE(sizes[d] >= 1, FI_ERR_INVALID, "sizes[%d] = %d", d, sizes[d]);
+		n *= sizes[d];
+	}
+	return n;
+}
+
+// n elements in `memory` on the device: the caller's, or a copy of the host array in buf
+template <typename T>
+const T* on_device(const T* src, int64_t n, int memory, DevBuf& buf)
+{
+	if (memory != FI_HOST) { return src; }
+	buf.alloc(sizeof(T) * n);
+	FI_HIP_TRY(hipMemcpy(buf.p, src, sizeof(T) * n, hipMemcpyHostToDevice));
+	return buf.as<T>();
+}
+
+// fi_mesh_destroy / fi_points_destroy / fi_surface_destroy: the object's buffers go back on the device it lives on
+template <typename Handle>
+int destroy_handle(Handle* h)
+{
+	if (!h) { return FI_OK; }
+	int dev = 0;
+	const bool switched = hipGetDevice(&dev) == hipSuccess && dev != h->device && hipSetDevice(h->device) == hipSuccess;
+	delete h;
+	if (switched) { (void)hipSetDevice(dev); }
+	return FI_OK;
+}
 
 }  // namespace
 
@@ -1009,13 +1042,10 @@ int fi_upscale_field(const float* small_field, int ndim, const int* small_sizes,
 		nl *= large_sizes[d];
 	}
 	fi::DevBuf ds, dl;
-	const float* s = small_field;
+	const float* s = fi::on_device(small_field, ns, memory, ds);
 	float*       o = out;
 	if (memory == FI_HOST) {
-		ds.alloc(sizeof(float) * ns);
 		dl.alloc(sizeof(float) * nl);
-		FI_HIP_TRY(hipMemcpy(ds.p, small_field, sizeof(float) * ns, hipMemcpyHostToDevice));
-		s = ds.as<float>();
 		o = dl.as<float>();
 	}
 	hipLaunchKernelGGL(fi::k_upscale, dim3(fi::blocks_for(nl)), dim3(fi::kThreads), 0, nullptr, a, nl, s, o);
@@ -1046,18 +1076,9 @@ int fi_iso_extract_field(const float* field, int ndim, const int* sizes, float i
 	*out = nullptr;
 	FI_REQUIRE(ndim != 1, FI_ERR_UNSUPPORTED, "iso-contours of a 1-D lattice are not supported");
 	FI_REQUIRE(ndim == 2 || ndim == 3, FI_ERR_INVALID, "ndim must be 2 or 3 (got %d)", ndim);
-	int64_t n = 1;
-	for (int d = 0; d < ndim; ++d) {
-		FI_REQUIRE(sizes[d] >= 1, FI_ERR_INVALID, "sizes[%d] = %d", d, sizes[d]);
-		n *= sizes[d];
-	}
-	fi::DevBuf df;
-	const float* f = field;
-	if (memory == FI_HOST) {
-		df.alloc(sizeof(float) * n);
-		FI_HIP_TRY(hipMemcpy(df.p, field, sizeof(float) * n, hipMemcpyHostToDevice));
-		f = df.as<float>();
-	}
+	const int64_t n = fi::lattice_points(ndim, sizes);
+	fi::DevBuf   df;
+	const float* f = fi::on_device(field, n, memory, df);
 	fi::iso_extract_whole(f, ndim, sizes, iso, 1, nullptr, nullptr, nullptr, out);
 	FI_API_END
 }
@@ -1083,24 +1104,10 @@ int fi_dual_contour_field(const float* field, const float* gradients, int ndim, 
 	*out = nullptr;
 	FI_REQUIRE(ndim != 1, FI_ERR_UNSUPPORTED, "dual contouring of a 1-D lattice is not supported");
 	FI_REQUIRE(ndim == 2 || ndim == 3, FI_ERR_INVALID, "ndim must be 2 or 3 (got %d)", ndim);
-	int64_t n = 1;
-	for (int d = 0; d < ndim; ++d) {
-		FI_REQUIRE(sizes[d] >= 1, FI_ERR_INVALID, "sizes[%d] = %d", d, sizes[d]);
-		n *= sizes[d];
-	}
+	const int64_t n = fi::lattice_points(ndim, sizes);
 	fi::DevBuf   df, dg;
-	const float* f = field;
-	const float* g = gradients;
-	if (memory == FI_HOST) {
-		df.alloc(sizeof(float) * n);
-		FI_HIP_TRY(hipMemcpy(df.p, field, sizeof(float) * n, hipMemcpyHostToDevice));
-		f = df.as<float>();
-		if (gradients) {
-			dg.alloc(sizeof(float) * ndim * n);
-			FI_HIP_TRY(hipMemcpy(dg.p, gradients, sizeof(float) * ndim * n, hipMemcpyHostToDevice));
-			g = dg.as<float>();
-		}
-	}
+	const float* f = fi::on_device(field, n, memory, df);
+	const float* g = gradients ? fi::on_device(gradients, ndim * n, memory, dg) : nullptr;
 	fi::dual_contour_whole(f, g, ndim, sizes, iso, nullptr, out);
 	FI_API_END
 }
@@ -1130,15 +1137,7 @@ int fi_mesh_copy(const fi_mesh* m, float* vertices, float* normals, int* indices
 	FI_API_END
 }
 
-int fi_mesh_destroy(fi_mesh* m)
-{
-	if (!m) { return FI_OK; }
-	int dev = 0;
-	const bool switched = hipGetDevice(&dev) == hipSuccess && dev != m->device && hipSetDevice(m->device) == hipSuccess;
-	delete m;
-	if (switched) { (void)hipSetDevice(dev); }
-	return FI_OK;
-}
+int fi_mesh_destroy(fi_mesh* m) { return fi::destroy_handle(m); }
 
 
 
@@ -1263,15 +1262,7 @@ int fi_points_distance_field(fi_points* h, const int* sizes, float max_distance,
 	FI_API_END
 }
 
-int fi_points_destroy(fi_points* h)
-{
-	if (!h) { return FI_OK; }
-	int dev = 0;
-	const bool switched = hipGetDevice(&dev) == hipSuccess && dev != h->device && hipSetDevice(h->device) == hipSuccess;
-	delete h;
-	if (switched) { (void)hipSetDevice(dev); }
-	return FI_OK;
-}
+int fi_points_destroy(fi_points* h) { return fi::destroy_handle(h); }
 
 
 // ---- distances to a surface; redistancing (fi_surface.hip) -------------------------------------
@@ -1304,20 +1295,8 @@ int fi_surface_create(fi_surface** out, int ndim, long num_vertices, const float
 	std::unique_ptr<fi_surface> h(new fi_surface());
 	FI_HIP_TRY(hipGetDevice(&h->device));
 	fi::DevBuf   bv, bi;
-	const float* v = vertices;
-	const int*   i = indices;
-	if (memory == FI_HOST) {
-		if (num_vertices > 0) {
-			bv.alloc(sizeof(float) * ndim * num_vertices);
-			FI_HIP_TRY(hipMemcpy(bv.p, vertices, sizeof(float) * ndim * num_vertices, hipMemcpyHostToDevice));
-			v = bv.as<float>();
-		}
-		if (num_primitives > 0) {
-			bi.alloc(sizeof(int) * ndim * num_primitives);
-			FI_HIP_TRY(hipMemcpy(bi.p, indices, sizeof(int) * ndim * num_primitives, hipMemcpyHostToDevice));
-			i = bi.as<int>();
-		}
-	}
+	const float* v = num_vertices > 0 ? fi::on_device(vertices, static_cast<int64_t>(ndim) * num_vertices, memory, bv) : vertices;
+	const int*   i = num_primitives > 0 ? fi::on_device(indices, static_cast<int64_t>(ndim) * num_primitives, memory, bi) : indices;
 	fi::surface_build(h->t, ndim, num_vertices, v, num_primitives, i, nullptr);
 	*out = h.release();
 	FI_API_END
@@ -1357,15 +1336,7 @@ int fi_surface_distance_field(fi_surface* h, const int* sizes, float max_distanc
 	FI_API_END
 }
 
-int fi_surface_destroy(fi_surface* h)
-{
-	if (!h) { return FI_OK; }
-	int dev = 0;
-	const bool switched = hipGetDevice(&dev) == hipSuccess && dev != h->device && hipSetDevice(h->device) == hipSuccess;
-	delete h;
-	if (switched) { (void)hipSetDevice(dev); }
-	return FI_OK;
-}
+int fi_surface_destroy(fi_surface* h) { return fi::destroy_handle(h); }
 
 int fi_redistance(fi_ctx* c, const float* field, float iso, int method, float max_distance, float* out, long long* primitives,
                   fi_mesh** mesh, int memory)
@@ -1387,19 +1358,10 @@ int fi_redistance_field(const float* field, int ndim, const int* sizes, float is
 	FI_REQUIRE(field && sizes, FI_ERR_INVALID, "null argument");
 	check_redistance(method, max_distance, out, memory);
 	FI_REQUIRE(ndim == 2 || ndim == 3, FI_ERR_UNSUPPORTED, "redistancing a %d-D lattice is not supported", ndim);
-	int64_t n = 1;
-	for (int d = 0; d < ndim; ++d) {
-		FI_REQUIRE(sizes[d] >= 1, FI_ERR_INVALID, "sizes[%d] = %d", d, sizes[d]);
-		n *= sizes[d];
-	}
+	const int64_t n = fi::lattice_points(ndim, sizes);
 	FI_REQUIRE(n < (int64_t(1) << 31), FI_ERR_UNSUPPORTED, "a lattice of %lld points", static_cast<long long>(n));
 	fi::DevBuf   df;
-	const float* f = field;
-	if (memory == FI_HOST) {
-		df.alloc(sizeof(float) * n);
-		FI_HIP_TRY(hipMemcpy(df.p, field, sizeof(float) * n, hipMemcpyHostToDevice));
-		f = df.as<float>();
-	}
+	const float* f = fi::on_device(field, n, memory, df);
 	fi::redistance_whole(f, ndim, sizes, iso, method, max_distance, out, primitives, mesh, memory, nullptr);
 	FI_API_END
 }

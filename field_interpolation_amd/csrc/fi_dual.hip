@@ -97,27 +97,6 @@ __device__ inline unsigned emits(const DualView& v, const int* c, unsigned m)
 	return out;
 }
 
-// exclusive prefix of x over the workgroup; *total: the workgroup's sum (every thread)
-__device__ inline uint32_t block_scan(uint32_t x, uint32_t* total)
-{
-	__shared__ uint32_t s[kDualThreads / 64];
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	uint32_t inc = x;
-	for (int o = 1; o < 64; o <<= 1) {
-		const uint32_t y = __shfl_up(inc, o, 64);
-		if (lane >= o) { inc += y; }
-	}
-	if (lane == 63) { s[wave] = inc; }
-	__syncthreads();
-	uint32_t pre = 0, all = 0;
-	for (int w = 0; w < kDualThreads / 64; ++w) {
-		pre += w < wave ? s[w] : 0u;
-		all += s[w];
-	}
-	*total = all;
-	return pre + inc - x;
-}
-
 // (is the cell active, its primitives) of dense cell i; *base: its lowest corner's lattice index
 template <int D>
 __device__ inline void cell_counts(const DualView& v, int64_t i, int64_t* base, uint32_t* nv, uint32_t* np, bool* bad)
@@ -144,9 +123,9 @@ __global__ __launch_bounds__(kDualThreads) void k_dc_count(DualView v, uint32_t*
 	}
 	if (__any(bad) && (threadIdx.x & 63) == 0) { atomicOr(flag, 1u); }
 	uint32_t tv = 0, tp = 0;
-	(void)block_scan(nv, &tv);
+	(void)block_scan<kDualThreads>(nv, &tv);
 	__syncthreads();
-	(void)block_scan(np, &tp);
+	(void)block_scan<kDualThreads>(np, &tp);
 	if (threadIdx.x == 0) {
 		wg_v[blockIdx.x] = tv;
 		wg_p[blockIdx.x] = tp;
@@ -172,9 +151,9 @@ __global__ __launch_bounds__(kDualThreads) void k_dc_compact(DualView v, const u
 	bool bad = false;
 	if (i < v.ncell) { cell_counts<D>(v, i, &base, &nv, &np, &bad); }
 	uint32_t tv = 0, tp = 0;
-	const uint32_t pv = block_scan(nv, &tv);
+	const uint32_t pv = block_scan<kDualThreads>(nv, &tv);
 	__syncthreads();
-	const uint32_t pp = block_scan(np, &tp);
+	const uint32_t pp = block_scan<kDualThreads>(np, &tp);
 	if (nv == 0) { return; }
 	const uint64_t k = off_v[blockIdx.x] + pv;
 	key[k] = base;
@@ -453,18 +432,7 @@ void run(const DualView& v0, hipStream_t st, fi_mesh* m)
 	FI_HIP_TRY(hipStreamSynchronize(st));
 }
 
-void check_dims(int ndim, const int* sizes)
-{
-	FI_REQUIRE(sizes != nullptr, FI_ERR_INVALID, "sizes is null");
-	FI_REQUIRE(ndim != 1, FI_ERR_UNSUPPORTED, "dual contouring of a 1-D lattice is not supported");
-	FI_REQUIRE(ndim == 2 || ndim == 3, FI_ERR_INVALID, "ndim must be 2 or 3 (got %d)", ndim);
-	int64_t n = 1;
-	for (int d = 0; d < ndim; ++d) {
-		FI_REQUIRE(sizes[d] >= 1, FI_ERR_INVALID, "sizes[%d] = %d", d, sizes[d]);
-		n *= sizes[d];
-	}
-	FI_REQUIRE(n < (int64_t(1) << 40), FI_ERR_UNSUPPORTED, "lattice too large");
-}
+void check_dims(int ndim, const int* sizes) { check_mesh_dims(ndim, sizes, "dual contouring of a 1-D lattice is not supported"); }
 
 }  // namespace
 
@@ -501,22 +469,7 @@ void dual_contour_ctx(fi_ctx* c, const float* field, const float* gradients, flo
 	FI_REQUIRE((!field && !gradients) || memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
 	AllocStream alloc_on(c->stream);
 	DevBuf buf, gbuf;
-	const float* f = nullptr;
-	if (field && memory == FI_DEVICE) {
-		f = field;
-	} else if (field) {
-		buf.alloc(sizeof(float) * g.nown);
-		FI_HIP_TRY(hipMemcpyAsync(buf.p, field, sizeof(float) * g.nown, hipMemcpyHostToDevice, c->stream));
-		f = buf.as<float>();
-	} else if (c->dtype == FI_F32) {
-		f = owned<float>(c, c->x);
-	} else {  // an fp64 solution, rounded to fp32 as fi_solve_cg's `out` is
-		buf.alloc(sizeof(float) * g.nown);
-		hipLaunchKernelGGL((k_to_float<double>), dim3(blocks_for(g.nown)), dim3(kThreads), 0, c->stream, g.nown,
-		                   owned<double>(c, c->x), buf.as<float>());
-		FI_HIP_TRY(hipGetLastError());
-		f = buf.as<float>();
-	}
+	const float* f = field_f32(c, field, memory, buf);
 	const float* gr = gradients;
 	if (gradients && memory == FI_HOST) {
 		gbuf.alloc(sizeof(float) * g.ndim * g.nown);

@@ -163,6 +163,16 @@ struct DevBuf {
 	T* as() const { return static_cast<T*>(p); }
 };
 
+// The tree part of a search structure (fi_bvh.h: NearestIndex in fi_nearest.h, SurfaceIndex in fi_surface.h): the usable
+// items in sorted order (float4 slots; `ids`: their indices where the slots have no room for them) and an implicit balanced
+// binary tree over leaves of consecutive items: node k (root 1, children 2k and 2k + 1) keeps its box as two float4 (lo, hi)
+// at box[2k], box[2k + 1]; leaf j is node P + j.  Built once, read by any number of queries.
+struct BvhIndex {
+	int64_t nf = 0;   // usable items: the tree's
+	int     H  = 0;   // tree depth: P = 2^H leaves (the last ones may be empty)
+	DevBuf  items, ids, box;
+};
+
 // ---- geometry: the (slab of the) lattice one context owns ------------------------------------------
 // The slowest axis L = ndim-1 is the decomposed one.  Local storage holds `halo` ghost planes on both
 // sides of the owned planes along L; every kernel takes global coordinates from `off`.

@@ -26,4 +26,42 @@ void iso_extract_ctx(fi_ctx* c, const float* field, float iso, int memory, fi_me
 // or nullptr: the members' last solutions, through the same ghost-plane exchange as iso_extract_ctx's slab contexts
 void iso_extract_group(std::vector<fi_ctx*>& members, const float* whole, float iso, fi_mesh** out);
 
+// ---- shared by the mesh extractors (fi_iso.hip, fi_dual.hip) ----------------------------------------------------------
+
+// the lattice a mesh is extracted from: 2-D or 3-D (one_d: the extractor's message for a 1-D one), below 2^40 points
+inline void check_mesh_dims(int ndim, const int* sizes, const char* one_d)
+{
+	FI_REQUIRE(sizes != nullptr, FI_ERR_INVALID, "sizes is null");
+	FI_REQUIRE(ndim != 1, FI_ERR_UNSUPPORTED, "%s", one_d);
+	FI_REQUIRE(ndim == 2 || ndim == 3, FI_ERR_INVALID, "ndim must be 2 or 3 (got %d)", ndim);
+	int64_t n = 1;
+	for (int d = 0; d < ndim; ++d) {
+		FI_REQUIRE(sizes[d] >= 1, FI_ERR_INVALID, "sizes[%d] = %d", d, sizes[d]);
+		n *= sizes[d];
+	}
+	FI_REQUIRE(n < (int64_t(1) << 40), FI_ERR_UNSUPPORTED, "lattice too large");
+}
+
+// exclusive prefix of x over a workgroup of THREADS; *total: the workgroup's sum (every thread)
+template <int THREADS>
+__device__ inline uint32_t block_scan(uint32_t x, uint32_t* total)
+{
+	__shared__ uint32_t s[THREADS / 64];
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	uint32_t inc = x;
+	for (int o = 1; o < 64; o <<= 1) {
+		const uint32_t y = __shfl_up(inc, o, 64);
+		if (lane >= o) { inc += y; }
+	}
+	if (lane == 63) { s[wave] = inc; }
+	__syncthreads();
+	uint32_t pre = 0, all = 0;
+	for (int w = 0; w < THREADS / 64; ++w) {
+		pre += w < wave ? s[w] : 0u;
+		all += s[w];
+	}
+	*total = all;
+	return pre + inc - x;
+}
+
 }  // namespace fi

@@ -108,27 +108,6 @@ __device__ inline unsigned prims_of(unsigned cs)
 	return D == 2 ? iso::kSqCount[cs] : iso::kCubeCount[cs];
 }
 
-// exclusive prefix of x over the workgroup; *total: the workgroup's sum (every thread)
-__device__ inline uint32_t block_scan(uint32_t x, uint32_t* total)
-{
-	__shared__ uint32_t s[kIsoThreads / 64];
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	uint32_t inc = x;
-	for (int o = 1; o < 64; o <<= 1) {
-		const uint32_t y = __shfl_up(inc, o, 64);
-		if (lane >= o) { inc += y; }
-	}
-	if (lane == 63) { s[wave] = inc; }
-	__syncthreads();
-	uint32_t pre = 0, all = 0;
-	for (int w = 0; w < kIsoThreads / 64; ++w) {
-		pre += w < wave ? s[w] : 0u;
-		all += s[w];
-	}
-	*total = all;
-	return pre + inc - x;
-}
-
 template <int D>
 __global__ __launch_bounds__(kIsoThreads) void k_iso_count(IsoView v, uint32_t* __restrict__ wg_v, uint32_t* __restrict__ wg_p,
                                                            uint32_t* __restrict__ flag)
@@ -156,9 +135,9 @@ __global__ __launch_bounds__(kIsoThreads) void k_iso_count(IsoView v, uint32_t* 
 	}
 	if (__any(bad) && (threadIdx.x & 63) == 0) { atomicOr(flag, 1u); }
 	uint32_t tv = 0, tp = 0;
-	(void)block_scan(nv, &tv);
+	(void)block_scan<kIsoThreads>(nv, &tv);
 	__syncthreads();
-	(void)block_scan(np, &tp);
+	(void)block_scan<kIsoThreads>(np, &tp);
 	if (threadIdx.x == 0) {
 		wg_v[blockIdx.x] = tv;
 		wg_p[blockIdx.x] = tp;
@@ -210,7 +189,7 @@ __global__ __launch_bounds__(kIsoThreads) void k_iso_vertices(IsoView v, const u
 		m = crossings<D>(v, c, fc, &bad);
 	}
 	uint32_t total = 0;
-	const uint32_t pre = block_scan(__popc(m), &total);
+	const uint32_t pre = block_scan<kIsoThreads>(__popc(m), &total);
 	if (i >= v.npts) { return; }
 	uint64_t k = wg_off[blockIdx.x] + pre;
 	base[i] = static_cast<uint32_t>(k);
@@ -281,7 +260,7 @@ __global__ __launch_bounds__(kIsoThreads) void k_iso_prims(IsoView v, const uint
 		}
 	}
 	uint32_t total = 0;
-	const uint32_t pre = block_scan(np, &total);
+	const uint32_t pre = block_scan<kIsoThreads>(np, &total);
 	if (np == 0) { return; }
 	const uint64_t k = wg_off[blockIdx.x] + pre;
 	for (unsigned t = 0; t < np; ++t) {
@@ -394,18 +373,7 @@ struct MeshList {  // meshes made so far, destroyed if a later one fails
 	}
 };
 
-void check_dims(int ndim, const int* sizes)
-{
-	FI_REQUIRE(sizes != nullptr, FI_ERR_INVALID, "sizes is null");
-	FI_REQUIRE(ndim != 1, FI_ERR_UNSUPPORTED, "iso-contours of a 1-D lattice are not supported");
-	FI_REQUIRE(ndim == 2 || ndim == 3, FI_ERR_INVALID, "ndim must be 2 or 3 (got %d)", ndim);
-	int64_t n = 1;
-	for (int d = 0; d < ndim; ++d) {
-		FI_REQUIRE(sizes[d] >= 1, FI_ERR_INVALID, "sizes[%d] = %d", d, sizes[d]);
-		n *= sizes[d];
-	}
-	FI_REQUIRE(n < (int64_t(1) << 40), FI_ERR_UNSUPPORTED, "lattice too large");
-}
+void check_dims(int ndim, const int* sizes) { check_mesh_dims(ndim, sizes, "iso-contours of a 1-D lattice are not supported"); }
 
 }  // namespace
 
@@ -439,20 +407,7 @@ void slab_pieces(RankSet& R, const float* const* fields, int memory, float iso, 
 	           "iso extraction over slabs needs %d ghost planes and slabs of at least %d planes (the context stores %d ghost "
 	           "planes, the thinnest slab has %d planes)", want, want, c0->halo, g0.gn[L] / c0->nranks);
 	AllocStream alloc_on(c0->stream);
-	for (size_t r = 0; r < R.size(); ++r) {
-		fi_ctx*     c = R[r];
-		const Geom& g = c->g;
-		FI_REQUIRE(fields[r] || c->vectors_ready, FI_ERR_STATE, "no solution yet");
-		ensure_vectors(c);
-		const size_t es = elem_size(c);
-		if (fields[r]) {
-			c->dtype == FI_F64 ? load_owned<double>(c, c->q, fields[r], memory) : load_owned<float>(c, c->q, fields[r], memory);
-		} else {
-			FI_HIP_TRY(hipMemcpyAsync(static_cast<char*>(c->q.p) + es * g.own_first, static_cast<const char*>(c->x.p) + es * g.own_first,
-			                          es * g.nown, hipMemcpyDeviceToDevice, c->stream));
-		}
-	}
-	halo_exchange(R, &fi_ctx::q, want);
+	slab_fields(R, fields, memory, want);
 	MeshList ms;
 	DevBuf   buf;
 	for (fi_ctx* c : R) {
@@ -488,22 +443,7 @@ void iso_extract_ctx(fi_ctx* c, const float* field, float iso, int memory, fi_me
 	}
 	AllocStream alloc_on(c->stream);
 	DevBuf buf;
-	const float* f = nullptr;
-	if (field && memory == FI_DEVICE) {
-		f = field;
-	} else if (field) {
-		buf.alloc(sizeof(float) * g.nown);
-		FI_HIP_TRY(hipMemcpyAsync(buf.p, field, sizeof(float) * g.nown, hipMemcpyHostToDevice, c->stream));
-		f = buf.as<float>();
-	} else if (c->dtype == FI_F32) {
-		f = owned<float>(c, c->x);
-	} else {  // an fp64 solution, rounded to fp32 as fi_solve_cg's `out` is
-		buf.alloc(sizeof(float) * g.nown);
-		hipLaunchKernelGGL((k_to_float<double>), dim3(blocks_for(g.nown)), dim3(kThreads), 0, c->stream, g.nown,
-		                   owned<double>(c, c->x), buf.as<float>());
-		FI_HIP_TRY(hipGetLastError());
-		f = buf.as<float>();
-	}
+	const float* f = field_f32(c, field, memory, buf);
 	MeshList ms;
 	run_any(g.ndim, piece_view(f, 0, g.ndim, g.gn, iso, 0, g.gn[L]), c->stream, ms.add());
 	ms.hand_out(out);

@@ -7,15 +7,10 @@
 namespace fi {
 
 // The search structure over one point set: the finite points sorted by their Morton code (over their own bounding box),
-// float4 each (x, y, z, the point's index as bits), and an implicit balanced binary tree over leaves of kNearestLeaf
-// consecutive points: node k (root 1, children 2k and 2k + 1) keeps its box as two float4 (lo, hi) at box[2k], box[2k + 1];
-// leaf j is node P + j.  Built once, read by any number of queries.
-struct NearestIndex {
-	int     D  = 0;
-	int64_t n  = 0;   // points of the set (finite or not)
-	int64_t nf = 0;   // finite points: the tree's
-	int     H  = 0;   // tree depth: P = 2^H leaves (the last ones may be empty)
-	DevBuf  pts, box;
+// float4 each (x, y, z, the point's index as bits), under the tree of BvhIndex (fi_internal.h) with leaves of 16 points.
+struct NearestIndex : BvhIndex {
+	int     D = 0;
+	int64_t n = 0;   // points of the set (finite or not)
 };
 
 // the set of a context: its fi_add_points batches in call order, the border prior's left out (PointBatch::prior); built on

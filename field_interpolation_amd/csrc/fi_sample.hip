@@ -370,19 +370,7 @@ void slab_sample(RankSet& R, const float* const* fields, const float* whole, int
 	if (n == 0) { return; }
 	AllocStream alloc_on(c0->stream);
 	Query q(D, n, positions, values, gradients, memory, c0->stream);
-	for (size_t r = 0; r < R.size() && !whole; ++r) {
-		fi_ctx*     c = R[r];
-		const Geom& g = c->g;
-		ensure_vectors(c);
-		const size_t es = elem_size(c);
-		if (fields[r]) {
-			c->dtype == FI_F64 ? load_owned<double>(c, c->q, fields[r], memory) : load_owned<float>(c, c->q, fields[r], memory);
-		} else {
-			FI_HIP_TRY(hipMemcpyAsync(static_cast<char*>(c->q.p) + es * g.own_first, static_cast<const char*>(c->x.p) + es * g.own_first,
-			                          es * g.nown, hipMemcpyDeviceToDevice, c->stream));
-		}
-	}
-	if (!whole) { halo_exchange(R, &fi_ctx::q, want); }
+	if (!whole) { slab_fields(R, fields, memory, want); }  // (no member is without a field: checked above, before n == 0 returns)
 	DevBuf buf, sval, sgrad;  // an fp64 member's values rounded to fp32; members 1.. before they are added to member 0's
 	if (R.size() > 1) {
 		sval.alloc(sizeof(float) * n);
@@ -488,14 +476,7 @@ void sample_ctx(fi_ctx* c, const float* field, int64_t n, const float* positions
 		launch(g.ndim, mode, q.args<double>(owned<double>(c, c->x), g.gn, fill), c->stream);
 	} else {
 		DevBuf       buf;
-		const float* f = field;
-		if (!field) {
-			f = owned<float>(c, c->x);
-		} else if (memory == FI_HOST) {
-			buf.alloc(sizeof(float) * g.nown);
-			FI_HIP_TRY(hipMemcpyAsync(buf.p, field, sizeof(float) * g.nown, hipMemcpyHostToDevice, c->stream));
-			f = buf.as<float>();
-		}
+		const float* f = field_f32(c, field, memory, buf);
 		launch(g.ndim, mode, q.args<float>(f, g.gn, fill), c->stream);
 		q.finish(c->stream);  // (before buf goes)
 		return;

@@ -589,6 +589,43 @@ void ensure_vectors(fi_ctx* c);
 template <typename T> void load_owned(fi_ctx* c, DevBuf& v, const float* src, int memory);
 template <typename T> void store_owned(fi_ctx* c, const DevBuf& v, float* dst, int memory);
 void halo_exchange(RankSet& R, DevBuf fi_ctx::*vec, int width = 0);
+// An undivided context's field as fp32 on the device, for the units that read it whole: the caller's device pointer, a host
+// array staged in buf on the context's stream or, with field == nullptr, the last solution -- the fp32 one in place, the fp64
+// one rounded to fp32 once into buf, as fi_solve_cg's `out` is.  (The caller has checked that there is a field or a solution.)
+inline const float* field_f32(fi_ctx* c, const float* field, int memory, DevBuf& buf)
+{
+	const Geom& g = c->g;
+	if (field && memory == FI_DEVICE) { return field; }
+	if (!field && c->dtype == FI_F32) { return owned<float>(c, c->x); }
+	buf.alloc(sizeof(float) * g.nown);
+	if (field) {
+		FI_HIP_TRY(hipMemcpyAsync(buf.p, field, sizeof(float) * g.nown, hipMemcpyHostToDevice, c->stream));
+	} else {
+		hipLaunchKernelGGL((k_to_float<double>), dim3(blocks_for(g.nown)), dim3(kThreads), 0, c->stream, g.nown, owned<double>(c, c->x),
+		                   buf.as<float>());
+		FI_HIP_TRY(hipGetLastError());
+	}
+	return buf.as<float>();
+}
+// The fields of a set of slab contexts in their work vectors q (local layout) with `want` ghost planes exchanged: member r's
+// owned values fields[r] (fp32, `memory`) or, with nullptr, its last solution.
+inline void slab_fields(RankSet& R, const float* const* fields, int memory, int want)
+{
+	for (size_t r = 0; r < R.size(); ++r) {
+		fi_ctx*     c = R[r];
+		const Geom& g = c->g;
+		FI_REQUIRE(fields[r] || c->vectors_ready, FI_ERR_STATE, "no solution yet");
+		ensure_vectors(c);
+		const size_t es = elem_size(c);
+		if (fields[r]) {
+			c->dtype == FI_F64 ? load_owned<double>(c, c->q, fields[r], memory) : load_owned<float>(c, c->q, fields[r], memory);
+		} else {
+			FI_HIP_TRY(hipMemcpyAsync(static_cast<char*>(c->q.p) + es * g.own_first, static_cast<const char*>(c->x.p) + es * g.own_first,
+			                          es * g.nown, hipMemcpyDeviceToDevice, c->stream));
+		}
+	}
+	halo_exchange(R, &fi_ctx::q, want);
+}
 bool overlap_possible(const fi_ctx* c);
 void exchange_begin(fi_ctx* c, void* v);
 void exchange_wait(fi_ctx* c);

@@ -8,14 +8,11 @@ namespace fi {
 
 // The search structure over one mesh: its usable primitives (every vertex coordinate finite) sorted by the Morton code of
 // their box centres (over the mesh's own bounds), each stored with its vertex coordinates inline -- 3-D: three float4
-// (a, b, c; the primitive's index as bits in the first .w), 2-D: one float4 (ax, ay, bx, by) and the index in `ids` -- and an
-// implicit balanced binary tree over leaves of consecutive primitives, node boxes as in NearestIndex (fi_nearest.h).
-struct SurfaceIndex {
+// (a, b, c; the primitive's index as bits in the first .w), 2-D: one float4 (ax, ay, bx, by) and the index in `ids` -- under
+// the tree of BvhIndex (fi_internal.h) with leaves of 8 primitives.
+struct SurfaceIndex : BvhIndex {
 	int     D  = 0;
 	int64_t np = 0;   // primitives of the mesh (usable or not)
-	int64_t nf = 0;   // usable primitives: the tree's
-	int     H  = 0;   // tree depth: P = 2^H leaves (the last ones may be empty)
-	DevBuf  prims, ids, box;
 };
 
 // a structure built from nv vertices (ndim floats each) and np primitives (ndim int32 indices each) already on the device;

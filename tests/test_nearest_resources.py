@@ -1,4 +1,4 @@
-"""The nearest-point kernels (fi_nearest.hip) against the compiler's resource report the build keeps next to the object
+"""The nearest-point kernels (fi_nearest.hip, and the shared build kernels of fi_bvh.h as this unit instantiates them) against the compiler's resource report the build keeps next to the object
 (field_interpolation_amd/csrc/fi_nearest.usage.txt): no VGPR or SGPR spills, no scratch, no AGPRs."""
 import os
 import re
@@ -20,10 +20,11 @@ def _report():
 
 
 def test_nearest_kernels_spill_nothing_and_use_no_scratch_or_agprs():
-    rep = {k: v for k, v in _report().items() if "k_nearest" in k}
-    # the queries: 1-, 2- and 3-D x (a query buffer, the lattice, the border list); the build: bounds (1-3 D) and their
-    # total, Morton codes (1-3 D), the gather (1-3 D), the leaf boxes, the node boxes
-    assert len(rep) == 9 + 3 + 1 + 3 + 3 + 1 + 1, sorted(rep)
+    rep = {k: v for k, v in _report().items() if "k_nearest" in k or "k_bvh_" in k}
+    # the queries (k_nearest_query): 1-, 2- and 3-D x (a query buffer, the lattice, the border list); the build (k_bvh_*):
+    # bounds (1-3 D) and their total, Morton codes (1-3 D), the gather (1-3 D), the leaf boxes (1-3 D), the node boxes
+    assert len(rep) == 9 + 3 + 1 + 3 + 3 + 3 + 1, sorted(rep)
+    assert sum("k_bvh_" in k for k in rep) == 3 + 1 + 3 + 3 + 3 + 1, sorted(rep)
     for name, r in rep.items():
         assert r["VGPRs Spill"] == 0, name
         assert r["SGPRs Spill"] == 0, name

@@ -1,4 +1,4 @@
-"""The surface-distance kernels (fi_surface.hip) against the compiler's resource report the build keeps next to the object
+"""The surface-distance kernels (fi_surface.hip, and the shared build kernels of fi_bvh.h as this unit instantiates them) against the compiler's resource report the build keeps next to the object
 (field_interpolation_amd/csrc/fi_surface.usage.txt): no VGPR or SGPR spills, no scratch, no AGPRs; the query kernels use
 no LDS and keep the occupancy DESIGN.md 4.9 records."""
 import os
@@ -21,10 +21,11 @@ def _report():
 
 
 def test_surface_kernels_spill_nothing_and_use_no_scratch_or_agprs():
-    rep = {k: v for k, v in _report().items() if "k_surf_" in k}
-    # the queries: 2- and 3-D x (a query buffer, the lattice, the signed lattice); the build: bounds (2-3 D) and their total,
-    # Morton codes (2-3 D), the gather (2-3 D), the leaf boxes (2-3 D), the node boxes
+    rep = {k: v for k, v in _report().items() if "k_surf_" in k or "k_bvh_" in k}
+    # the queries (k_surf_query): 2- and 3-D x (a query buffer, the lattice, the signed lattice); the build (k_bvh_*): bounds
+    # (2-3 D) and their total, Morton codes (2-3 D), the gather (2-3 D), the leaf boxes (2-3 D), the node boxes
     assert len(rep) == 6 + 2 + 1 + 2 + 2 + 2 + 1, sorted(rep)
+    assert sum("k_bvh_" in k for k in rep) == 2 + 1 + 2 + 2 + 2 + 1, sorted(rep)
     for name, r in rep.items():
         assert r["VGPRs Spill"] == 0, name
         assert r["SGPRs Spill"] == 0, name

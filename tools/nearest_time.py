@@ -119,11 +119,11 @@ def summarize(path, kind):
         for r in csv.DictReader(f):
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]) - int(r["Start_Timestamp"]), r["Kernel_Name"]))
     rows.sort()
-    # the builds come first: the launches before the first kernel that is neither a build kernel, rocPRIM's sort nor the
+    # the builds come first: the launches before the first kernel that is neither a build kernel (fi_bvh.h's k_bvh_*), rocPRIM's sort nor the
     # runtime's blits (the zeroed tail of a new buffer, the read-back of the finite count)
     build = []
     for _, d, k in rows:
-        if not (("k_nearest" in k and "k_nearest_query" not in k) or "rocprim" in k or "__amd_rocclr" in k):
+        if not ("k_bvh_" in k or "rocprim" in k or "__amd_rocclr" in k):
             break
         build.append((d, k))
     builds = 1 + REPS

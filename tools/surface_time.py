@@ -8,7 +8,7 @@ for both methods at max_distance = 4 and inf; run it under rocprofv3 --kernel-tr
     python tools/surface_time.py summarize <kernel_trace.csv>
 
 Each (method, max_distance) runs once to warm up and REPS times timed, in the order of COMBOS; `summarize` splits the
-trace's k_surf_* launches into those calls (one k_surf_bounds launch per build) and prints per-call medians of the build
+trace's launches into those calls (one k_bvh_bounds launch per build: fi_bvh.h's build kernels are k_bvh_*) and prints per-call medians of the build
 (every build kernel, rocPRIM's sort between them included, summed) and of the signed lattice query kernel.
 """
 import csv
@@ -82,10 +82,10 @@ def summarize(path):
         for r in csv.DictReader(f):
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
     rows.sort()
-    # a call: from its k_surf_bounds (the first build kernel) to the end of its query kernel
+    # a call: from its k_bvh_bounds (the first build kernel) to the end of its query kernel
     calls, cur = [], None
     for s, e, k in rows:
-        if "k_surf_bounds" in k and "total" not in k:
+        if "k_bvh_bounds" in k and "total" not in k:
             cur = {"start": s, "build": 0, "query": 0, "query_start": None}
             calls.append(cur)
         if cur is None:
@@ -93,7 +93,7 @@ def summarize(path):
         if "k_surf_query" in k:
             cur["query"] += e - s
             cur["query_start"] = s if cur["query_start"] is None else cur["query_start"]
-        elif cur["query_start"] is None and ("k_surf_" in k or "rocprim" in k):
+        elif cur["query_start"] is None and ("k_bvh_" in k or "rocprim" in k):
             cur["build"] += e - s
     per = 1 + REPS
     assert len(calls) == per * len(COMBOS), (len(calls), per * len(COMBOS))
