@@ -27,7 +27,9 @@ SYMBOLS = [
     "fi_nearest", "fi_distance_field", "fi_points_create", "fi_points_nearest", "fi_points_distance_field", "fi_points_destroy",
     "fi_surface_create", "fi_surface_from_mesh", "fi_surface_distance", "fi_surface_distance_field", "fi_surface_destroy",
     "fi_redistance", "fi_redistance_field",
+    "fi_point_count", "fi_point_residuals", "fi_robust_reweight", "fi_reset_point_weights", "fi_solve_robust",
 ]
+FI_LOSS = {"huber": 0, "cauchy": 1, "tukey": 2}
 
 
 class FiWeights(C.Structure):
@@ -57,6 +59,16 @@ class FiStats(C.Structure):
                 ("operator_applies", C.c_int), ("halo_exchanges", C.c_int), ("reductions", C.c_int),
                 ("coarse_unconverged", C.c_int), ("field_estimate", C.c_double), ("field_per_residual", C.c_double),
                 ("stop_residual", C.c_double), ("field_rounds", C.c_int)]
+
+
+class FiRobustOptions(C.Structure):
+    _fields_ = [("loss", C.c_int), ("tuning", C.c_float), ("scale", C.c_float), ("rounds", C.c_int),
+                ("weight_tolerance", C.c_float)]
+
+
+class FiRobustStats(C.Structure):
+    _fields_ = [("rounds", C.c_int), ("iterations", C.c_int), ("scale", C.c_float), ("max_weight_change", C.c_float),
+                ("points_used", C.c_long), ("points_zeroed", C.c_long), ("reweight_ms", C.c_double)]
 
 
 class FiError(RuntimeError):
@@ -147,6 +159,11 @@ def lib():
     L.fi_surface_destroy.argtypes = [vp]
     L.fi_redistance.argtypes = [vp, fp, C.c_float, C.c_int, C.c_float, fp, vp, C.POINTER(vp), C.c_int]
     L.fi_redistance_field.argtypes = [fp, C.c_int, ip, C.c_float, C.c_int, C.c_float, fp, vp, C.POINTER(vp), C.c_int]
+    L.fi_point_count.argtypes = [vp, C.POINTER(C.c_long)]
+    L.fi_point_residuals.argtypes = [vp, fp, fp, C.c_int]
+    L.fi_robust_reweight.argtypes = [vp, fp, C.POINTER(FiRobustOptions), fp, C.POINTER(C.c_float), C.c_int]
+    L.fi_reset_point_weights.argtypes = [vp]
+    L.fi_solve_robust.argtypes = [vp, fp, C.POINTER(FiRobustOptions), C.c_int, C.c_float, fp, fp, C.POINTER(FiRobustStats), C.c_int]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError if the .so lacks a declared symbol
     _LIB = L

@@ -524,6 +524,67 @@ class LatticeField:
             raise
         return out, it.value, rel.value
 
+    # ---- robust fits (include/fi_hip.h, "robust fits") -------------------------------------------------
+    def point_count(self):
+        """The number of data points: every add_points batch in call order, the border prior's rows left out."""
+        n = C.c_long(0)
+        check(_capi.lib().fi_point_count(self._h, C.byref(n)))
+        return n.value
+
+    def _per_point(self, like):
+        n = self.point_count()
+        if like is not None and hasattr(like, "data_ptr") and like.is_cuda:
+            import torch
+            t = torch.empty(n, dtype=torch.float32, device=like.device)
+            return t, C.c_void_p(t.data_ptr())
+        a = np.empty(n, np.float32)
+        return a, C.c_void_p(a.ctypes.data)
+
+    def point_residuals(self, solution=None):
+        """Every data point's residual against `solution` (this context's owned values, host or device) or, with None, the
+        last solve's solution where it lives: the root of the summed squares of the point's rows at unit point weight; -1
+        for a point that emits no row.  Results live where `solution` lives (numpy for None)."""
+        s, smem, _keep = _buf(solution)
+        r, rp = self._per_point(solution)
+        check(_capi.lib().fi_point_residuals(self._h, s, rp, FI_HOST if smem is None else smem))
+        return r
+
+    def robust_reweight(self, solution=None, loss="huber", tuning=0.0, scale=0.0):
+        """One step of iteratively reweighted least squares: residuals -> scale (1.4826 x their median unless given) ->
+        weight factors omega -> point weights base * sqrt(omega); the rows are emitted again and the next solve assembles
+        them.  loss: "huber", "cauchy" or "tukey"; tuning 0: the loss's default constant.  -> (omega, scale); scale 0 means
+        more than half of the points fit exactly and nothing was changed."""
+        s, smem, _keep = _buf(solution)
+        om, op = self._per_point(solution)
+        opt = _capi.FiRobustOptions(_capi.FI_LOSS[loss], float(tuning), float(scale), 0, 0.0)
+        sc = C.c_float(0)
+        check(_capi.lib().fi_robust_reweight(self._h, s, C.byref(opt), op, C.byref(sc), FI_HOST if smem is None else smem))
+        if sc.value != 0.0:
+            self._dirty = True
+        return om, sc.value
+
+    def reset_point_weights(self):
+        """Back to the caller's point weights (every omega 1); the next solve assembles again."""
+        check(_capi.lib().fi_reset_point_weights(self._h))
+        self._dirty = True
+
+    def solve_robust(self, guess=None, loss="huber", tuning=0.0, scale=0.0, rounds=5, weight_tolerance=0.0, max_iterations=0,
+                     error_tolerance=0.0):
+        """A plain solve, then up to `rounds` reweighted ones, each from the previous field, under the solver options this
+        context carries.  Ends early at scale 0 or when no omega moved by weight_tolerance.  Afterwards the context holds the
+        last weights.  -> (field, omega, stats dict: rounds, iterations of all solves, scale, max_weight_change, points_used,
+        points_zeroed, reweight_ms)"""
+        self._ready()
+        g, kg, _kg = _buf(guess)
+        out = self._out(guess)
+        o, ko, _ko = _buf(out)
+        om, op = self._per_point(guess)
+        opt = _capi.FiRobustOptions(_capi.FI_LOSS[loss], float(tuning), float(scale), int(rounds), float(weight_tolerance))
+        st = _capi.FiRobustStats()
+        check(_capi.lib().fi_solve_robust(self._h, g, C.byref(opt), int(max_iterations), float(error_tolerance), o, op,
+                                          C.byref(st), _same_memory(kg, ko)))
+        return out, om, {f: getattr(st, f) for f, _ in st._fields_}
+
     def iso_surface(self, solution=None, iso=0.0, normals=True):
         """The iso-contour (2-D) / iso-surface (3-D) f = iso of `solution` (this context's owned values, host or device) or,
         with None, of the last solve's solution where it lives on the device -- the step src/sdf_field.cpp:605-613 takes

@@ -21,6 +21,7 @@
 #include "fi_prim.h"
 
 #include "fi_internal.h"
+#include "fi_rows.h"
 #include "fi_sort.h"
 #include "fi_nearest.h"
 
@@ -46,31 +47,22 @@ __device__ inline double block_row_sum(const double* B, int q)
 	return s;
 }
 
-struct EmitArgs {
-	Geom  g;
-	float vw, gw;
-	int   vk, gk;
-	int   has_nrm, has_pw, has_val;
-	int   rows_per_point;        // 1 + D, or 1 when the batch has no gradient rows (no normals or a zero gradient weight)
-	uint32_t invalid_key;
-	float pos_scale, nrm_scale;  // 1 on the caller's lattice; 1/2^l and 2^l on coarser levels
-};
-
-// Extended local cell id of the cell with GLOBAL origin c[] (origins run from -1), or invalid when the
-// cell does not touch this rank's slab.
+// the row tables of one batch: what k_emit_rows makes of a point's rows (fi_rows.h)
 template <int D>
-__device__ inline uint32_t cell_key(const Geom& g, const int* c, uint32_t invalid)
-{
-	uint32_t key = 0;
-	uint32_t mul = 1;
-	for (int d = 0; d < D; ++d) {
-		const int l = c[d] - g.coff[d];
-		if (l < 0 || l >= g.cn[d]) { return invalid; }
-		key += static_cast<uint32_t>(l) * mul;
-		mul *= static_cast<uint32_t>(g.cn[d]);
+struct RowWriter {
+	long      slot0;
+	uint32_t* __restrict__ key;
+	float*    __restrict__ coef;
+	float*    __restrict__ rhs;
+	__device__ void row(int r, uint32_t k, const int*, const float* c, float b)
+	{
+		constexpr int NC = 1 << D;
+		const long slot = slot0 + r;
+		key[slot] = k;
+		rhs[slot] = b;
+		for (int q = 0; q < NC; ++q) { coef[slot * NC + q] = c[q]; }
 	}
-	return key;
-}
+};
 
 template <int D>
 __global__ __launch_bounds__(kThreads) void k_emit_rows(EmitArgs a, long n, const float* __restrict__ pos,
@@ -80,143 +72,12 @@ __global__ __launch_bounds__(kThreads) void k_emit_rows(EmitArgs a, long n, cons
                                                          uint32_t* __restrict__ key, float* __restrict__ coef,
                                                          float* __restrict__ rhs)
 {
-	constexpr int NC = 1 << D;
 	const long i = static_cast<long>(blockIdx.x) * kThreads + threadIdx.x;
 	if (i >= n) { return; }
-	const Geom& g = a.g;
-
-	float p[D];
-	bool  finite = true;
-	for (int d = 0; d < D; ++d) {
-		p[d]   = pos[i * D + d] * a.pos_scale;
-		if (g.pshift[d] != 0.0f) { p[d] += g.pshift[d]; }  // a level halved cell-centred along d
-		finite = finite && isfinite(p[d]);
-	}
 	const float w     = a.has_pw ? pw[i] : 1.0f;
 	const float value = a.has_val ? val[i] : 0.0f;
-	const long  slot0 = i * a.rows_per_point;
-
-	// cell of the point: floor(pos) per axis (multilerp :29-32, cell_index :115)
-	int   cell[D];
-	float t[D];
-	bool  cell_in_ext = finite;  // origin within [-1, size-1] on every axis
-	bool  cell_valid  = finite;  // 0 <= origin and origin + 1 < size (cell_index :116)
-	for (int d = 0; d < D; ++d) {
-		const float fl = floorf(p[d]);
-		if (!(fl >= -1.0f && fl <= static_cast<float>(g.gn[d] - 1))) {
-			cell_in_ext = false;
-			cell_valid  = false;
-			cell[d]     = 0;
-			t[d]        = 0.0f;
-			continue;
-		}
-		cell[d] = static_cast<int>(fl);
-		t[d]    = p[d] - static_cast<float>(cell[d]);
-		if (!(0 <= cell[d] && cell[d] + 1 < g.gn[d])) { cell_valid = false; }
-	}
-
-	// ---- value row ----------------------------------------------------------------------------
-	{
-		const float cw = w * a.vw;
-		uint32_t k = a.invalid_key;
-		float    c[NC];
-		float    b = 0.0f;
-		for (int q = 0; q < NC; ++q) { c[q] = 0.0f; }
-		if (a.vk == FI_VALUE_LINEAR_INTERPOLATION) {
-			// field_interpolation.cpp:57-80: corners outside the lattice are dropped, the kept weights
-			// are not renormalised; rhs = (sum of kept coefficient) * value.
-			if (cw != 0.0f && cell_in_ext) {
-				int   kept = 0;
-				float sum  = 0.0f;
-				for (int q = 0; q < NC; ++q) {
-					float lw = 1.0f;
-					bool  in = true;
-					for (int d = 0; d < D; ++d) {
-						const int up = (q >> d) & 1;
-						const int cc = cell[d] + up;
-						lw *= up ? t[d] : 1.0f - t[d];
-						in = in && (0 <= cc) && (cc < g.gn[d]);
-					}
-					if (in) {
-						const float s = lw * cw;
-						c[q] = s;
-						sum += s;
-						++kept;
-					}
-				}
-				if (kept > 0) {
-					k = cell_key<D>(g, cell, a.invalid_key);
-					b = sum * value;
-				}
-			}
-		} else {
-			// field_interpolation.cpp:82-107 through add_equation (sparse_linear.cpp:34-50): nearest
-			// lattice point by std::round; row [1]*cw, rhs (value - (pos-nearest).gradient)*cw.
-			if (cw != 0.0f && finite) {
-				bool  ok    = true;
-				float along = 0.0f;
-				int   corner = 0;
-				int   cc[D];
-				for (int d = 0; d < D; ++d) {
-					const float r = roundf(p[d]);
-					if (!(r >= 0.0f && r <= static_cast<float>(g.gn[d] - 1))) {
-						ok = false;
-						cc[d] = 0;
-						continue;
-					}
-					const int q = static_cast<int>(r);
-					along += (p[d] - static_cast<float>(q)) * (nrm[i * D + d] * a.nrm_scale);
-					// the nearest point is a corner of the (extended) cell floor(pos)
-					int base = static_cast<int>(floorf(p[d]));
-					if (base < -1) { base = -1; }
-					if (base > q) { base = q; }
-					if (q - base > 1) { base = q - 1; }
-					cc[d] = base;
-					corner |= (q - base) << d;
-				}
-				if (ok) {
-					k = cell_key<D>(g, cc, a.invalid_key);
-					c[corner] = 1.0f * cw;
-					b = (value - along) * cw;
-				}
-			}
-		}
-		key[slot0] = k;
-		rhs[slot0] = b;
-		for (int q = 0; q < NC; ++q) { coef[slot0 * NC + q] = c[q]; }
-	}
-
-	// ---- gradient rows ------------------------------------------------------------------------
-	if (a.rows_per_point == 1) { return; }
-	for (int d = 0; d < D; ++d) {
-		const long slot = slot0 + 1 + d;
-		uint32_t k = a.invalid_key;
-		float    c[NC];
-		float    b = 0.0f;
-		for (int q = 0; q < NC; ++q) { c[q] = 0.0f; }
-		if (a.has_nrm) {
-			const float cw = w * a.gw;
-			const float gd = nrm[i * D + d] * a.nrm_scale;
-			if (cw != 0.0f && cell_valid) {
-				if (a.gk == FI_GRADIENT_NEAREST_NEIGHBOR) {
-					// field_interpolation.cpp:134-149: [-1, +1]*cw on the cell edge along d.
-					c[0]      = -1.0f * cw;
-					c[1 << d] = +1.0f * cw;
-					b         = gd * cw;
-					k         = cell_key<D>(g, cell, a.invalid_key);
-				} else if (a.gk == FI_GRADIENT_CELL_EDGES) {
-					// field_interpolation.cpp:150-187: +-cw*2/2^D on all corners, rhs cw*g_d.
-					const float term = cw * 2.0f / static_cast<float>(NC);
-					for (int q = 0; q < NC; ++q) { c[q] = (((q >> d) & 1) ? +1.0f : -1.0f) * term; }
-					b = cw * gd;
-					k = cell_key<D>(g, cell, a.invalid_key);
-				}
-			}
-		}
-		key[slot] = k;
-		rhs[slot] = b;
-		for (int q = 0; q < NC; ++q) { coef[slot * NC + q] = c[q]; }
-	}
+	RowWriter<D> out{i * a.rows_per_point, key, coef, rhs};
+	point_rows<D>(a, i, pos, nrm, w, w, value, out);
 }
 
 __global__ void k_iota(uint32_t* v, long n)

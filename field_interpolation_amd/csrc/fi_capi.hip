@@ -7,6 +7,7 @@
 #include "fi_sample.h"
 #include "fi_nearest.h"
 #include "fi_surface.h"
+#include "fi_robust.h"
 
 #include <memory>
 
@@ -399,6 +400,9 @@ void add_points_device(fi_ctx* c, long n, const float* p, const float* g, const 
 		};
 		b->n = n;
 		b->prior = false;
+		b->reweighted = false;  // (a new batch carries the caller's weights; the robust factors start again from 1)
+		b->had_pw     = false;
+		c->robust.n   = 0;
 		keep(b->pos, p, static_cast<size_t>(n) * D);
 		b->has_nrm = keep(b->nrm, g, static_cast<size_t>(n) * D);
 		b->has_pw  = keep(b->pw, w, static_cast<size_t>(n));
@@ -469,6 +473,7 @@ int fi_clear_points(fi_ctx* c)
 	c->pending.clear();
 	for (auto* b : c->batches) { c->batches_pool.push_back(b); }
 	c->batches.clear();
+	c->robust.n = 0;
 	fi::nearest_release(c);
 	fi::generic_clear(c);
 	c->assembled = false;
@@ -892,6 +897,107 @@ int fi_error_map(fi_ctx* c, const float* solution, float* out, int memory)
 		fi::error_map(c, c->x.p, c->q.p);
 		fi::store_owned<float>(c, c->q, out, memory);
 	}
+	FI_API_END
+}
+
+// ---- robust fits (fi_robust.hip) ---------------------------------------------------------------------
+int fi_point_count(const fi_ctx* c, long* n)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	FI_REQUIRE(n != nullptr, FI_ERR_INVALID, "null output");
+	*n = fi::robust_point_count(c);
+	FI_API_END
+}
+
+int fi_point_residuals(fi_ctx* c, const float* field, float* residuals, int memory)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::robust_residuals(c, field, residuals, memory);
+	FI_API_END
+}
+
+int fi_robust_reweight(fi_ctx* c, const float* field, const fi_robust_options* options, float* omega, float* scale, int memory)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	FI_REQUIRE(options != nullptr, FI_ERR_INVALID, "options is null");
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	const fi::RobustStep step = fi::robust_reweight(c, field, options->loss, options->tuning, options->scale, omega, memory);
+	if (scale) { *scale = step.scale; }
+	FI_API_END
+}
+
+int fi_reset_point_weights(fi_ctx* c)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	fi::robust_reset(c);
+	FI_API_END
+}
+
+int fi_solve_robust(fi_ctx* c, const float* guess, const fi_robust_options* options, int max_iterations, float tol, float* out,
+                    float* omega, fi_robust_stats* stats, int memory)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	FI_REQUIRE(options != nullptr, FI_ERR_INVALID, "options is null");
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	FI_REQUIRE(options->rounds >= 0, FI_ERR_INVALID, "rounds = %d", options->rounds);
+	FI_REQUIRE(options->weight_tolerance >= 0.0f, FI_ERR_INVALID, "weight_tolerance must be >= 0");
+	const long n = fi::robust_check(c);  // (every refusal before any work)
+	fi_robust_stats rs{};
+	if (stats) { *stats = rs; }
+	auto ok = [](int code) {  // the entry has left its message with fi_last_error
+		if (code != FI_OK) { throw fi::Fail{code}; }
+	};
+	if (!c->assembled) { ok(fi_assemble(c)); }
+	int it = 0;
+	ok(fi_solve_cg(c, guess, max_iterations, tol, out, &it, nullptr, memory));
+	rs.iterations = it;
+	struct Start {  // the rounds start from the previous solution in the context's precision, kept beside the solver's vectors
+		fi_ctx* c;
+		~Start() { c->guess_native = nullptr; }
+	} start{c};
+	const size_t es = fi::elem_size(c);
+	bool weighted = false;
+	for (int round = 0; round < options->rounds; ++round) {
+		const auto t0 = std::chrono::steady_clock::now();
+		c->robust.xkeep.alloc(es * c->g.nown);
+		FI_HIP_TRY(hipMemcpyAsync(c->robust.xkeep.p, static_cast<const char*>(c->x.p) + es * c->g.own_first, es * c->g.nown,
+		                          hipMemcpyDeviceToDevice, c->stream));
+		const fi::RobustStep step = fi::robust_reweight(c, nullptr, options->loss, options->tuning, options->scale, nullptr, memory);
+		rs.reweight_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+		rs.scale             = step.scale;
+		rs.max_weight_change = step.max_weight_change;
+		rs.points_used       = step.points_used;
+		rs.points_zeroed     = step.points_zeroed;
+		if (step.scale == 0.0f) { break; }  // nothing changed: the field is the fit of the weights the context holds
+		weighted = true;
+		ok(fi_assemble(c));
+		c->guess_native = c->robust.xkeep.p;
+		const int code = fi_solve_cg(c, nullptr, max_iterations, tol, out, &it, nullptr, memory);
+		c->guess_native = nullptr;
+		ok(code);
+		rs.iterations += it;
+		rs.rounds = round + 1;
+		if (options->weight_tolerance > 0.0f && step.max_weight_change < options->weight_tolerance) { break; }
+	}
+	if (omega) {
+		if (weighted || c->robust.n == n) {
+			FI_HIP_TRY(hipMemcpy(omega, c->robust.omega.p, sizeof(float) * n, memory == FI_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+		} else {  // no step taken: every factor is 1
+			std::vector<float> ones(static_cast<size_t>(n), 1.0f);
+			FI_HIP_TRY(hipMemcpy(omega, ones.data(), sizeof(float) * n, memory == FI_HOST ? hipMemcpyHostToHost : hipMemcpyHostToDevice));
+		}
+	}
+	if (stats) { *stats = rs; }
 	FI_API_END
 }
 

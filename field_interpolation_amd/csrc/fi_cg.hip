@@ -872,7 +872,9 @@ void solve_cg_t(fi_ctx* c, const float* guess, int max_iterations, float tol, fl
 		fi_ctx* c; int* it; float* rel;
 		~Report() { if (it) { *it = c->stats.iterations; } if (rel) { *rel = static_cast<float>(c->stats.rel_residual); } }
 	} report{c, iterations, rel_residual};
-	if (!guess && c->twin && c->twin->coarse) {
+	if (c->guess_native) {  // (fi_solve_robust: the previous round's solution, unrounded)
+		FI_HIP_TRY(hipMemcpyAsync(owned<T>(c, c->x), c->guess_native, sizeof(T) * c->g.nown, hipMemcpyDeviceToDevice, c->stream));
+	} else if (!guess && c->twin && c->twin->coarse) {
 		twin_cascade_guess(R);  // coarse-to-fine start on the fp32 replica, widened
 	} else if (!guess && c->coarse) {
 		cascade_guess<T>(R);
@@ -885,7 +887,7 @@ void solve_cg_t(fi_ctx* c, const float* guess, int max_iterations, float tol, fl
 		return;
 	}
 	if (c->mg_mode == 1 && (c->coarse || (c->twin && c->twin->coarse))) {
-		c->predictable_start = !guess;
+		c->predictable_start = !guess && !c->guess_native;
 		cg_run_mg<T>(R, max_iterations, tol);
 	} else if (poly_ok(c)) {
 		cg_run_poly_or_jacobi<T>(R, max_iterations, tol);

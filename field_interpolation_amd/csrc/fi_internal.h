@@ -315,6 +315,20 @@ struct PointBatch {
 	float  vw = 0, gw = 0;
 	int    vk = 0, gk = 0;
 	bool   prior = false;  // the rows of fi_add_border_prior: lattice points, not data -- no distance source of a later call
+	// robust fits (fi_robust.hip): once reweighted, pw holds base * sqrt(omega) and the caller's weights wait in pw0 (had_pw;
+	// without them base = 1 and pw was allocated by the reweighting).  base is never overwritten
+	DevBuf pw0;
+	bool   reweighted = false, had_pw = false;
+};
+
+// Robust fits (fi_robust.hip): what a reweighting step of a context keeps between its rounds.
+struct RobustState {
+	long   n = 0;        // data points omega[] is valid for (0: every omega is 1 -- no reweighting since the points changed)
+	DevBuf omega;        // float[n]  the last weight factors, in point order
+	DevBuf r, keys, sorted, tmp;  // float[n] residuals, their sort keys before and after, the sort's workspace
+	DevBuf rec;          // RobustRecord
+	DevBuf field;        // a caller's field staged / widened to the context's precision
+	DevBuf xkeep;        // fi_solve_robust: the last round's solution in the context's precision (the next solve's start)
 };
 
 struct Comm;  // RCCL state (fi_comm.cpp)
@@ -369,6 +383,9 @@ struct fi_ctx {
 	std::vector<fi::Pending*> pending;
 	std::vector<fi::Pending*> pending_pool;  // buffers of cleared batches, reused by the next fi_add_points
 	std::vector<fi::PointBatch*> batches, batches_pool;  // the points themselves (for coarser levels)
+	fi::RobustState robust;
+	const void* guess_native = nullptr;  // fi_solve_robust: the next solve starts from these owned values (device, the context's
+	                                     // precision) instead of the caller's fp32 guess
 	fi::NearestIndex* nearest = nullptr;  // built by the first nearest-point query, dropped by fi_add_points / fi_clear_points
 
 	// multilevel: coarser replicas of this problem (lattice halved per level), owned by the finest context

@@ -36,4 +36,10 @@ inline hipError_t sort_pairs_u32(void* tmp, size_t& bytes, const uint32_t* keys_
 	return rocprim::radix_sort_pairs<sort_detail::onesweep<9>>(tmp, bytes, keys_in, keys_out, values_in, values_out, n, b0, b1, stream);
 }
 
+// keys alone (the residuals of a robust fit, fi_robust.hip), all 32 bits
+inline hipError_t sort_keys_u32(void* tmp, size_t& bytes, const uint32_t* keys_in, uint32_t* keys_out, unsigned int n, hipStream_t stream)
+{
+	return rocprim::radix_sort_keys<sort_detail::onesweep<9>>(tmp, bytes, keys_in, keys_out, n, 0u, 32u, stream);
+}
+
 }  // namespace fi

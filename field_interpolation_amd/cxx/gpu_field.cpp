@@ -184,6 +184,43 @@ std::vector<float> GpuLatticeField::solve(int max_iterations, float error_tolera
 	return out;
 }
 
+std::vector<float> GpuLatticeField::solve_robust(const RobustOptions& options, int max_iterations, float error_tolerance,
+                                                 std::vector<float>* point_weights)
+{
+	if (!assemble()) { return {}; }
+	long n = 0;
+	if (fi_point_count(ctx_, &n) != FI_OK) { return {}; }
+	const fi_robust_options opt{static_cast<int>(options.loss), options.tuning, options.scale, options.rounds, options.weight_tolerance};
+	std::vector<float> out(num_unknowns());
+	if (point_weights) { point_weights->resize(static_cast<size_t>(n)); }
+	fi_robust_stats st{};
+	if (fi_solve_robust(ctx_, nullptr, &opt, max_iterations, error_tolerance, out.data(), (point_weights && n > 0) ? point_weights->data() : nullptr,
+	                    &st, FI_HOST) != FI_OK) {
+		warn("robust solve failed");
+		return {};
+	}
+	iterations_ = st.iterations;
+	error_      = 0;
+	fi_stats s{};
+	if (fi_get_stats(ctx_, &s) == FI_OK) { error_ = static_cast<float>(s.rel_residual); }
+	return out;
+}
+
+bool GpuLatticeField::point_residuals(std::vector<float>* residuals) const
+{
+	long n = 0;
+	if (!residuals || fi_point_count(ctx_, &n) != FI_OK) {
+		warn("point_residuals");
+		return false;
+	}
+	residuals->resize(static_cast<size_t>(n));
+	if (fi_point_residuals(ctx_, nullptr, residuals->data(), FI_HOST) != FI_OK) {
+		warn("point_residuals");
+		return false;
+	}
+	return true;
+}
+
 std::vector<float> GpuLatticeField::solve_tiled_with_guess(const std::vector<float>& guess, const SolveOptions& options)
 {
 	if (guess.size() != num_unknowns()) {

@@ -345,6 +345,79 @@ int fi_tile_pass(fi_ctx* ctx, const float* guess, int tile_size, float* out, int
  * fi_add_points are read from the row tables of the last batches (kept until fi_clear_points). */
 int fi_error_map(fi_ctx* ctx, const float* solution, float* out, int memory);
 
+/* ---- robust fits: data points reweighted by their residuals ------------------------------------
+ * Iteratively reweighted least squares for data with gross errors: solve, measure every point's residual, lower the weight
+ * of the points that disagree with the fit, solve again from the previous field.  The contract ("Robust
+ * fits") is this project's own; the reference has no counterpart (its demo only injects the outliers, src/sdf_field.cpp:323-328).
+ *   - a DATA POINT is a point of a fi_add_points batch that is not a border-prior batch; points are numbered in call order,
+ *     then by order within a call; a context of n points uses these numbers in every buffer below;
+ *   - residual of a point: its rows as fi_add_points forms them with the point weight set to 1 (cw = value_weight for the value
+ *     row, gradient_weight for the gradient rows).  Per row e = sum_q c[q] x[corner q] - b, q = 0 .. 2^D - 1 left to right
+ *     (corners outside the lattice have c = 0 and are not read); r = sqrt(e_value^2 + e_0^2 + ... + e_(D-1)^2), squared and
+ *     added in that order over the rows the point emits.  FI_F32 contexts: every operation in float.  FI_F64 contexts:
+ *     coefficients and rhs formed in float exactly as the rows are, then widened; x, the sums and the sqrt in double; r rounded
+ *     to float once.  A point that emits no row (outside the lattice, non-finite, base weight 0) has r = -1 and takes no part
+ *     in anything below;
+ *   - scale: M = the points with r >= 0, med = the element of rank (M - 1) / 2 (integer division) of their r in ascending
+ *     order, s = 1.4826f * med in float; a caller's scale > 0 replaces it;
+ *   - weight factor, all in float: u = r / (s * c), the product formed first; c the tuning constant, 0 = the loss's default:
+ *       FI_LOSS_HUBER   c = 1.345   omega = u <= 1 ? 1 : 1 / u
+ *       FI_LOSS_CAUCHY  c = 2.385   omega = 1 / (1 + u * u)
+ *       FI_LOSS_TUKEY   c = 4.685   omega = u < 1 ? (1 - u * u)^2 : 0, the square as one product
+ *     points with r = -1 keep omega = 1;
+ *   - new point weight pw_i = base_i * sqrtf(omega_i): a row weight enters the objective squared, so this puts omega on the
+ *     point's squared residual.  base_i is the weight the caller gave, or 1; it is kept and never overwritten: every
+ *     reweighting starts from base, not from the last omega;
+ *   - s = 0 (more than half of the points fit exactly): the step changes nothing and reports scale 0; a loop ends there.
+ * FI_ERR_UNSUPPORTED: slab contexts and group members (a rank holds only its own points and the median is global, as for
+ * fi_add_border_prior); contexts that hold fi_add_rows_coo rows; batches with FI_GRADIENT_LINEAR_INTERPOLATION, whose rows
+ * live among the generic rows.  FI_ERR_STATE: no data points; no field given and no last solution.  Border-prior batches are
+ * re-emitted unchanged.  Residuals measure disagreement with the FIT: an outlier the field can bend to (an oriented point in
+ * empty space under a weak model) keeps a small residual and its weight -- the leverage-point limit, DESIGN.md 4.10. */
+#define FI_LOSS_HUBER 0
+#define FI_LOSS_CAUCHY 1
+#define FI_LOSS_TUKEY 2
+
+typedef struct fi_robust_options {
+	int   loss;             /* FI_LOSS_* */
+	float tuning;           /* c; 0: the loss's default */
+	float scale;            /* s; 0: 1.4826 x the median residual */
+	int   rounds;           /* fi_solve_robust: reweighted solves at most */
+	float weight_tolerance; /* fi_solve_robust: end when max_i |omega_new - omega_old| is below it; 0: never */
+} fi_robust_options;
+
+typedef struct fi_robust_stats {
+	int    rounds;            /* reweighted solves done (the first, plain solve is not counted) */
+	int    iterations;        /* CG iterations of all solves */
+	float  scale;             /* s of the last reweighting step */
+	float  max_weight_change; /* max_i |omega_new - omega_old| of the last reweighting step */
+	long   points_used;       /* M of the last reweighting step */
+	long   points_zeroed;     /* points with r >= 0 whose omega is 0 after it */
+	double reweight_ms;       /* host time of all reweighting steps (residuals, scale, weights, rows re-emitted) */
+} fi_robust_stats;
+
+/* the number of data points of the context */
+int fi_point_count(const fi_ctx* ctx, long* n);
+/* residuals: float[n].  field: the context's owned values (fp32), or NULL for its last solution where it lives (FI_F64: in
+ * full precision).  `memory` applies to field and residuals. */
+int fi_point_residuals(fi_ctx* ctx, const float* field, float* residuals, int memory);
+/* One step: residuals -> scale -> omega -> point weights; the rows are emitted again from the points, in the order of the
+ * first emission, so the context then holds the rows a fresh one holds that was given base * sqrt(omega) as point weights.
+ * Only loss, tuning and scale of the options are read.  omega: float[n] or NULL; scale: the s used, or NULL.  The context
+ * needs fi_assemble afterwards (not when the step reports scale 0). */
+int fi_robust_reweight(fi_ctx* ctx, const float* field, const fi_robust_options* options, float* omega, float* scale, int memory);
+/* back to the caller's weights (every omega 1); needs fi_assemble */
+int fi_reset_point_weights(fi_ctx* ctx);
+/* Assembles if needed; solves from `guess` (NULL: zeros, or the coarse-to-fine start where levels are set); then up to
+ * options->rounds times: reweights from the current field, assembles, solves from the current field.  Ends early at scale 0
+ * and, after the solve, when the step's max |omega_new - omega_old| < weight_tolerance.  Every solve is fi_solve_cg with
+ * max_iterations and tol, under whatever solver options the context carries (levels, V-cycle or K-cycle, mixed precision,
+ * field tolerance); the coarser levels and the fp32 replica pick the weights up through the re-assembly.  Afterwards the
+ * context holds the last weights: fi_error_map, fi_true_residual and a later fi_solve_cg see the robust system.
+ * out: the owned unknowns (fp32); omega: float[n] or NULL; stats may be NULL.  `memory` applies to guess, out and omega. */
+int fi_solve_robust(fi_ctx* ctx, const float* guess, const fi_robust_options* options, int max_iterations, float tol, float* out,
+                    float* omega, fi_robust_stats* stats, int memory);
+
 /* fp64 copy of the last solution (FI_F64 contexts keep full precision; FI_F32 widens). Host buffer. */
 int fi_get_solution_f64(fi_ctx* ctx, double* out);
 

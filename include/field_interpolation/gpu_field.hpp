@@ -15,6 +15,17 @@ struct fi_ctx;
 
 namespace field_interpolation {
 
+// Robust fits (include/fi_hip.h, "robust fits"): data points reweighted by their residuals between solves.
+struct RobustOptions
+{
+	enum class Loss { kHuber = 0, kCauchy = 1, kTukey = 2 };
+	Loss  loss             = Loss::kHuber;
+	float tuning           = 0; // the loss's constant c; 0: its default (1.345, 2.385, 4.685)
+	float scale            = 0; // the residual scale s; 0: 1.4826 x the median residual
+	int   rounds           = 5; // reweighted solves at most
+	float weight_tolerance = 0; // end when no weight factor moved by this much; 0: never
+};
+
 class GpuLatticeField
 {
 public:
@@ -93,6 +104,17 @@ public:
 	// max_distance.  The contract is include/fi_hip.h fi_redistance.  false: no solution yet, or the library refused the call.
 	bool redistance(std::vector<float>* out, float iso = 0, bool dual = false,
 	                float max_distance = std::numeric_limits<float>::infinity(), std::vector<long long>* primitives = nullptr) const;
+
+	// Iteratively reweighted least squares for data with gross errors: a plain solve, then up to options.rounds solves, each
+	// after the data points were reweighted by their residuals against the previous field (fi_solve_robust; every solve as
+	// solve() runs it).  point_weights (optional): the weight factor omega of every data point, in the order the points were
+	// added.  Afterwards the field holds the last weights.  An empty result means failure; last_iterations() counts all solves.
+	// Residuals measure disagreement with the fit: an outlier the field can bend to keeps its weight.
+	std::vector<float> solve_robust(const RobustOptions& options, int max_iterations, float error_tolerance,
+	                                std::vector<float>* point_weights = nullptr);
+	// Every data point's residual against the last solution: the root of the summed squares of its rows at unit point weight,
+	// -1 for a point that emits no row.  false: no solution yet, or the library refused the call.
+	bool point_residuals(std::vector<float>* residuals) const;
 
 	int    last_iterations() const { return iterations_; }
 	float  last_error() const { return error_; }
