@@ -166,6 +166,65 @@ def _nearest(call, ndim, queries, max_distance, indices):
     return (dist, idx) if indices else dist
 
 
+def _knn(call, ndim, queries, k, max_distance, indices):
+    """Shared body of the k-nearest-point queries: call(n, queries, k, max_distance, distances, indices, memory) is the C
+    entry point.  Outputs (n, k) live where `queries` lives, as in _nearest."""
+    q, qmem, qkeep = _buf(queries)
+    count = qkeep.numel() if hasattr(qkeep, "numel") else qkeep.size
+    if count % ndim:
+        raise ValueError("queries: %d values, not a multiple of ndim = %d (x fastest)" % (count, ndim))
+    n, k = count // ndim, int(k)
+    if not 1 <= k <= 32:
+        raise ValueError("k must be 1..32 (got %d)" % k)
+    if hasattr(qkeep, "data_ptr"):
+        import torch
+        dist = torch.empty((n, k), dtype=torch.float32, device=qkeep.device)
+        idx = torch.empty((n, k), dtype=torch.int64, device=qkeep.device) if indices else None
+        if n == 0:      # (an empty tensor has no storage to point at)
+            return (dist, idx) if indices else dist
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    else:
+        dist = np.empty((n, k), np.float32)
+        idx = np.empty((n, k), np.int64) if indices else None
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+    check(call(n, q, k, float(max_distance), ptr(dist), ptr(idx), qmem))
+    return (dist, idx) if indices else dist
+
+
+def _estimate_normals(call, ndim, n, k, max_distance, viewpoints, directions, variation, device):
+    """Shared body of the normal estimation: call(k, max_distance, orient, guides, num_guides, normals, variation, memory)
+    is the C entry point.  Outputs are numpy arrays, or torch tensors on the GPU when the guides are device tensors or with
+    device=True."""
+    if viewpoints is not None and directions is not None:
+        raise ValueError("viewpoints or directions, not both")
+    guides = viewpoints if viewpoints is not None else directions
+    orient = 0 if guides is None else (1 if viewpoints is not None else 2)
+    g, gmem, gkeep = _buf(guides)
+    ng = 0
+    if guides is not None:
+        count = gkeep.numel() if hasattr(gkeep, "numel") else gkeep.size
+        if count % ndim:
+            raise ValueError("guides: %d values, not a multiple of ndim = %d (x fastest)" % (count, ndim))
+        ng = count // ndim
+    on_device = device or gmem == FI_DEVICE
+    if on_device:
+        import torch
+        if guides is not None and gmem != FI_DEVICE:
+            gkeep = torch.as_tensor(gkeep).to("cuda")
+            g = C.c_void_p(gkeep.data_ptr())
+        dev = gkeep.device if guides is not None else "cuda"
+        nrm = torch.empty((n, ndim), dtype=torch.float32, device=dev)
+        var = torch.empty(n, dtype=torch.float32, device=dev) if variation else None
+        ptr = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())  # noqa: E731
+    else:
+        nrm = np.empty((n, ndim), np.float32)
+        var = np.empty(n, np.float32) if variation else None
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+    if n > 0 or not on_device:
+        check(call(int(k), float(max_distance), orient, g, ng, ptr(nrm), ptr(var), FI_DEVICE if on_device else FI_HOST))
+    return (nrm, var) if variation else nrm
+
+
 def _distance_field(call, total, indices, device):
     """Shared body of the distance fields: call(distances, indices, memory); numpy arrays of `total` values (x fastest), or
     torch tensors on the current GPU with device=True."""
@@ -212,6 +271,26 @@ class PointIndex:
         def call(n, q, md, d, i, mem):
             return _capi.lib().fi_points_nearest(self._h, n, q, md, d, i, mem)
         return _nearest(call, self.ndim, queries, max_distance, indices)
+
+    def knn(self, queries, k, max_distance=math.inf, indices=True):
+        """Distances (n, k) float32 and, with indices=True, indices (n, k) int64 of the k nearest points of the set to each
+        of `queries` (n x ndim), nearest first, equal distances by ascending index; 1 <= k <= 32.  Entries that do not exist
+        (fewer than k finite points, beyond max_distance) are +inf / -1 at the end; a non-finite query gets NaN / -1.  A
+        point of the set finds itself (include/fi_hip.h fi_knn)."""
+        def call(n, q, kk, md, d, i, mem):
+            return _capi.lib().fi_points_knn(self._h, n, q, kk, md, d, i, mem)
+        return _knn(call, self.ndim, queries, k, max_distance, indices)
+
+    def estimate_normals(self, k=16, max_distance=math.inf, viewpoints=None, directions=None, variation=False, device=False):
+        """Normals (num_points, ndim) float32 of the set's own points, each fitted to its k nearest points (itself included)
+        within max_distance by a local PCA in fp64 on the device; with variation=True also the surface variation
+        lambda_min / sum(lambda) (num_points,).  viewpoints: one sensor position (ndim,) or one per point -- normals look
+        at it (outward: the sign sdf_from_points wants); directions: rough normals, one per point, to agree with; neither:
+        each normal's largest component is positive, which is NOT a consistent orientation.  Points that are non-finite or
+        have fewer than ndim neighbours get a zero normal and a NaN variation (include/fi_hip.h fi_estimate_normals)."""
+        def call(kk, md, orient, g, ng, nrm, var, mem):
+            return _capi.lib().fi_points_estimate_normals(self._h, kk, md, orient, g, ng, nrm, var, mem)
+        return _estimate_normals(call, self.ndim, self.num_points, k, max_distance, viewpoints, directions, variation, device)
 
     def distance_field(self, sizes, max_distance=math.inf, indices=False, device=False):
         """PointIndex.nearest of every point of a lattice of `sizes` (x fastest), flat."""
@@ -629,6 +708,23 @@ class LatticeField:
             return _capi.lib().fi_nearest(self._h, n, q, md, d, i, mem)
         return _nearest(call, len(self.sizes), queries, max_distance, indices)
 
+    def knn(self, queries, k, max_distance=math.inf, indices=True):
+        """PointIndex.knn over the data points of this context (include/fi_hip.h fi_knn): the set and the search structure
+        are nearest()'s."""
+        def call(n, q, kk, md, d, i, mem):
+            return _capi.lib().fi_knn(self._h, n, q, kk, md, d, i, mem)
+        return _knn(call, len(self.sizes), queries, k, max_distance, indices)
+
+    def estimate_normals(self, k=16, max_distance=math.inf, viewpoints=None, directions=None, variation=False, device=False):
+        """PointIndex.estimate_normals of the data points of this context, in the order they were added
+        (include/fi_hip.h fi_estimate_normals)."""
+        n = C.c_long(0)
+        check(_capi.lib().fi_point_count(self._h, C.byref(n)))
+
+        def call(kk, md, orient, g, ng, nrm, var, mem):
+            return _capi.lib().fi_estimate_normals(self._h, kk, md, orient, g, ng, nrm, var, mem)
+        return _estimate_normals(call, len(self.sizes), n.value, k, max_distance, viewpoints, directions, variation, device)
+
     def distance_field(self, max_distance=math.inf, indices=False, device=False):
         """LatticeField.nearest of every lattice point (x fastest), flat: numpy arrays, or torch tensors with device=True."""
         def call(d, i, mem):
@@ -940,6 +1036,17 @@ def sdf_from_points(sizes, weights, positions, normals=None, point_weights=None,
     field.add_points(weights.data_pos, weights.value_kernel, weights.data_gradient, weights.gradient_kernel,
                      positions, normals, point_weights)
     return field
+
+
+def sdf_from_unoriented_points(sizes, weights, positions, k=16, viewpoints=None, directions=None, **kw):
+    """sdf_from_points for a cloud without normals: a PointIndex over `positions`, its estimate_normals(k, viewpoints,
+    directions), then sdf_from_points(sizes, weights, positions, normals, **kw).  Without viewpoints or directions the
+    normals carry no consistent orientation, and neither does the field's sign."""
+    if positions is None:
+        raise ValueError("positions is null")
+    normals = PointIndex(positions, ndim=len(sizes)).estimate_normals(k=k, viewpoints=viewpoints, directions=directions,
+                                                                      device=hasattr(positions, "is_cuda") and positions.is_cuda)
+    return sdf_from_points(sizes, weights, positions, normals, **kw)
 
 
 def solve_sparse_linear_with_guess(field, guess, max_iterations=0, error_tolerance=0.0):

@@ -6,6 +6,7 @@
 #include "fi_dual.h"
 #include "fi_sample.h"
 #include "fi_nearest.h"
+#include "fi_knn.h"
 #include "fi_surface.h"
 #include "fi_robust.h"
 
@@ -1369,6 +1370,80 @@ int fi_points_distance_field(fi_points* h, const int* sizes, float max_distance,
 }
 
 int fi_points_destroy(fi_points* h) { return fi::destroy_handle(h); }
+
+
+// ---- k nearest data points; normals from them (fi_knn.hip) --------------------------------------
+namespace {
+void check_k(int k)
+{
+	FI_REQUIRE(1 <= k && k <= fi::kMaxNeighbours, FI_ERR_INVALID, "k must be 1..%d (got %d)", fi::kMaxNeighbours, k);
+}
+
+void check_normals(const fi::NearestIndex* t, int ndim, int k, float max_distance, int orient, const float* guides, long num_guides,
+                   const float* normals, int memory)
+{
+	FI_REQUIRE(ndim >= 2, FI_ERR_INVALID, "normals need 2 or 3 dimensions (got %d)", ndim);
+	check_k(k);
+	FI_REQUIRE(k >= ndim, FI_ERR_INVALID, "k = %d neighbours span no plane in %d dimensions", k, ndim);
+	FI_REQUIRE(normals != nullptr, FI_ERR_INVALID, "normals is null");
+	FI_REQUIRE(max_distance >= 0.0f, FI_ERR_INVALID, "max_distance must be >= 0 (got %g)", static_cast<double>(max_distance));
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	FI_REQUIRE(orient == FI_ORIENT_NONE || orient == FI_ORIENT_VIEWPOINTS || orient == FI_ORIENT_DIRECTIONS, FI_ERR_INVALID,
+	           "bad orientation mode %d", orient);
+	if (orient == FI_ORIENT_NONE || !t) { return; }
+	FI_REQUIRE(guides != nullptr, FI_ERR_INVALID, "orientation mode %d without guides", orient);
+	FI_REQUIRE(num_guides == t->n || (orient == FI_ORIENT_VIEWPOINTS && num_guides == 1), FI_ERR_INVALID,
+	           "%ld guides for %lld points", num_guides, static_cast<long long>(t->n));
+}
+}  // namespace
+
+int fi_knn(fi_ctx* c, long n, const float* queries, int k, float max_distance, float* distances, long long* indices, int memory)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	check_nearest(n, queries, max_distance, distances, memory);
+	check_k(k);
+	check_undivided(c);
+	if (n == 0) { return FI_OK; }
+	fi::knn_query(fi::nearest_of(c), n, queries, k, max_distance, distances, indices, memory, c->stream);
+	FI_API_END
+}
+
+int fi_points_knn(fi_points* h, long n, const float* queries, int k, float max_distance, float* distances, long long* indices,
+                  int memory)
+{
+	FI_API_BEGIN
+	check_points(h);
+	check_nearest(n, queries, max_distance, distances, memory);
+	check_k(k);
+	fi::knn_query(h->t, n, queries, k, max_distance, distances, indices, memory, nullptr);
+	FI_API_END
+}
+
+int fi_estimate_normals(fi_ctx* c, int k, float max_distance, int orient, const float* guides, long num_guides, float* normals,
+                        float* variation, int memory)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	check_normals(nullptr, c->g.ndim, k, max_distance, orient, guides, num_guides, normals, memory);
+	check_undivided(c);
+	const fi::NearestIndex& t = fi::nearest_of(c);
+	check_normals(&t, c->g.ndim, k, max_distance, orient, guides, num_guides, normals, memory);
+	fi::estimate_normals(t, k, max_distance, orient, guides, num_guides, normals, variation, memory, c->stream);
+	FI_API_END
+}
+
+int fi_points_estimate_normals(fi_points* h, int k, float max_distance, int orient, const float* guides, long num_guides,
+                               float* normals, float* variation, int memory)
+{
+	FI_API_BEGIN
+	check_points(h);
+	check_normals(&h->t, h->t.D, k, max_distance, orient, guides, num_guides, normals, memory);
+	fi::estimate_normals(h->t, k, max_distance, orient, guides, num_guides, normals, variation, memory, nullptr);
+	FI_API_END
+}
 
 
 // ---- distances to a surface; redistancing (fi_surface.hip) -------------------------------------

@@ -1,0 +1,422 @@
+// fi_knn.hip -- exact k nearest data points, and point-cloud normals from them, on the device.
+//
+// The contract (include/fi_hip.h fi_knn / fi_estimate_normals): s(p, q) is fi_nearest's; a query's result is
+// the first k of the pairs (s, j) over the finite points in lexicographic order, those beyond max_distance dropped.  A normal
+// is the direction of least spread of a point's own k nearest points (itself included): fp64, one rounding per operation
+// (-ffp-contract=off), a cyclic Jacobi iteration of a fixed number of sweeps -- the arithmetic of tests/normals_reference.py,
+// bit for bit.
+//
+// Search: fi_bvh.h's stackless walk over fi_nearest.h's tree, unchanged.  The visitor keeps the k best pairs sorted in
+// registers and reports the k-th s as the walk's pruning bound; the walk prunes on lb > bound (strict), so a leaf that holds
+// an equal s with a smaller index is still visited.  The list has a capacity fixed at compile time (8, 16 or 32) and every
+// access names its entry at compile time: an index known at run time would put it in scratch.  A k below the capacity
+// blocks the front of the list with entries that sort before every real pair, so the k-th best is always the LAST entry.
+#include "fi_solver_internal.h"
+#include "fi_knn.h"
+#include "fi_bvh.h"
+
+namespace fi {
+
+namespace {
+
+using namespace bvh;
+
+constexpr int kSweeps = 6;
+
+__device__ inline bool pair_less(float s, uint32_t j, float s1, uint32_t j1) { return s < s1 || (s == s1 && j < j1); }
+
+// The k best pairs (s, j) in ascending order as entries [CAP - k, CAP) of a list of CAP entries, each with its sorted slot of
+// the tree (`at`: dead code where nobody reads it).  The list is a chain of structs walked by template recursion, entry
+// N - 1 last: every access names its entry at compile time, so the whole list lives in registers.
+template <int N>
+struct List {
+	List<N - 1> lo;  // the entries before this one
+	float       s;
+	uint32_t    j, at;
+};
+template <>
+struct List<0> {};
+
+// entries [first_open, CAP) empty (+inf, no index); those in front blocked: (-1, 0) sorts before every pair, so a blocked
+// entry is never displaced and never shifted
+template <int N>
+__device__ __forceinline__ void list_reset(List<N>& l, int first_open)
+{
+	if constexpr (N > 0) {
+		const bool open = N - 1 >= first_open;
+		l.s  = open ? INFINITY : -1.0f;
+		l.j  = open ? kNone : 0u;
+		l.at = 0u;
+		list_reset<N - 1>(l.lo, first_open);
+	}
+}
+
+// the pair sorts before entry N - 1: that entry's predecessor moves up into it while the pair sorts before that one as
+// well, else the pair lands here (the old entry N - 1 has gone to N, or is dropped at the end of the list)
+template <int N>
+__device__ __forceinline__ void list_put(List<N>& l, float ns, uint32_t nj, uint32_t slot)
+{
+	if constexpr (N == 1) {
+		l.s  = ns;
+		l.j  = nj;
+		l.at = slot;
+	} else {
+		const bool up = pair_less(ns, nj, l.lo.s, l.lo.j);
+		l.s  = up ? l.lo.s : ns;
+		l.j  = up ? l.lo.j : nj;
+		l.at = up ? l.lo.at : slot;
+		if (up) { list_put<N - 1>(l.lo, ns, nj, slot); }
+	}
+}
+
+// accept a pair only if it sorts before the k-th
+template <int N>
+__device__ __forceinline__ void list_offer(List<N>& l, float ns, uint32_t nj, uint32_t slot)
+{
+	if (pair_less(ns, nj, l.s, l.j)) { list_put<N>(l, ns, nj, slot); }
+}
+
+// f(r, s, j, at) for every entry in ascending order
+template <int N, class F>
+__device__ __forceinline__ void list_each(const List<N>& l, F&& f)
+{
+	if constexpr (N > 0) {
+		list_each<N - 1>(l.lo, f);
+		f(N - 1, l.s, l.j, l.at);
+	}
+}
+
+// a pair found (as opposed to a blocked or an empty entry) within lim
+__device__ inline bool found(float s, uint32_t j, float lim) { return s >= 0.0f && j != kNone && !(s > lim); }
+
+struct KnnArgs {
+	Tree         t;
+	int64_t      n;
+	const float* q;     // float[n][D]
+	int          k;
+	float        lim;   // the largest float whose sqrtf is <= max_distance
+	float*       dist;  // float[n][k]
+	long long*   idx;   // long long[n][k], or nullptr
+};
+
+// (the walk is latency-bound: the classes up to 16 stay within 64 VGPRs, 8 waves per SIMD, like fi_nearest's queries --
+// tests/test_knn_resources.py)
+template <int D, int CAP>
+__global__ __launch_bounds__(kThreads) void k_knn_query(KnnArgs a)
+{
+	const int64_t out = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+	if (out >= a.n) { return; }
+	float q[D];
+#pragma unroll
+	for (int d = 0; d < D; ++d) { q[d] = a.q[out * D + d]; }
+	const bool finite = finite_point<D>(q);
+	List<CAP>  b;
+	list_reset<CAP>(b, CAP - a.k);
+	if (finite) {
+		float bound;
+		search<D, kNearestLeaf>(a.t, q, a.lim, bound, [&](int64_t i, float& least) {
+			const float4 p = a.t.items[i];
+			list_offer<CAP>(b, sq_dist<D>(p, q), __float_as_uint(p.w), 0u);
+			least = b.s;  // the k-th s: +inf until k pairs are held
+		});
+	}
+	list_each<CAP>(b, [&](int r, float s, uint32_t j, uint32_t) {
+		const int o = r - (CAP - a.k);
+		if (o < 0) { return; }
+		const bool ok = finite && found(s, j, a.lim);
+		// (a finite point whose s overflows is still a neighbour: +inf with its index, as in fi_nearest)
+		a.dist[out * a.k + o] = !finite ? NAN : (ok ? sqrtf(s) : INFINITY);
+		if (a.idx) { a.idx[out * a.k + o] = ok ? static_cast<long long>(j) : -1LL; }
+	});
+}
+
+// ---- normals ----------------------------------------------------------------------------------------------------------
+
+// one Jacobi rotation of the pair (P, Q) of the symmetric matrix A (both triangles kept) and the vector matrix V (columns)
+template <int D, int P, int Q>
+__device__ inline void rotate(double (&A)[D][D], double (&V)[D][D])
+{
+	const double apq = A[P][Q];
+	if (apq == 0.0) { return; }
+	const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
+	const double t     = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+	const double c     = 1.0 / sqrt(t * t + 1.0);
+	const double s     = t * c;
+	const double tap   = t * apq;
+	A[P][P] = A[P][P] - tap;
+	A[Q][Q] = A[Q][Q] + tap;
+	A[P][Q] = A[Q][P] = 0.0;
+#pragma unroll
+	for (int r = 0; r < D; ++r) {
+		if (r == P || r == Q) { continue; }
+		const double arp = A[r][P], arq = A[r][Q];
+		A[r][P] = A[P][r] = c * arp - s * arq;
+		A[r][Q] = A[Q][r] = s * arp + c * arq;
+	}
+#pragma unroll
+	for (int r = 0; r < D; ++r) {
+		const double vrp = V[r][P], vrq = V[r][Q];
+		V[r][P] = c * vrp - s * vrq;
+		V[r][Q] = s * vrp + c * vrq;
+	}
+}
+
+enum { kOrientNone = 0, kOrientViewpoints = 1, kOrientDirections = 2 };
+
+struct NormalArgs {
+	Tree         t;
+	int          k;
+	float        lim;
+	int          orient;
+	const float* guides;      // float[num_guides][D], or nullptr
+	int64_t      num_guides;
+	float*       normals;     // float[n][D]
+	float*       variation;   // float[n], or nullptr
+};
+
+// Thread i takes the point of sorted slot i (a wave's points are Morton neighbours and walk the same nodes), searches its
+// neighbours, and fits their plane; the result goes to the point's own index.
+template <int D, int CAP>
+__global__ __launch_bounds__(kThreads) void k_knn_normals(NormalArgs a)
+{
+	const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+	if (i >= a.t.nf) { return; }
+	const float4  self = a.t.items[i];
+	const float   s3[3] = {self.x, self.y, self.z};
+	const int64_t me    = __float_as_uint(self.w);
+	float         q[D];
+#pragma unroll
+	for (int d = 0; d < D; ++d) { q[d] = s3[d]; }
+	List<CAP> b;
+	list_reset<CAP>(b, CAP - a.k);
+	float bound;
+	search<D, kNearestLeaf>(a.t, q, a.lim, bound, [&](int64_t at, float& least) {
+		const float4 p = a.t.items[at];
+		list_offer<CAP>(b, sq_dist<D>(p, q), __float_as_uint(p.w), static_cast<uint32_t>(at));
+		least = b.s;
+	});
+
+	// the centroid: the neighbours' sum from 0.0 in result order, divided by their number
+	int    m = 0;
+	double c[D];
+#pragma unroll
+	for (int d = 0; d < D; ++d) { c[d] = 0.0; }
+	list_each<CAP>(b, [&](int, float s, uint32_t j, uint32_t at) {
+		if (!found(s, j, a.lim)) { return; }
+		const float4 p = a.t.items[at];
+		const float  v[3] = {p.x, p.y, p.z};
+#pragma unroll
+		for (int d = 0; d < D; ++d) { c[d] = c[d] + static_cast<double>(v[d]); }
+		++m;
+	});
+	if (m < D) {  // no plane: a zero normal (the blank fill has written it for the points outside the tree)
+#pragma unroll
+		for (int d = 0; d < D; ++d) { a.normals[me * D + d] = 0.0f; }
+		if (a.variation) { a.variation[me] = NAN; }
+		return;
+	}
+#pragma unroll
+	for (int d = 0; d < D; ++d) { c[d] = c[d] / static_cast<double>(m); }
+
+	// the covariance sums, from 0.0 in result order
+	double A[D][D], V[D][D];
+#pragma unroll
+	for (int x = 0; x < D; ++x) {
+#pragma unroll
+		for (int y = 0; y < D; ++y) {
+			A[x][y] = 0.0;
+			V[x][y] = x == y ? 1.0 : 0.0;
+		}
+	}
+	list_each<CAP>(b, [&](int, float s, uint32_t j, uint32_t at) {
+		if (!found(s, j, a.lim)) { return; }
+		const float4 p = a.t.items[at];
+		const float  v[3] = {p.x, p.y, p.z};
+		double       e[D];
+#pragma unroll
+		for (int d = 0; d < D; ++d) { e[d] = static_cast<double>(v[d]) - c[d]; }
+#pragma unroll
+		for (int x = 0; x < D; ++x) {
+#pragma unroll
+			for (int y = x; y < D; ++y) { A[x][y] = A[x][y] + e[x] * e[y]; }
+		}
+	});
+#pragma unroll
+	for (int x = 0; x < D; ++x) {
+#pragma unroll
+		for (int y = 0; y < x; ++y) { A[x][y] = A[y][x]; }
+	}
+
+	// a fixed number of sweeps, no early exit: the result is defined by the count alone
+#pragma unroll 1
+	for (int sweep = 0; sweep < kSweeps; ++sweep) {
+		rotate<D, 0, 1>(A, V);
+		if constexpr (D == 3) {
+			rotate<D, 0, 2>(A, V);
+			rotate<D, 1, 2>(A, V);
+		}
+	}
+
+	// the column of the smallest diagonal entry (the lowest on a tie) ...
+	int    col  = 0;
+	double lmin = A[0][0];
+#pragma unroll
+	for (int d = 1; d < D; ++d) {
+		if (A[d][d] < lmin) {
+			lmin = A[d][d];
+			col  = d;
+		}
+	}
+	double nrm[D];
+#pragma unroll
+	for (int d = 0; d < D; ++d) {
+		nrm[d] = V[d][0];
+#pragma unroll
+		for (int x = 1; x < D; ++x) { nrm[d] = col == x ? V[d][x] : nrm[d]; }
+	}
+	// ... its component of largest magnitude (the first such axis) made positive
+	double big = nrm[0];
+#pragma unroll
+	for (int d = 1; d < D; ++d) { big = fabs(nrm[d]) > fabs(big) ? nrm[d] : big; }
+	bool flip = big < 0.0;
+	if (a.orient != kOrientNone) {
+		double w = 0.0;
+#pragma unroll
+		for (int d = 0; d < D; ++d) {
+			double g;
+			if (a.orient == kOrientViewpoints) {
+				g = static_cast<double>(a.guides[(a.num_guides == 1 ? 0 : me) * D + d]) - static_cast<double>(q[d]);
+			} else {
+				g = static_cast<double>(a.guides[me * D + d]);
+			}
+			w = w + (flip ? -nrm[d] : nrm[d]) * g;
+		}
+		if (isfinite(w) && w < 0.0) { flip = !flip; }
+	}
+#pragma unroll
+	for (int d = 0; d < D; ++d) { a.normals[me * D + d] = static_cast<float>(flip ? -nrm[d] : nrm[d]); }
+	if (a.variation) {
+		double tot = 0.0;
+#pragma unroll
+		for (int d = 0; d < D; ++d) { tot = tot + A[d][d]; }
+		a.variation[me] = static_cast<float>(tot == 0.0 ? 0.0 : lmin / tot);
+	}
+}
+
+// what a point outside the tree (a non-finite one) gets
+__global__ __launch_bounds__(kThreads) void k_knn_blank(int64_t n, int D, float* __restrict__ normals, float* __restrict__ variation)
+{
+	const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+	if (i >= n) { return; }
+	for (int d = 0; d < D; ++d) { normals[i * D + d] = 0.0f; }
+	if (variation) { variation[i] = NAN; }
+}
+
+int capacity_for(int k) { return k <= 8 ? 8 : k <= 16 ? 16 : 32; }
+
+template <int D>
+void launch_query(int cap, dim3 grid, const KnnArgs& a, hipStream_t st)
+{
+	switch (cap) {
+	case 8: hipLaunchKernelGGL((k_knn_query<D, 8>), grid, dim3(kThreads), 0, st, a); break;
+	case 16: hipLaunchKernelGGL((k_knn_query<D, 16>), grid, dim3(kThreads), 0, st, a); break;
+	default: hipLaunchKernelGGL((k_knn_query<D, 32>), grid, dim3(kThreads), 0, st, a); break;
+	}
+}
+
+template <int D>
+void launch_normals(int cap, dim3 grid, const NormalArgs& a, hipStream_t st)
+{
+	switch (cap) {
+	case 8: hipLaunchKernelGGL((k_knn_normals<D, 8>), grid, dim3(kThreads), 0, st, a); break;
+	case 16: hipLaunchKernelGGL((k_knn_normals<D, 16>), grid, dim3(kThreads), 0, st, a); break;
+	default: hipLaunchKernelGGL((k_knn_normals<D, 32>), grid, dim3(kThreads), 0, st, a); break;
+	}
+}
+
+// a caller's output of `count` elements on the device: the buffer itself (FI_DEVICE) or a staged one, copied back by back()
+template <typename T>
+struct Staged {
+	T*     host;
+	T*     dev;
+	size_t bytes;
+	int    memory;
+	DevBuf buf;
+	Staged(T* out, int64_t count, int mem) : host(out), dev(out), bytes(sizeof(T) * count), memory(mem)
+	{
+		if (out && memory == FI_HOST) {
+			buf.alloc(bytes);
+			dev = buf.as<T>();
+		}
+	}
+	void back(hipStream_t st)
+	{
+		if (host && memory == FI_HOST) { FI_HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st)); }
+	}
+};
+
+}  // namespace
+
+void knn_query(const NearestIndex& t, int64_t n, const float* queries, int k, float max_distance, float* distances, long long* indices,
+               int memory, hipStream_t st)
+{
+	if (n == 0) { return; }
+	AllocStream       alloc_on(st);
+	Staged<float>     d(distances, n * k, memory);
+	Staged<long long> ix(indices, n * k, memory);
+	DevBuf            bq;
+	KnnArgs           a{};
+	a.t    = tree_of(t);
+	a.n    = n;
+	a.q    = stage_queries(queries, n, t.D, memory, bq, st);
+	a.k    = k;
+	a.lim  = limit_for(max_distance);
+	a.dist = d.dev;
+	a.idx  = ix.dev;
+	const dim3 grid(blocks_for(n));
+	switch (t.D) {
+	case 1: launch_query<1>(capacity_for(k), grid, a, st); break;
+	case 2: launch_query<2>(capacity_for(k), grid, a, st); break;
+	default: launch_query<3>(capacity_for(k), grid, a, st); break;
+	}
+	FI_HIP_TRY(hipGetLastError());
+	d.back(st);
+	ix.back(st);
+	FI_HIP_TRY(hipStreamSynchronize(st));
+}
+
+void estimate_normals(const NearestIndex& t, int k, float max_distance, int orient, const float* guides, int64_t num_guides,
+                      float* normals, float* variation, int memory, hipStream_t st)
+{
+	if (t.n == 0) { return; }
+	AllocStream   alloc_on(st);
+	Staged<float> nr(normals, t.n * t.D, memory);
+	Staged<float> va(variation, t.n, memory);
+	DevBuf        bg;
+	NormalArgs    a{};
+	a.t          = tree_of(t);
+	a.k          = k;
+	a.lim        = limit_for(max_distance);
+	a.orient     = orient;
+	a.guides     = orient == kOrientNone ? nullptr : stage_queries(guides, num_guides, t.D, memory, bg, st);
+	a.num_guides = num_guides;
+	a.normals    = nr.dev;
+	a.variation  = va.dev;
+	if (t.nf < t.n) {
+		hipLaunchKernelGGL(k_knn_blank, dim3(blocks_for(t.n)), dim3(kThreads), 0, st, t.n, t.D, a.normals, a.variation);
+	}
+	if (t.nf > 0) {
+		const dim3 grid(blocks_for(t.nf));
+		if (t.D == 2) {
+			launch_normals<2>(capacity_for(k), grid, a, st);
+		} else {
+			launch_normals<3>(capacity_for(k), grid, a, st);
+		}
+	}
+	FI_HIP_TRY(hipGetLastError());
+	nr.back(st);
+	va.back(st);
+	FI_HIP_TRY(hipStreamSynchronize(st));
+}
+
+}  // namespace fi

@@ -13,6 +13,23 @@ struct NearestIndex : BvhIndex {
 	int64_t n = 0;   // points of the set (finite or not)
 };
 
+// what the units that walk this tree share (fi_nearest.hip, fi_knn.hip): the points of a leaf ...
+constexpr int kNearestLeaf = 16;
+
+// ... and s(p, q) of the contract for a stored point p and a query q
+template <int D>
+__device__ inline float sq_dist(const float4& p, const float* q)
+{
+	const float c[3] = {p.x, p.y, p.z};
+	float       s    = 0.0f;
+#pragma unroll
+	for (int d = 0; d < D; ++d) {
+		const float e = c[d] - q[d];
+		s = s + e * e;
+	}
+	return s;
+}
+
 // the set of a context: its fi_add_points batches in call order, the border prior's left out (PointBatch::prior); built on
 // the context's stream, kept in c->nearest until the next fi_add_points / fi_clear_points
 const NearestIndex& nearest_of(fi_ctx* c);

@@ -16,8 +16,6 @@ namespace {
 
 using namespace bvh;
 
-constexpr int kNearestLeaf = 16;
-
 // the items of the build (fi_bvh.h): n points of D floats; usable means finite; stored as float4 (x, y, z, the index as bits)
 template <int D>
 struct PointItems {
@@ -53,19 +51,6 @@ struct PointItems {
 		FI_REQUIRE(c[0] <= static_cast<uint64_t>(n), FI_ERR_HIP, "nearest: %u finite points of %lld", c[0], static_cast<long long>(n));
 	}
 };
-
-template <int D>
-__device__ inline float sq_dist(const float4& p, const float* q)
-{
-	const float c[3] = {p.x, p.y, p.z};
-	float       s    = 0.0f;
-#pragma unroll
-	for (int d = 0; d < D; ++d) {
-		const float e = c[d] - q[d];
-		s = s + e * e;
-	}
-	return s;
-}
 
 // where the queries come from
 enum { kFromBuffer = 0, kFromLattice = 1, kFromList = 2 };

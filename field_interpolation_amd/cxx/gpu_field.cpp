@@ -357,6 +357,49 @@ bool GpuLatticeField::nearest(const std::vector<float>& queries, std::vector<flo
 	return true;
 }
 
+bool GpuLatticeField::knn(const std::vector<float>& queries, int k, std::vector<float>* distances, std::vector<long long>* indices,
+                          float max_distance) const
+{
+	const size_t D = sizes_.size();
+	if (!distances || queries.size() % D != 0 || k < 1 || k > 32) {
+		warn("knn");
+		return false;
+	}
+	const size_t n = queries.size() / D;
+	distances->resize(n * k);
+	if (indices) { indices->resize(n * k); }
+	if (n == 0) { return true; }
+	if (fi_knn(ctx_, static_cast<long>(n), queries.data(), k, max_distance, distances->data(), indices ? indices->data() : nullptr,
+	           FI_HOST) != FI_OK) {
+		warn("knn");
+		return false;
+	}
+	return true;
+}
+
+bool GpuLatticeField::estimate_normals(std::vector<float>* normals, int k, const std::vector<float>& viewpoints,
+                                       std::vector<float>* variation, float max_distance) const
+{
+	const size_t D = sizes_.size();
+	long         n = 0;
+	if (!normals || viewpoints.size() % D != 0 || fi_point_count(ctx_, &n) != FI_OK) {
+		warn("estimate_normals");
+		return false;
+	}
+	normals->resize(D * n);
+	if (variation) { variation->resize(n); }
+	// (data() of an empty vector may be null: the library would refuse it; its other checks still run on a dummy)
+	float      none[3] = {0.0f, 0.0f, 0.0f};
+	const bool guided  = !viewpoints.empty();
+	if (fi_estimate_normals(ctx_, k, max_distance, guided ? FI_ORIENT_VIEWPOINTS : FI_ORIENT_NONE, guided ? viewpoints.data() : nullptr,
+	                        static_cast<long>(viewpoints.size() / D), n ? normals->data() : none, variation && n ? variation->data() : nullptr,
+	                        FI_HOST) != FI_OK) {
+		warn("estimate_normals");
+		return false;
+	}
+	return true;
+}
+
 bool GpuLatticeField::distance_field(std::vector<float>* distances, std::vector<long long>* indices, float max_distance) const
 {
 	if (!distances) {

@@ -602,6 +602,53 @@ int fi_points_nearest(fi_points* points, long n, const float* queries, float max
 int fi_points_distance_field(fi_points* points, const int* sizes, float max_distance, float* out, long long* indices, int memory);
 int fi_points_destroy(fi_points* points);
 
+/* ---- k nearest data points ----------------------------------------------------------------------
+ * The contract.  The point set, s(p, q), finiteness and max_distance are fi_nearest's, and so is the search
+ * structure (built once, shared with fi_nearest):
+ *   - a finite query q and 1 <= k <= 32: the pairs (s(p_j, q), j) over the finite points in lexicographic order (s first,
+ *     then the index); the result is the first k of them with sqrtf(s) <= max_distance, in that order;
+ *   - distances[i * k + r] = sqrtf(s_r), indices[i * k + r] = j_r; entries that do not exist (fewer than k finite points,
+ *     neighbours beyond max_distance) are +inf / -1 and stand at the end;
+ *   - a query with a non-finite coordinate: every distance NaN, every index -1;
+ *   - a data point queried against its own set finds itself at distance 0 (or a duplicate with a smaller index first): it is
+ *     not removed;
+ *   - results depend neither on the launch shape nor on timing; for k = 1 they equal fi_nearest's bit for bit.
+ * distances float[n * k], indices long long[n * k] or NULL.  The errors of fi_nearest; k outside 1..32: FI_ERR_INVALID. */
+int fi_knn(fi_ctx* ctx, long n, const float* queries, int k, float max_distance, float* distances, long long* indices, int memory);
+int fi_points_knn(fi_points* points, long n, const float* queries, int k, float max_distance, float* distances, long long* indices,
+                  int memory);
+
+/* ---- normals of a point cloud -------------------------------------------------------------------
+ * The contract (tests/normals_reference.py is its definition in numpy).  For every point i of the set (a
+ * context's points in the order they were added, or a fi_points), in ndim = 2 or 3 dimensions:
+ *   1. its neighbours are its own fi_knn result (k, max_distance), itself included: m valid entries in result order.  A
+ *      non-finite point, or m < ndim: the normal is all zeros and the variation NaN;
+ *   2. everything else is fp64, one rounding per operation, only + - * / sqrt.  The centroid c: the neighbours' coordinates
+ *      (widened from fp32) summed from 0.0 in neighbour order, divided by m.  The covariance sums: a_xy = the sum from 0.0 in
+ *      neighbour order of (p_x - c_x)(p_y - c_y), not divided by m;
+ *   3. six sweeps of a cyclic Jacobi iteration over the pairs (0,1), (0,2), (1,2) (2-D: the one pair), never fewer.  A pair
+ *      with a_pq == 0 is skipped; else theta = (a_qq - a_pp) / (2 a_pq), t = sign(theta) / (|theta| + sqrt(theta theta + 1))
+ *      with sign(0) = +1, c = 1 / sqrt(t t + 1), s = t c;  a_pp -= t a_pq, a_qq += t a_pq, a_pq = 0;  the third axis r:
+ *      (a_rp, a_rq) <- (c a_rp - s a_rq, s a_rp + c a_rq);  every row r of the vector matrix V (the identity at first):
+ *      (v_rp, v_rq) <- (c v_rp - s v_rq, s v_rp + c v_rq);
+ *   4. the normal is the column of V whose diagonal entry of A is smallest (the lowest column on a tie), its component of
+ *      largest magnitude (the first such axis) made positive: the canonical sign.  variation = that diagonal entry / (the
+ *      diagonal summed from 0.0 in axis order), 0 where that sum is 0: 0 on a plane, 1 / ndim for an isotropic neighbourhood;
+ *   5. orient = FI_ORIENT_NONE: the canonical sign -- NOT a consistent orientation of the cloud.  FI_ORIENT_VIEWPOINTS:
+ *      guides = num_guides viewpoints (1: one sensor position; or one per point); w = the sum from 0.0 in ascending axes of
+ *      n_a (v_a - p_a), and the normal is negated where w < 0: normals look at the sensor, which is outward, the sign
+ *      fi_add_points expects.  FI_ORIENT_DIRECTIONS: the same with guides[i] in place of v - p (rough normals from
+ *      elsewhere), one per point.  w == 0 or non-finite: the canonical sign stays;
+ *   6. normals float[n * ndim]: the fp64 components rounded to fp32, not renormalised; variation float[n] or NULL.
+ * ndim = 1, k outside 1..32, k < ndim, NULL normals, a NaN or negative max_distance, a bad memory kind or orient, orient != 0
+ * with NULL guides or a wrong num_guides: FI_ERR_INVALID.  A slab context: FI_ERR_UNSUPPORTED, as for fi_nearest.  `memory`
+ * applies to every buffer of the call. */
+enum { FI_ORIENT_NONE = 0, FI_ORIENT_VIEWPOINTS = 1, FI_ORIENT_DIRECTIONS = 2 };
+int fi_estimate_normals(fi_ctx* ctx, int k, float max_distance, int orient, const float* guides, long num_guides, float* normals,
+                        float* variation, int memory);
+int fi_points_estimate_normals(fi_points* points, int k, float max_distance, int orient, const float* guides, long num_guides,
+                               float* normals, float* variation, int memory);
+
 /* ---- exact distances to a surface; redistancing ------------------------------------------------
  * The contract ("Distances to a surface") is this project's own.  All arithmetic is fp32, one rounding per
  * operation (no FMA contraction):

@@ -95,6 +95,18 @@ public:
 	// The contract is include/fi_hip.h fi_nearest.  false: the library refused the call.
 	bool nearest(const std::vector<float>& queries, std::vector<float>* distances, std::vector<long long>* indices = nullptr,
 	             float max_distance = std::numeric_limits<float>::infinity()) const;
+	// The k nearest data points of each query, nearest first, equal distances by ascending index (1 <= k <= 32): k distances
+	// (and indices) per query; entries that do not exist are +inf / -1 at the end.  The contract is include/fi_hip.h fi_knn.
+	bool knn(const std::vector<float>& queries, int k, std::vector<float>* distances, std::vector<long long>* indices = nullptr,
+	         float max_distance = std::numeric_limits<float>::infinity()) const;
+	// Normals (ndim floats per point) of the data points given to add_points so far, in that order, each fitted to its k
+	// nearest points (itself included) on the device.  viewpoints: ndim floats (one sensor position) or ndim per point --
+	// normals look at it, which is outward; empty: each normal's largest component is positive, NOT a consistent
+	// orientation.  variation (optional): lambda_min / sum(lambda) per point.  The contract is include/fi_hip.h
+	// fi_estimate_normals.  false: the library refused the call.
+	bool estimate_normals(std::vector<float>* normals, int k = 16, const std::vector<float>& viewpoints = std::vector<float>(),
+	                      std::vector<float>* variation = nullptr,
+	                      float max_distance = std::numeric_limits<float>::infinity()) const;
 	// nearest() of every lattice point (x fastest): num_unknowns() distances (and indices)
 	bool distance_field(std::vector<float>* distances, std::vector<long long>* indices = nullptr,
 	                    float max_distance = std::numeric_limits<float>::infinity()) const;
