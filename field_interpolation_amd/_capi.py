@@ -26,6 +26,7 @@ SYMBOLS = [
     "fi_group_sample", "fi_sample", "fi_sample_field",
     "fi_nearest", "fi_distance_field", "fi_points_create", "fi_points_nearest", "fi_points_distance_field", "fi_points_destroy",
     "fi_knn", "fi_points_knn", "fi_estimate_normals", "fi_points_estimate_normals",
+    "fi_orient_normals", "fi_points_orient_normals",
     "fi_surface_create", "fi_surface_from_mesh", "fi_surface_distance", "fi_surface_distance_field", "fi_surface_destroy",
     "fi_redistance", "fi_redistance_field",
     "fi_point_count", "fi_point_residuals", "fi_robust_reweight", "fi_reset_point_weights", "fi_solve_robust",
@@ -157,6 +158,8 @@ def lib():
     L.fi_points_knn.argtypes = [vp, C.c_long, fp, C.c_int, C.c_float, fp, vp, C.c_int]
     L.fi_estimate_normals.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, C.c_long, fp, fp, C.c_int]
     L.fi_points_estimate_normals.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, C.c_long, fp, fp, C.c_int]
+    L.fi_orient_normals.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, C.c_long, fp, vp, C.c_int]
+    L.fi_points_orient_normals.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, C.c_long, fp, vp, C.c_int]
     L.fi_surface_create.argtypes = [C.POINTER(vp), C.c_int, C.c_long, fp, C.c_long, vp, C.c_int]
     L.fi_surface_from_mesh.argtypes = [C.POINTER(vp), vp]
     L.fi_surface_distance.argtypes = [vp, C.c_long, fp, C.c_float, fp, vp, fp, C.c_int]

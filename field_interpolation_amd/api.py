@@ -225,6 +225,57 @@ def _estimate_normals(call, ndim, n, k, max_distance, viewpoints, directions, va
     return (nrm, var) if variation else nrm
 
 
+def _orient_normals(call, ndim, n, normals, k, max_distance, viewpoints, directions, components, device):
+    """Shared body of the normal orientation: call(k, max_distance, anchor, guides, num_guides, normals, components, memory)
+    is the C entry point.  Works on a copy of `normals`: a numpy array, or a torch tensor on the GPU when the normals or the
+    guides are device tensors or with device=True."""
+    if viewpoints is not None and directions is not None:
+        raise ValueError("viewpoints or directions, not both")
+    guides = viewpoints if viewpoints is not None else directions
+    anchor = 0 if guides is None else (1 if viewpoints is not None else 2)
+    g, gmem, gkeep = _buf(guides)
+    ng = 0
+    if guides is not None:
+        count = gkeep.numel() if hasattr(gkeep, "numel") else gkeep.size
+        if count % ndim:
+            raise ValueError("guides: %d values, not a multiple of ndim = %d (x fastest)" % (count, ndim))
+        ng = count // ndim
+    _, nmem, nkeep = _buf(normals)
+    count = nkeep.numel() if hasattr(nkeep, "numel") else nkeep.size
+    if count != n * ndim:
+        raise ValueError("normals: %d values for %d points of %d dimensions" % (count, n, ndim))
+    on_device = device or gmem == FI_DEVICE or nmem == FI_DEVICE
+    if on_device:
+        import torch
+        if guides is not None and gmem != FI_DEVICE:
+            gkeep = torch.as_tensor(gkeep).to("cuda")
+            g = C.c_void_p(gkeep.data_ptr())
+        nrm = nkeep.clone() if nmem == FI_DEVICE else torch.as_tensor(nkeep).to(gkeep.device if guides is not None else "cuda")
+        nrm = nrm.reshape(n, ndim)
+        comp = torch.empty(n, dtype=torch.int64, device=nrm.device) if components else None
+        ptr = lambda t: None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())  # noqa: E731
+    else:
+        nrm = np.array(nkeep, np.float32).reshape(n, ndim)
+        comp = np.empty(n, np.int64) if components else None
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+    if n > 0 or not on_device:
+        check(call(int(k), float(max_distance), anchor, g, ng, ptr(nrm), ptr(comp), FI_DEVICE if on_device else FI_HOST))
+    return (nrm, comp) if components else nrm
+
+
+def _propagated(index, call, ndim, n, k, max_distance, viewpoints, directions, variation, device):
+    """estimate_normals(propagate=True) of a PointIndex or a LatticeField: the canonical normals, then their orientation,
+    the guides as votes"""
+    if viewpoints is not None and directions is not None:
+        raise ValueError("viewpoints or directions, not both")
+    on_device = device or any(hasattr(g, "is_cuda") and g.is_cuda for g in (viewpoints, directions))
+    res = _estimate_normals(call, ndim, n, k, max_distance, None, None, variation, on_device)
+    nrm, var = res if variation else (res, None)
+    nrm = index.orient_normals(nrm, k=k, max_distance=max_distance, viewpoints=viewpoints, directions=directions,
+                               device=on_device)
+    return (nrm, var) if variation else nrm
+
+
 def _distance_field(call, total, indices, device):
     """Shared body of the distance fields: call(distances, indices, memory); numpy arrays of `total` values (x fastest), or
     torch tensors on the current GPU with device=True."""
@@ -281,16 +332,34 @@ class PointIndex:
             return _capi.lib().fi_points_knn(self._h, n, q, kk, md, d, i, mem)
         return _knn(call, self.ndim, queries, k, max_distance, indices)
 
-    def estimate_normals(self, k=16, max_distance=math.inf, viewpoints=None, directions=None, variation=False, device=False):
+    def estimate_normals(self, k=16, max_distance=math.inf, viewpoints=None, directions=None, variation=False, device=False,
+                         propagate=False):
         """Normals (num_points, ndim) float32 of the set's own points, each fitted to its k nearest points (itself included)
         within max_distance by a local PCA in fp64 on the device; with variation=True also the surface variation
         lambda_min / sum(lambda) (num_points,).  viewpoints: one sensor position (ndim,) or one per point -- normals look
         at it (outward: the sign sdf_from_points wants); directions: rough normals, one per point, to agree with; neither:
         each normal's largest component is positive, which is NOT a consistent orientation.  Points that are non-finite or
-        have fewer than ndim neighbours get a zero normal and a NaN variation (include/fi_hip.h fi_estimate_normals)."""
+        have fewer than ndim neighbours get a zero normal and a NaN variation (include/fi_hip.h fi_estimate_normals).
+        propagate=True: the canonical normals, then orient_normals(k, max_distance) over them -- a consistent orientation
+        without guides; viewpoints / directions then only vote for each component's sign."""
         def call(kk, md, orient, g, ng, nrm, var, mem):
             return _capi.lib().fi_points_estimate_normals(self._h, kk, md, orient, g, ng, nrm, var, mem)
-        return _estimate_normals(call, self.ndim, self.num_points, k, max_distance, viewpoints, directions, variation, device)
+        if not propagate:
+            return _estimate_normals(call, self.ndim, self.num_points, k, max_distance, viewpoints, directions, variation, device)
+        return _propagated(self, call, self.ndim, self.num_points, k, max_distance, viewpoints, directions, variation, device)
+
+    def orient_normals(self, normals, k=16, max_distance=math.inf, viewpoints=None, directions=None, components=False,
+                       device=False):
+        """`normals` (num_points, ndim) with one consistent sign per connected component of the set's k-nearest-neighbour
+        graph: signs spread along the minimum spanning forest that prefers parallel normal lines (Hoppe et al.), found on
+        the device; with components=True also each point's component (its smallest point index; -1 for a point that is
+        non-finite or has a zero or non-finite normal, which stays as it is).  Without guides a component's highest point
+        on the last axis looks up that axis; viewpoints / directions (as for estimate_normals) vote per component instead,
+        so one sensor position serves a whole closed object (include/fi_hip.h fi_orient_normals)."""
+        def call(kk, md, anchor, g, ng, nrm, comp, mem):
+            return _capi.lib().fi_points_orient_normals(self._h, kk, md, anchor, g, ng, nrm, comp, mem)
+        return _orient_normals(call, self.ndim, self.num_points, normals, k, max_distance, viewpoints, directions, components,
+                               device)
 
     def distance_field(self, sizes, max_distance=math.inf, indices=False, device=False):
         """PointIndex.nearest of every point of a lattice of `sizes` (x fastest), flat."""
@@ -715,7 +784,8 @@ class LatticeField:
             return _capi.lib().fi_knn(self._h, n, q, kk, md, d, i, mem)
         return _knn(call, len(self.sizes), queries, k, max_distance, indices)
 
-    def estimate_normals(self, k=16, max_distance=math.inf, viewpoints=None, directions=None, variation=False, device=False):
+    def estimate_normals(self, k=16, max_distance=math.inf, viewpoints=None, directions=None, variation=False, device=False,
+                         propagate=False):
         """PointIndex.estimate_normals of the data points of this context, in the order they were added
         (include/fi_hip.h fi_estimate_normals)."""
         n = C.c_long(0)
@@ -723,7 +793,21 @@ class LatticeField:
 
         def call(kk, md, orient, g, ng, nrm, var, mem):
             return _capi.lib().fi_estimate_normals(self._h, kk, md, orient, g, ng, nrm, var, mem)
-        return _estimate_normals(call, len(self.sizes), n.value, k, max_distance, viewpoints, directions, variation, device)
+        if not propagate:
+            return _estimate_normals(call, len(self.sizes), n.value, k, max_distance, viewpoints, directions, variation, device)
+        return _propagated(self, call, len(self.sizes), n.value, k, max_distance, viewpoints, directions, variation, device)
+
+    def orient_normals(self, normals, k=16, max_distance=math.inf, viewpoints=None, directions=None, components=False,
+                       device=False):
+        """PointIndex.orient_normals over the data points of this context, in the order they were added
+        (include/fi_hip.h fi_orient_normals)."""
+        n = C.c_long(0)
+        check(_capi.lib().fi_point_count(self._h, C.byref(n)))
+
+        def call(kk, md, anchor, g, ng, nrm, comp, mem):
+            return _capi.lib().fi_orient_normals(self._h, kk, md, anchor, g, ng, nrm, comp, mem)
+        return _orient_normals(call, len(self.sizes), n.value, normals, k, max_distance, viewpoints, directions, components,
+                               device)
 
     def distance_field(self, max_distance=math.inf, indices=False, device=False):
         """LatticeField.nearest of every lattice point (x fastest), flat: numpy arrays, or torch tensors with device=True."""
@@ -1038,14 +1122,16 @@ def sdf_from_points(sizes, weights, positions, normals=None, point_weights=None,
     return field
 
 
-def sdf_from_unoriented_points(sizes, weights, positions, k=16, viewpoints=None, directions=None, **kw):
+def sdf_from_unoriented_points(sizes, weights, positions, k=16, viewpoints=None, directions=None, propagate=False, **kw):
     """sdf_from_points for a cloud without normals: a PointIndex over `positions`, its estimate_normals(k, viewpoints,
-    directions), then sdf_from_points(sizes, weights, positions, normals, **kw).  Without viewpoints or directions the
-    normals carry no consistent orientation, and neither does the field's sign."""
+    directions, propagate), then sdf_from_points(sizes, weights, positions, normals, **kw).  Without viewpoints or
+    directions and without propagate=True the normals carry no consistent orientation, and neither does the field's sign;
+    with propagate=True the guides are optional (PointIndex.orient_normals)."""
     if positions is None:
         raise ValueError("positions is null")
     normals = PointIndex(positions, ndim=len(sizes)).estimate_normals(k=k, viewpoints=viewpoints, directions=directions,
-                                                                      device=hasattr(positions, "is_cuda") and positions.is_cuda)
+                                                                      device=hasattr(positions, "is_cuda") and positions.is_cuda,
+                                                                      propagate=propagate)
     return sdf_from_points(sizes, weights, positions, normals, **kw)
 
 

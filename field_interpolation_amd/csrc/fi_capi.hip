@@ -7,6 +7,7 @@
 #include "fi_sample.h"
 #include "fi_nearest.h"
 #include "fi_knn.h"
+#include "fi_orient.h"
 #include "fi_surface.h"
 #include "fi_robust.h"
 
@@ -1442,6 +1443,50 @@ int fi_points_estimate_normals(fi_points* h, int k, float max_distance, int orie
 	check_points(h);
 	check_normals(&h->t, h->t.D, k, max_distance, orient, guides, num_guides, normals, memory);
 	fi::estimate_normals(h->t, k, max_distance, orient, guides, num_guides, normals, variation, memory, nullptr);
+	FI_API_END
+}
+
+
+// ---- a consistent sign for normals (fi_orient.hip) ----------------------------------------------
+namespace {
+void check_orient(const fi::NearestIndex* t, int ndim, int k, float max_distance, int anchor, const float* guides, long num_guides,
+                  const float* normals, int memory)
+{
+	FI_REQUIRE(ndim >= 2, FI_ERR_INVALID, "normals need 2 or 3 dimensions (got %d)", ndim);
+	check_k(k);
+	FI_REQUIRE(normals != nullptr, FI_ERR_INVALID, "normals is null");
+	FI_REQUIRE(max_distance >= 0.0f, FI_ERR_INVALID, "max_distance must be >= 0 (got %g)", static_cast<double>(max_distance));
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	FI_REQUIRE(anchor == FI_ORIENT_NONE || anchor == FI_ORIENT_VIEWPOINTS || anchor == FI_ORIENT_DIRECTIONS, FI_ERR_INVALID,
+	           "bad anchor %d", anchor);
+	if (anchor == FI_ORIENT_NONE || !t) { return; }
+	FI_REQUIRE(guides != nullptr, FI_ERR_INVALID, "anchor %d without guides", anchor);
+	FI_REQUIRE(num_guides == t->n || (anchor == FI_ORIENT_VIEWPOINTS && num_guides == 1), FI_ERR_INVALID,
+	           "%ld guides for %lld points", num_guides, static_cast<long long>(t->n));
+}
+}  // namespace
+
+int fi_orient_normals(fi_ctx* c, int k, float max_distance, int anchor, const float* guides, long num_guides, float* normals,
+                      long long* components, int memory)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	check_orient(nullptr, c->g.ndim, k, max_distance, anchor, guides, num_guides, normals, memory);
+	check_undivided(c);
+	const fi::NearestIndex& t = fi::nearest_of(c);
+	check_orient(&t, c->g.ndim, k, max_distance, anchor, guides, num_guides, normals, memory);
+	fi::orient_normals(t, k, max_distance, anchor, guides, num_guides, normals, components, memory, c->stream);
+	FI_API_END
+}
+
+int fi_points_orient_normals(fi_points* h, int k, float max_distance, int anchor, const float* guides, long num_guides,
+                             float* normals, long long* components, int memory)
+{
+	FI_API_BEGIN
+	check_points(h);
+	check_orient(&h->t, h->t.D, k, max_distance, anchor, guides, num_guides, normals, memory);
+	fi::orient_normals(h->t, k, max_distance, anchor, guides, num_guides, normals, components, memory, nullptr);
 	FI_API_END
 }
 

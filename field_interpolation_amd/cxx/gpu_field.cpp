@@ -400,6 +400,27 @@ bool GpuLatticeField::estimate_normals(std::vector<float>* normals, int k, const
 	return true;
 }
 
+bool GpuLatticeField::orient_normals(std::vector<float>* normals, int k, const std::vector<float>& viewpoints,
+                                     std::vector<long long>* components, float max_distance) const
+{
+	const size_t D = sizes_.size();
+	long         n = 0;
+	if (!normals || viewpoints.size() % D != 0 || fi_point_count(ctx_, &n) != FI_OK || normals->size() != D * n) {
+		warn("orient_normals");
+		return false;
+	}
+	if (components) { components->resize(n); }
+	float      none[3] = {0.0f, 0.0f, 0.0f};
+	const bool guided  = !viewpoints.empty();
+	if (fi_orient_normals(ctx_, k, max_distance, guided ? FI_ORIENT_VIEWPOINTS : FI_ORIENT_NONE, guided ? viewpoints.data() : nullptr,
+	                      static_cast<long>(viewpoints.size() / D), n ? normals->data() : none,
+	                      components && n ? components->data() : nullptr, FI_HOST) != FI_OK) {
+		warn("orient_normals");
+		return false;
+	}
+	return true;
+}
+
 bool GpuLatticeField::distance_field(std::vector<float>* distances, std::vector<long long>* indices, float max_distance) const
 {
 	if (!distances) {

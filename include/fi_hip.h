@@ -649,6 +649,36 @@ int fi_estimate_normals(fi_ctx* ctx, int k, float max_distance, int orient, cons
 int fi_points_estimate_normals(fi_points* points, int k, float max_distance, int orient, const float* guides, long num_guides,
                                float* normals, float* variation, int memory);
 
+/* ---- a consistent sign for the normals of a point cloud -------------------------------------------
+ * The contract (tests/orient_reference.py is its definition in numpy).  `normals` float[n * ndim] in point
+ * order (fi_estimate_normals' with FI_ORIENT_NONE, or any others) are read and written in place; ndim = 2 or 3:
+ *   1. point i is LIVE if its position is finite and its normal is finite and not all zeros.  A point that is not live keeps
+ *      its normal's bits and gets component -1;
+ *   2. the graph: for every live i its own fi_knn result (k, max_distance) over the whole set; entries j = -1, j = i and j
+ *      not live are skipped, every other entry is the undirected edge {i, j}; an edge listed from either side counts once;
+ *   3. edge values, fp64 from the fp32 normals, one rounding per operation: d = 0.0 + n_i0 n_j0 + n_i1 n_j1 (+ n_i2 n_j2) in
+ *      ascending axes (symmetric in i and j); flip = d < 0; a = (float)|d|;
+ *   4. the edges are strictly ordered by (a descending, lo = min(i, j) ascending, hi = max(i, j) ascending): agreement of the
+ *      normal LINES first, the indices make the order total.  The forest is the minimum spanning forest of the graph under
+ *      that order -- unique, so the result does not depend on how it is computed;
+ *   5. inside a component, t_i = +1 or -1 with t_i t_j = -1 exactly on the forest edges with flip, and t = +1 at the
+ *      component's smallest point index c; components[i] = c (long long[n], or NULL);
+ *   6. the component's sign S.  The extreme rule (FI_ORIENT_NONE, and a tied vote): e is the live member with the largest
+ *      coordinate on the last axis (compared as fp32; a tie: the smallest index); of t_e n_e, from axis ndim - 1 down to 0,
+ *      the first non-zero component decides: S = -1 if it is negative, else +1.  The vote (FI_ORIENT_VIEWPOINTS,
+ *      FI_ORIENT_DIRECTIONS; guides as for fi_estimate_normals): w_i is step 5's expression of fi_estimate_normals for the
+ *      normal t_i n_i; members with w > 0 vote +, with w < 0 vote -, with w == 0 or non-finite do not vote; more - than +:
+ *      S = -1, more + than -: S = +1, equal counts: the extreme rule.  One sensor position thus serves a whole closed object,
+ *      where fi_estimate_normals' per-point test is wrong on the far side;
+ *   7. n_i <- S t_i n_i: the same bits, or every component's sign bit turned.
+ * Results depend neither on the launch shape nor on timing.  ndim = 1, k outside 1..32, NULL normals, a NaN or negative
+ * max_distance, a bad memory kind or anchor, anchor != 0 with NULL guides or a wrong num_guides: FI_ERR_INVALID.  A slab
+ * context: FI_ERR_UNSUPPORTED.  n = 0 succeeds.  `memory` applies to every buffer of the call. */
+int fi_orient_normals(fi_ctx* ctx, int k, float max_distance, int anchor, const float* guides, long num_guides, float* normals,
+                      long long* components, int memory);
+int fi_points_orient_normals(fi_points* points, int k, float max_distance, int anchor, const float* guides, long num_guides,
+                             float* normals, long long* components, int memory);
+
 /* ---- exact distances to a surface; redistancing ------------------------------------------------
  * The contract ("Distances to a surface") is this project's own.  All arithmetic is fp32, one rounding per
  * operation (no FMA contraction):

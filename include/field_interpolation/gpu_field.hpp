@@ -107,6 +107,14 @@ public:
 	bool estimate_normals(std::vector<float>* normals, int k = 16, const std::vector<float>& viewpoints = std::vector<float>(),
 	                      std::vector<float>* variation = nullptr,
 	                      float max_distance = std::numeric_limits<float>::infinity()) const;
+	// One consistent sign for `normals` (ndim floats per data point, in place) per connected component of the points'
+	// k-nearest-neighbour graph, spread along its minimum spanning forest on the device; without viewpoints a component's
+	// highest point on the last axis looks up that axis, with viewpoints (ndim floats, or ndim per point) they vote per
+	// component.  components (optional): each point's component (its smallest point index, -1 for a point without a usable
+	// normal).  The contract is include/fi_hip.h fi_orient_normals.  false: the library refused the call.
+	bool orient_normals(std::vector<float>* normals, int k = 16, const std::vector<float>& viewpoints = std::vector<float>(),
+	                    std::vector<long long>* components = nullptr,
+	                    float max_distance = std::numeric_limits<float>::infinity()) const;
 	// nearest() of every lattice point (x fastest): num_unknowns() distances (and indices)
 	bool distance_field(std::vector<float>* distances, std::vector<long long>* indices = nullptr,
 	                    float max_distance = std::numeric_limits<float>::infinity()) const;
