@@ -138,31 +138,21 @@ struct RowsOnGpu {
 	// The rows' note (recipe.hpp) still holds: the noted rows matrix-free on their lattice -- fi_set_model for the model rows
 	// (never uploaded: config 3's 100 M triplets stay on the host), fi_add_points for the data rows from the noted copies of
 	// the point arrays -- and only the rows nobody vouches for as triplets.  false: nothing was set up (the caller's edits
-	// broke a checksum, two sets of model weights, a triplet appended to a noted row, a lattice of another shape, more than
-	// three dimensions): the generic path below takes all rows, as before round 6.
+	// broke a checksum -- it covers every noted triplet and right-hand side --, two sets of model weights, a triplet appended
+	// to a noted row, a lattice of another shape, more than three dimensions): the generic path below takes all rows, as
+	// before round 6.
 	bool from_recipe(const LinearEquation& eq, int num_columns, int dtype, const std::vector<int>* lattice)
 	{
 		const detail::Recipe* r = eq.recipe.get();
-		if (!r || r->segments.empty() || std::getenv("FI_DROPIN_NO_RECIPE")) { return false; }
-		if (lattice && !lattice->empty() && *lattice != r->sizes) { return false; }
-		if (r->sizes.empty() || r->sizes.size() > 3) { return false; }
+		if (!r || std::getenv("FI_DROPIN_NO_RECIPE")) { return false; }
+		// the note's ranges, and every triplet and right-hand side in them, read again at every solve (recipe.hpp)
+		if (!detail::noted_rows_unchanged(eq, lattice)) { return false; }
 		long long n = 1;
 		for (int s : r->sizes) { n *= s; }
 		if (n != num_columns) { return false; }
 		const detail::Segment* model = nullptr;
-		size_t row_end = 0, trip_end = 0;
 		for (const detail::Segment& s : r->segments) {
-			if (s.row0 < row_end || s.trip0 < trip_end || s.row1 < s.row0 || s.trip1 < s.trip0 || s.row1 > eq.rhs.size() ||
-			    s.trip1 > eq.triplets.size()) {
-				return false;
-			}
-			row_end  = s.row1;
-			trip_end = s.trip1;
-			if (detail::sample_checksum(eq.triplets, s.trip0, s.trip1, eq.rhs, s.row0, s.row1) != s.checksum) { return false; }
-			if (s.kind == detail::Segment::kModel) {
-				if (model) { return false; }
-				model = &s;
-			}
+			if (s.kind == detail::Segment::kModel) { model = &s; }
 		}
 		// the rows between the noted ranges, renumbered from 0 in their order
 		std::vector<Triplet> extra;

@@ -32,8 +32,9 @@ struct LinearEquation  // A x = rhs; entries sharing (row, col) add up
 	std::vector<float> rhs;
 	// Not in the original: add_field_constraints / add_points of this library note beside the rows what they appended
 	// (model weights, the point arrays).  A solver that finds the noted rows unchanged applies them matrix-free on the
-	// lattice instead of uploading them as triplets; rows the note does not cover go up as before.  Callers never touch it
-	// (brace-initialisation, copies and moves of the two members above work as in the original).
+	// lattice instead of uploading them as triplets; rows the note does not cover go up as before.  "Unchanged" is checked
+	// over every noted triplet and right-hand side at every solve: rows edited in place are solved as edited, through the
+	// triplets.  Callers never touch it (brace-initialisation, copies and moves of the two members above work as in the original).
 	std::shared_ptr<const detail::Recipe> recipe;
 };
 
