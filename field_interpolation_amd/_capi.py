@@ -23,6 +23,7 @@ SYMBOLS = [
     "fi_group_solve_cg", "fi_group_apply_AtA_f64", "fi_group_true_residual", "fi_group_get_solution_f64", "fi_group_tile_pass", "fi_group_error_map",
     "fi_group_iso_extract", "fi_iso_extract", "fi_iso_extract_field", "fi_mesh_info", "fi_mesh_copy", "fi_mesh_destroy",
     "fi_dual_contour", "fi_dual_contour_field",
+    "fi_mesh_create", "fi_mesh_parts", "fi_mesh_measure", "fi_mesh_select",
     "fi_group_sample", "fi_sample", "fi_sample_field",
     "fi_nearest", "fi_distance_field", "fi_points_create", "fi_points_nearest", "fi_points_distance_field", "fi_points_destroy",
     "fi_knn", "fi_points_knn", "fi_estimate_normals", "fi_points_estimate_normals",
@@ -71,6 +72,12 @@ class FiRobustOptions(C.Structure):
 class FiRobustStats(C.Structure):
     _fields_ = [("rounds", C.c_int), ("iterations", C.c_int), ("scale", C.c_float), ("max_weight_change", C.c_float),
                 ("points_used", C.c_long), ("points_zeroed", C.c_long), ("reweight_ms", C.c_double)]
+
+
+class FiMeshPart(C.Structure):
+    _fields_ = [("vertices", C.c_longlong), ("primitives", C.c_longlong), ("edges", C.c_longlong),
+                ("boundary", C.c_longlong), ("irregular", C.c_longlong), ("size", C.c_double), ("enclosed", C.c_double),
+                ("lo", C.c_float * 3), ("hi", C.c_float * 3)]
 
 
 class FiError(RuntimeError):
@@ -145,6 +152,10 @@ def lib():
     L.fi_mesh_info.argtypes = [vp, C.POINTER(C.c_long), C.POINTER(C.c_long), ip]
     L.fi_mesh_copy.argtypes = [vp, fp, fp, vp, vp, C.c_int]
     L.fi_mesh_destroy.argtypes = [vp]
+    L.fi_mesh_create.argtypes = [C.POINTER(vp), C.c_int, C.c_long, fp, fp, vp, C.c_long, vp, C.c_int]
+    L.fi_mesh_parts.argtypes = [vp, C.POINTER(C.c_long), vp, vp, C.c_int]
+    L.fi_mesh_measure.argtypes = [vp, C.c_long, vp, C.POINTER(C.c_long)]
+    L.fi_mesh_select.argtypes = [vp, C.c_long, vp, C.POINTER(vp)]
     L.fi_group_sample.argtypes = [vp, fp, C.c_long, fp, C.c_int, C.c_float, fp, fp]
     L.fi_sample.argtypes = [vp, fp, C.c_long, fp, C.c_int, C.c_float, fp, fp, C.c_int]
     L.fi_sample_field.argtypes = [fp, C.c_int, ip, C.c_long, fp, C.c_int, C.c_float, fp, fp, C.c_int]

@@ -66,7 +66,7 @@ def _buf(a, dtype=np.float32):
         return None, None, None
     if hasattr(a, "data_ptr"):           # torch tensor
         import torch
-        want = {np.float32: torch.float32, np.float64: torch.float64, np.int32: torch.int32}[dtype]
+        want = {np.float32: torch.float32, np.float64: torch.float64, np.int32: torch.int32, np.int64: torch.int64}[dtype]
         t = a.contiguous()
         if t.dtype != want:
             t = t.to(want)
@@ -102,6 +102,149 @@ def _take_mesh(h, ndim, normals=True):
         return IsoMesh(v, n, i, k)
     finally:
         _capi.lib().fi_mesh_destroy(h)
+
+
+MeshParts = collections.namedtuple("MeshParts", ["vertex_labels", "primitive_labels", "vertices", "primitives", "edges", "boundary",
+                                                 "irregular", "size", "enclosed", "lo", "hi", "closed", "euler"])
+MeshParts.__doc__ = """The connected parts of a mesh (include/fi_hip.h, fi_mesh_parts / fi_mesh_measure): vertex_labels (V,) and
+primitive_labels (P,) int32, the part of every vertex (-1: used by no primitive) and primitive, parts numbered by their smallest
+vertex; then one entry per part: vertices, primitives, edges, boundary, irregular (int64), size (area / length) and enclosed
+(volume / area, positive for a blob of inside, negative for a cavity; meaningful for closed parts) float64, lo / hi (C, ndim)
+float32 bounding boxes, closed = no boundary and nothing irregular, euler = vertices - edges + primitives (2-D, where the
+segments are the edges: vertices - edges)."""
+
+
+def _mesh_handle(mesh):
+    """A device mesh handle (the caller destroys it) of an IsoMesh of numpy arrays or torch tensors -> (handle, ndim, memory,
+    a tensor of the mesh or None)."""
+    v, vmem, vkeep = _buf(mesh.vertices)
+    n, nmem, _nkeep = _buf(mesh.normals)
+    i, imem, ikeep = _buf(mesh.indices, np.int32)
+    k, kmem, _kkeep = _buf(mesh.keys, np.int64)
+    mem = _same_memory(vmem, nmem, imem, kmem)
+    if len(vkeep.shape) != 2 or len(ikeep.shape) != 2 or vkeep.shape[1] != ikeep.shape[1]:
+        raise ValueError("a mesh is vertices (V, ndim) and indices (P, ndim)")
+    ndim = int(vkeep.shape[1])
+    nv, npr = int(vkeep.shape[0]), int(ikeep.shape[0])
+    for other, keep in ((n, _nkeep), (k, _kkeep)):
+        if other is not None and int(keep.shape[0]) != nv:
+            raise ValueError("normals and keys have one entry per vertex")
+    h = C.c_void_p()
+    check(_capi.lib().fi_mesh_create(C.byref(h), ndim, nv, v if nv else None, n if nv else None, k if nv else None, npr,
+                                     i if npr else None, mem))
+    return h, ndim, mem, (vkeep if hasattr(vkeep, "data_ptr") else None)
+
+
+def _handle_parts(h, ndim, like=None):
+    """MeshParts of a device mesh handle; the labels as torch tensors on like's device, else numpy."""
+    L = _capi.lib()
+    nv, np_, count = C.c_long(0), C.c_long(0), C.c_long(0)
+    check(L.fi_mesh_info(h, C.byref(nv), C.byref(np_), None))
+    if like is not None and like.is_cuda:
+        import torch
+        vl = torch.empty(nv.value, dtype=torch.int32, device=like.device)
+        pl = torch.empty(np_.value, dtype=torch.int32, device=like.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None  # noqa: E731
+        check(L.fi_mesh_parts(h, C.byref(count), ptr(vl), ptr(pl), FI_DEVICE))
+    else:
+        vl, pl = np.empty(nv.value, np.int32), np.empty(np_.value, np.int32)
+        check(L.fi_mesh_parts(h, C.byref(count), C.c_void_p(vl.ctypes.data), C.c_void_p(pl.ctypes.data), FI_HOST))
+    rows = (_capi.FiMeshPart * max(count.value, 1))()
+    check(L.fi_mesh_measure(h, count.value, C.cast(rows, C.c_void_p), C.byref(count)))
+    rows = rows[:count.value]
+    col = lambda f, t: np.array([getattr(r, f) for r in rows], t)  # noqa: E731
+    ints = {f: col(f, np.int64) for f in ("vertices", "primitives", "edges", "boundary", "irregular")}
+    box = lambda f: np.array([list(getattr(r, f))[:ndim] for r in rows], np.float32).reshape(-1, ndim)  # noqa: E731
+    closed = (ints["boundary"] == 0) & (ints["irregular"] == 0)
+    euler = ints["vertices"] - ints["edges"] + (ints["primitives"] if ndim == 3 else 0)
+    return MeshParts(vl, pl, ints["vertices"], ints["primitives"], ints["edges"], ints["boundary"], ints["irregular"],
+                     col("size", np.float64), col("enclosed", np.float64), box("lo"), box("hi"), closed, euler)
+
+
+def _handle_select(h, keep):
+    """The sub-mesh of the parts keep marks, as a new device mesh handle."""
+    keep = np.ascontiguousarray(np.asarray(keep).astype(bool), np.uint8).reshape(-1)
+    out = C.c_void_p()
+    check(_capi.lib().fi_mesh_select(h, len(keep), C.c_void_p(keep.ctypes.data) if len(keep) else None, C.byref(out)))
+    return out
+
+
+def _take_mesh_like(h, ndim, normals, like):
+    """_take_mesh, or with `like` a CUDA tensor the same as torch tensors on its device."""
+    if like is None or not like.is_cuda:
+        return _take_mesh(h, ndim, normals)
+    import torch
+    try:
+        nv, np_ = C.c_long(0), C.c_long(0)
+        check(_capi.lib().fi_mesh_info(h, C.byref(nv), C.byref(np_), None))
+        v = torch.empty((nv.value, ndim), dtype=torch.float32, device=like.device)
+        n = torch.empty((nv.value, ndim), dtype=torch.float32, device=like.device) if normals else None
+        i = torch.empty((np_.value, ndim), dtype=torch.int32, device=like.device)
+        k = torch.empty(nv.value, dtype=torch.int64, device=like.device)
+        ptr = lambda t: None if t is None or not t.numel() else C.c_void_p(t.data_ptr())  # noqa: E731
+        check(_capi.lib().fi_mesh_copy(h, ptr(v), ptr(n), ptr(i), ptr(k), FI_DEVICE))
+        return IsoMesh(v, n, i, k)
+    finally:
+        _capi.lib().fi_mesh_destroy(h)
+
+
+def mesh_parts(mesh):
+    """The connected parts of a mesh the caller holds (an IsoMesh of numpy arrays, or of torch CUDA tensors: then the labels
+    come back as tensors on that device), labelled and measured on the device.  normals and keys may be None.  -> MeshParts"""
+    h, ndim, _mem, like = _mesh_handle(mesh)
+    try:
+        return _handle_parts(h, ndim, like)
+    finally:
+        _capi.lib().fi_mesh_destroy(h)
+
+
+def select_parts(mesh, keep):
+    """The sub-mesh of the parts whose entry of `keep` (one boolean per part, e.g. keep_parts') is set: their vertices in the
+    original order with normals and keys, their primitives in the original order with indices remapped; vertices no kept
+    primitive uses are dropped.  -> IsoMesh, where `mesh` lives"""
+    h, ndim, _mem, like = _mesh_handle(mesh)
+    try:
+        out = _handle_select(h, keep)
+    finally:
+        _capi.lib().fi_mesh_destroy(h)
+    return _take_mesh_like(out, ndim, mesh.normals is not None, like)
+
+
+def keep_parts(parts, largest=None, min_size=0.0, min_primitives=0, closed=None):
+    """A boolean mask over the parts of a MeshParts: those with size >= min_size, at least min_primitives primitives and, with
+    closed = True / False, those that are closed / open; with largest = k only the k of them with the largest size (ties go
+    to the lower part number).  Evaluated on the host from the rows of fi_mesh_measure."""
+    size = np.asarray(parts.size, np.float64)
+    mask = (size >= float(min_size)) & (np.asarray(parts.primitives) >= int(min_primitives))
+    if closed is not None:
+        mask &= np.asarray(parts.closed) == bool(closed)
+    if largest is not None:
+        if int(largest) < 0:
+            raise ValueError("largest must be >= 0")
+        order = np.argsort(-size, kind="stable")          # descending size, ties by ascending part number
+        order = order[mask[order]][:int(largest)]
+        mask = np.zeros(len(size), bool)
+        mask[order] = True
+    return mask
+
+
+def _finish_mesh(h, ndim, normals, largest, min_size, parts):
+    """What the extractors return for a device mesh handle: the mesh, filtered on the device if largest / min_size ask for
+    it (label -> measure -> select, one copy at the end), and with parts=True the MeshParts of the mesh returned."""
+    if largest is None and min_size is None and not parts:
+        return _take_mesh(h, ndim, normals)
+    try:
+        if largest is not None or min_size is not None:
+            keep = keep_parts(_handle_parts(h, ndim), largest=largest, min_size=0.0 if min_size is None else min_size)
+            kept = _handle_select(h, keep)
+            _capi.lib().fi_mesh_destroy(h)
+            h = kept
+        described = _handle_parts(h, ndim) if parts else None
+    except BaseException:
+        _capi.lib().fi_mesh_destroy(h)
+        raise
+    mesh = _take_mesh(h, ndim, normals)
+    return (mesh, described) if parts else mesh
 
 
 def merge_meshes(pieces):
@@ -733,30 +876,33 @@ class LatticeField:
                                           C.byref(st), _same_memory(kg, ko)))
         return out, om, {f: getattr(st, f) for f, _ in st._fields_}
 
-    def iso_surface(self, solution=None, iso=0.0, normals=True):
+    def iso_surface(self, solution=None, iso=0.0, normals=True, largest=None, min_size=None, parts=False):
         """The iso-contour (2-D) / iso-surface (3-D) f = iso of `solution` (this context's owned values, host or device) or,
         with None, of the last solve's solution where it lives on the device -- the step src/sdf_field.cpp:605-613 takes
-        after the solve.  A slab context returns its piece (merge_meshes joins them).  -> IsoMesh"""
+        after the solve.  A slab context returns its piece (merge_meshes joins them).  -> IsoMesh
+        largest = k / min_size = s: only the k largest connected parts / the parts of at least that area (2-D: length) are
+        kept (keep_parts), chosen and cut out on the device before the one copy to the host; parts=True: -> (IsoMesh,
+        MeshParts of that mesh)."""
         h = C.c_void_p()
         if solution is None:
             check(_capi.lib().fi_iso_extract(self._h, None, float(iso), FI_HOST, C.byref(h)))
         else:
             s, mem, _keep = _buf(solution)
             check(_capi.lib().fi_iso_extract(self._h, s, float(iso), mem, C.byref(h)))
-        return _take_mesh(h, len(self.sizes), normals)
+        return _finish_mesh(h, len(self.sizes), normals, largest, min_size, parts)
 
-    def dual_contour(self, solution=None, iso=0.0, gradients=None, normals=True):
+    def dual_contour(self, solution=None, iso=0.0, gradients=None, normals=True, largest=None, min_size=None, parts=False):
         """The dual contour (2-D: segments, 3-D: triangles) of `solution` (this context's owned values, host or device) or,
         with None, of the last solve's solution where it lives on the device: one vertex per crossed cell, fitted to the
         corner gradients so that sharp corners survive (include/fi_hip.h fi_dual_contour).  gradients: (num_owned, ndim)
         in the same memory as `solution`, or None for central differences of f - iso.  Undivided contexts only.  -> IsoMesh
-        (keys: the lattice index of each vertex's cell)"""
+        (keys: the lattice index of each vertex's cell).  largest, min_size, parts: as iso_surface's."""
         s, smem, _ks = _buf(solution)
         g, gmem, _kg = _buf(gradients)
         mem = _same_memory(smem, gmem)
         h = C.c_void_p()
         check(_capi.lib().fi_dual_contour(self._h, s, g, float(iso), mem, C.byref(h)))
-        return _take_mesh(h, len(self.sizes), normals)
+        return _finish_mesh(h, len(self.sizes), normals, largest, min_size, parts)
 
     def sample(self, positions, solution=None, gradients=False, cubic=False, fill=float("nan")):
         """Values (n,) -- and with gradients=True also gradients (n, ndim) -- of `solution` (this context's owned values) or,
@@ -1211,26 +1357,26 @@ def upscale_field(field, small_sizes, large_sizes):
     return out
 
 
-def iso_surface(field, sizes, iso=0.0, normals=True):
+def iso_surface(field, sizes, iso=0.0, normals=True, largest=None, min_size=None, parts=False):
     """The iso-contour (2-D) / iso-surface (3-D) f = iso of a whole lattice field (numpy array or torch CUDA tensor, x
-    fastest), e.g. the output of upscale_field.  -> IsoMesh"""
+    fastest), e.g. the output of upscale_field.  -> IsoMesh.  largest, min_size, parts: as LatticeField.iso_surface's."""
     src, mem, _keep = _buf(field)
     sz = (C.c_int * len(sizes))(*[int(s) for s in sizes])
     h = C.c_void_p()
     check(_capi.lib().fi_iso_extract_field(src, len(sizes), sz, float(iso), mem, C.byref(h)))
-    return _take_mesh(h, len(sizes), normals)
+    return _finish_mesh(h, len(sizes), normals, largest, min_size, parts)
 
 
-def dual_contour(field, sizes, iso=0.0, gradients=None, normals=True):
+def dual_contour(field, sizes, iso=0.0, gradients=None, normals=True, largest=None, min_size=None, parts=False):
     """LatticeField.dual_contour of a whole lattice field (numpy array or torch CUDA tensor, x fastest); gradients:
-    (prod(sizes), ndim) in the same memory, or None.  -> IsoMesh"""
+    (prod(sizes), ndim) in the same memory, or None.  -> IsoMesh.  largest, min_size, parts: as LatticeField.iso_surface's."""
     src, mem, _keep = _buf(field)
     g, gmem, _kg = _buf(gradients)
     mem = _same_memory(mem, gmem)
     sz = (C.c_int * len(sizes))(*[int(s) for s in sizes])
     h = C.c_void_p()
     check(_capi.lib().fi_dual_contour_field(src, g, len(sizes), sz, float(iso), mem, C.byref(h)))
-    return _take_mesh(h, len(sizes), normals)
+    return _finish_mesh(h, len(sizes), normals, largest, min_size, parts)
 
 
 def redistance(field, sizes, iso=0.0, method="iso", max_distance=math.inf):

@@ -10,6 +10,7 @@
 #include "fi_orient.h"
 #include "fi_surface.h"
 #include "fi_robust.h"
+#include "fi_parts.h"
 
 #include <memory>
 
@@ -1239,6 +1240,7 @@ int fi_mesh_copy(const fi_mesh* m, float* vertices, float* normals, int* indices
 	const hipMemcpyKind kind = memory == FI_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
 	const size_t nv = static_cast<size_t>(m->nv), np = static_cast<size_t>(m->np), D = static_cast<size_t>(m->ndim);
 	if (vertices && nv) { FI_HIP_TRY(hipMemcpy(vertices, m->pos.p, sizeof(float) * D * nv, kind)); }
+	FI_REQUIRE(!normals || m->has_normals, FI_ERR_INVALID, "the mesh has no normals");
 	if (normals && nv) { FI_HIP_TRY(hipMemcpy(normals, m->nrm.p, sizeof(float) * D * nv, kind)); }
 	if (indices && np) { FI_HIP_TRY(hipMemcpy(indices, m->idx.p, sizeof(int) * D * np, kind)); }
 	if (keys && nv) { FI_HIP_TRY(hipMemcpy(keys, m->key.p, sizeof(int64_t) * nv, kind)); }
@@ -1246,6 +1248,36 @@ int fi_mesh_copy(const fi_mesh* m, float* vertices, float* normals, int* indices
 }
 
 int fi_mesh_destroy(fi_mesh* m) { return fi::destroy_handle(m); }
+
+// ---- the connected parts of a mesh (fi_parts.hip) -------------------------------------------------
+int fi_mesh_create(fi_mesh** out, int ndim, long num_vertices, const float* vertices, const float* normals, const long long* keys,
+                   long num_primitives, const int* indices, int memory)
+{
+	FI_API_BEGIN
+	fi::mesh_create(out, ndim, num_vertices, vertices, normals, keys, num_primitives, indices, memory);
+	FI_API_END
+}
+
+int fi_mesh_parts(const fi_mesh* m, long* num_parts, int* vertex_labels, int* primitive_labels, int memory)
+{
+	FI_API_BEGIN
+	fi::mesh_parts(m, num_parts, vertex_labels, primitive_labels, memory);
+	FI_API_END
+}
+
+int fi_mesh_measure(const fi_mesh* m, long capacity, fi_mesh_part* parts, long* num_parts)
+{
+	FI_API_BEGIN
+	fi::mesh_measure(m, capacity, parts, num_parts);
+	FI_API_END
+}
+
+int fi_mesh_select(const fi_mesh* m, long num_parts, const unsigned char* keep, fi_mesh** out)
+{
+	FI_API_BEGIN
+	fi::mesh_select(m, num_parts, keep, out);
+	FI_API_END
+}
 
 
 

@@ -1,9 +1,16 @@
 // fi_iso.h -- iso-contour / iso-surface extraction (fi_iso.hip), shared by the C ABI units (fi_capi.hip, fi_group.hip).
 #pragma once
 
+#include <memory>
+#include <mutex>
+
 #include "fi_internal.h"
 
-// the device-resident mesh of fi_iso_extract* (include/fi_hip.h)
+namespace fi {
+struct MeshParts;  // the labelling of a mesh's connected parts and what hangs on it (fi_parts.hip)
+}
+
+// the device-resident mesh of fi_iso_extract* / fi_dual_contour* / fi_mesh_create (include/fi_hip.h); immutable once built
 struct fi_mesh {
 	int        device = 0;
 	int        ndim = 0;
@@ -11,6 +18,10 @@ struct fi_mesh {
 	fi::DevBuf pos, nrm;         // float[nv][ndim]
 	fi::DevBuf idx;              // int32[np][ndim]
 	fi::DevBuf key;              // int64[nv], ascending
+	bool       has_normals = true;  // false: a caller's mesh without normals (fi_mesh_create): nrm is empty
+	// the connected parts, computed at first use (fi_mesh_parts / fi_mesh_measure / fi_mesh_select) and kept with the handle
+	mutable std::mutex                     parts_lock;
+	mutable std::shared_ptr<fi::MeshParts> parts;
 };
 
 namespace fi {

@@ -1,6 +1,7 @@
 // GpuLatticeField: the matrix-free fast path (include/field_interpolation/gpu_field.hpp) over fi_hip.h.
 #include "field_interpolation/gpu_field.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -311,6 +312,59 @@ bool GpuLatticeField::dual_contour(float iso, std::vector<float>* vertices, std:
 		                  indices ? indices->data() : nullptr, nullptr, FI_HOST) == FI_OK;
 	}
 	if (!ok) { warn("dual_contour"); }
+	fi_mesh_destroy(m);
+	return ok;
+}
+
+static_assert(sizeof(MeshPart) == sizeof(fi_mesh_part), "MeshPart mirrors fi_mesh_part");
+
+bool GpuLatticeField::iso_surface_parts(float iso, bool dual, int largest, double min_size, std::vector<float>* vertices,
+                                        std::vector<int>* indices, std::vector<float>* normals, std::vector<MeshPart>* parts) const
+{
+	fi_mesh* m = nullptr;
+	if ((dual ? fi_dual_contour(ctx_, nullptr, nullptr, iso, FI_HOST, &m) : fi_iso_extract(ctx_, nullptr, iso, FI_DEVICE, &m)) != FI_OK) {
+		warn("iso_surface_parts");
+		return false;
+	}
+	// the rows of every part, the mask by keep_parts' rule (field_interpolation_amd/api.py), the sub-mesh, its own rows
+	long count = 0;
+	bool ok = fi_mesh_measure(m, 0, nullptr, &count) == FI_OK || count > 0;
+	std::vector<fi_mesh_part> rows(static_cast<size_t>(count));
+	ok = ok && fi_mesh_measure(m, count, rows.data(), &count) == FI_OK;
+	fi_mesh* kept = nullptr;
+	if (ok) {
+		std::vector<long> order;
+		for (long c = 0; c < count; ++c) {
+			if (rows[static_cast<size_t>(c)].size >= min_size) { order.push_back(c); }
+		}
+		if (largest >= 0) {
+			std::stable_sort(order.begin(), order.end(),
+			                 [&](long a, long b) { return rows[static_cast<size_t>(a)].size > rows[static_cast<size_t>(b)].size; });
+			if (order.size() > static_cast<size_t>(largest)) { order.resize(static_cast<size_t>(largest)); }
+		}
+		std::vector<unsigned char> keep(static_cast<size_t>(count), 0);
+		for (long c : order) { keep[static_cast<size_t>(c)] = 1; }
+		ok = fi_mesh_select(m, count, keep.data(), &kept) == FI_OK;
+	}
+	long nv = 0, np = 0;
+	int  vpp = 0;
+	ok = ok && fi_mesh_info(kept, &nv, &np, &vpp) == FI_OK;
+	const size_t D = sizes_.size();
+	if (ok) {
+		if (vertices) { vertices->resize(D * static_cast<size_t>(nv)); }
+		if (normals) { normals->resize(D * static_cast<size_t>(nv)); }
+		if (indices) { indices->resize(static_cast<size_t>(vpp) * static_cast<size_t>(np)); }
+		ok = fi_mesh_copy(kept, vertices ? vertices->data() : nullptr, normals ? normals->data() : nullptr,
+		                  indices ? indices->data() : nullptr, nullptr, FI_HOST) == FI_OK;
+	}
+	if (ok && parts) {
+		long left = 0;
+		ok = fi_mesh_measure(kept, 0, nullptr, &left) == FI_OK || left > 0;
+		parts->resize(static_cast<size_t>(left));
+		ok = ok && fi_mesh_measure(kept, left, reinterpret_cast<fi_mesh_part*>(parts->data()), &left) == FI_OK;
+	}
+	if (!ok) { warn("iso_surface_parts"); }
+	fi_mesh_destroy(kept);
 	fi_mesh_destroy(m);
 	return ok;
 }

@@ -540,6 +540,52 @@ int fi_mesh_info(const fi_mesh* m, long* num_vertices, long* num_primitives, int
 int fi_mesh_copy(const fi_mesh* m, float* vertices, float* normals, int* indices, long long* keys, int memory);
 int fi_mesh_destroy(fi_mesh* m);
 
+/* ---- the connected parts of a mesh ------------------------------------------------------------
+ * Labels a device mesh's connected parts, says what each part is, and keeps a chosen subset, without the mesh leaving the
+ * device.  Works on the meshes of fi_iso_extract* / fi_dual_contour* (a slab piece's parts are the piece's own) and on meshes
+ * the caller brings (fi_mesh_create).  The contract (tests/mesh_parts_reference.py is its definition in numpy):
+ *   - parts: two primitives belong to one part when a chain of primitives joins them, each sharing a vertex INDEX with the
+ *     next (coincident positions under different indices do not join).  A vertex no primitive uses has label -1 and belongs
+ *     to no part.  Parts are numbered 0 .. C-1 by their smallest vertex index, ascending; labels are int32 and do not depend
+ *     on the run or the launch shape.  An empty mesh: 0 parts, FI_OK.  The labelling is computed at the first of the three
+ *     calls below that needs it and kept with the handle (meshes are immutable);
+ *   - counts, exact.  A half-edge is a directed index pair of a primitive: (a,b), (b,c), (c,a) of a triangle, (a,b) of a
+ *     segment; half-edges with equal ends are ignored.  `vertices` and `primitives` count the part's used vertices and its
+ *     primitives.  3-D: `edges` the distinct unordered pairs, `boundary` the pairs used by exactly one half-edge, `irregular`
+ *     the pairs used by more than two half-edges or by two of the same direction.  2-D: `edges` the half-edges, `boundary`
+ *     the vertices of total degree 1, `irregular` the used vertices that have neither degree 1 nor (in, out) = (1, 1).
+ *     A part is CLOSED when boundary == 0 && irregular == 0; its Euler characteristic in 3-D is vertices - edges + primitives;
+ *   - measures, fp64 from the fp32 coordinates converted exactly, one rounding per operation.  3-D: size = sum of
+ *     |(b-a) x (c-a)| / 2 (the area), enclosed = sum of a . (b x c) / 6.  2-D: size = sum of |b-a| (the length), enclosed =
+ *     sum of (a_x b_y - a_y b_x) / 2.  With the extractors' orientation `enclosed` is positive for a blob of inside and
+ *     negative for a cavity; it means something only for a closed part (the sum over an open part depends on the origin).
+ *     The sums are taken in a fixed order (chunks of 256 of the part's primitives in ascending primitive number, each summed
+ *     by a fixed tree, the chunks added in ascending order) without floating-point atomics: a repeated call returns the same
+ *     bytes.  lo / hi: the per-axis fp32 extremes of the part's vertices (2-D: lo[2] = hi[2] = 0);
+ * fi_mesh_create: vertices ndim floats per vertex, indices ndim int32 per primitive, all in `memory`.  ndim other than 2 or 3:
+ * FI_ERR_UNSUPPORTED (as fi_surface_create); an index outside [0, num_vertices): FI_ERR_INVALID and no mesh; a count >= 2^31:
+ * FI_ERR_UNSUPPORTED; a negative count or a null array of a non-zero count: FI_ERR_INVALID.  keys NULL: the keys 0 .. V-1.
+ * normals NULL: the mesh has no normals -- fi_mesh_copy of it (and of whatever fi_mesh_select makes of it) refuses a normals
+ * buffer with FI_ERR_INVALID.
+ * fi_mesh_parts: the labels into arrays in `memory` (num_vertices / num_primitives int32; either may be NULL).
+ * fi_mesh_measure: parts is a HOST array of `capacity` rows; *num_parts is always set; capacity < *num_parts: FI_ERR_INVALID
+ * and nothing written (parts may be NULL with capacity 0 to ask for the count).
+ * fi_mesh_select: keep is a HOST array, one byte per part (non-zero: kept); num_parts must equal the mesh's count, else
+ * FI_ERR_INVALID.  The result holds the vertices of the kept parts in their original order with their normals and keys (the
+ * keys stay ascending; unused vertices are dropped) and the kept primitives in their original order with their indices
+ * remapped.  No atomics write an output.  Keeping everything on a mesh without unused vertices returns the same arrays;
+ * keeping nothing an empty mesh. */
+typedef struct fi_mesh_part {
+	long long vertices, primitives, edges, boundary, irregular;
+	double    size, enclosed;
+	float     lo[3], hi[3];
+} fi_mesh_part;
+int fi_mesh_create(fi_mesh** out, int ndim, long num_vertices, const float* vertices, const float* normals,
+                   const long long* keys, long num_primitives, const int* indices, int memory);
+int fi_mesh_parts(const fi_mesh* m, long* num_parts, int* vertex_labels, int* primitive_labels, int memory);
+int fi_mesh_measure(const fi_mesh* m, long capacity, fi_mesh_part* parts, long* num_parts);
+int fi_mesh_select(const fi_mesh* m, long num_parts, const unsigned char* keep, fi_mesh** out);
+
 /* ---- point queries: values and gradients at arbitrary positions --------------------------------
  * The contract ("Point queries") is this project's own:
  *   - positions: n points of ndim fp32 values, interleaved, in global lattice coordinates (x fastest, as fi_add_points);

@@ -26,6 +26,16 @@ struct RobustOptions
 	float weight_tolerance = 0; // end when no weight factor moved by this much; 0: never
 };
 
+// One connected part of a mesh (include/fi_hip.h fi_mesh_part, field for field): exact counts, the fp64 measures, the box.
+struct MeshPart
+{
+	long long vertices, primitives, edges, boundary, irregular;
+	double    size, enclosed; // area and enclosed volume (2-D: length and enclosed area); enclosed means something if closed()
+	float     lo[3], hi[3];
+	bool      closed() const { return boundary == 0 && irregular == 0; }
+	long long euler() const { return vertices - edges + primitives; } // of a 3-D part
+};
+
 class GpuLatticeField
 {
 public:
@@ -81,6 +91,14 @@ public:
 	// fastest; without them, central differences of f - iso.  false: no solution yet, or the library refused the call.
 	bool dual_contour(float iso, std::vector<float>* vertices, std::vector<int>* indices, std::vector<float>* normals = nullptr,
 	                  const std::vector<float>* gradients = nullptr) const;
+
+	// iso_surface (dual = false) or dual_contour with central differences (dual = true) of the last solution, cut down to
+	// chosen connected parts on the device before the one copy to the host: the parts of size (area; 2-D: length) >= min_size
+	// and, with largest >= 0, only the `largest` largest of them (ties go to the part with the smaller first vertex).
+	// parts (optional): one row per part of the mesh returned, numbered by their smallest vertex.  The contract is
+	// include/fi_hip.h fi_mesh_parts .. fi_mesh_select.  false: no solution yet, or the library refused the call.
+	bool iso_surface_parts(float iso, bool dual, int largest, double min_size, std::vector<float>* vertices, std::vector<int>* indices,
+	                       std::vector<float>* normals = nullptr, std::vector<MeshPart>* parts = nullptr) const;
 
 	// Values (and, if asked, gradients: ndim floats per point) of the last solution at `positions` (ndim floats per point,
 	// global lattice coordinates, x fastest), sampled where the solution lives on the device: multilinear, or Catmull-Rom
