@@ -683,6 +683,11 @@ class LatticeField:
         fl = [math.floor(float(np.float32(p))) for p in pos]
         return all(0 <= f and f + 1 < n for f, n in zip(fl, self.sizes))
 
+    def _lerp_valid(self, pos):
+        # kLinearInterpolation keeps a sample of multilerp(pos - 0.5, 1) when 0 <= q and q + 1 < size for q in {fl, fl + 1}
+        fl = [math.floor(float(np.float32(p) - np.float32(0.5))) for p in pos]
+        return all(n >= 2 and -1 <= f and f + 1 < n for f, n in zip(fl, self.sizes))
+
     def add_value_constraint(self, pos, value, weight):
         """add_value_constraint (field_interpolation.cpp:57-80).  False if the position was ignored."""
         pos = np.atleast_1d(np.asarray(pos, np.float32))
@@ -710,8 +715,8 @@ class LatticeField:
         pos = np.atleast_1d(np.asarray(pos, np.float32))
         if weight == 0:
             return False
-        if int(kernel) != GradientKernel.kLinearInterpolation and not self._cell_valid(pos):
-            return False
+        if not (self._lerp_valid(pos) if int(kernel) == GradientKernel.kLinearInterpolation else self._cell_valid(pos)):
+            return False                                                     # no sample kept (cpp:219) / cell_index < 0
         self.add_points(0.0, ValueKernel.kLinearInterpolation, weight, kernel, pos,
                         np.atleast_1d(np.asarray(gradient, np.float32)), None)
         return True

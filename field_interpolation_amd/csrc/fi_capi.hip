@@ -49,9 +49,12 @@ __global__ __launch_bounds__(kThreads) void k_upscale(UpscaleArgs a, int64_t nla
 		rest /= a.lsz[d];
 		const float sp = static_cast<float>(c) * (static_cast<float>(a.ssz[d]) - 1.0f) /
 		                 (static_cast<float>(a.lsz[d]) - 1.0f);
+		// a large axis of ONE point: 0 * (small - 1) / 0 is NaN.  The reference, as compiled for x86, floors it to INT_MIN, keeps
+		// no sample and writes 0 (:477-478); here the cast would give 0 and NaN weights, so the point is sent far outside.
+		const bool  ok = sp == sp;
 		const float fl = floorf(sp);
-		base[d] = static_cast<int>(fl);
-		t[d]    = sp - static_cast<float>(base[d]);
+		base[d] = ok ? static_cast<int>(fl) : -4;
+		t[d]    = ok ? sp - static_cast<float>(base[d]) : 0.0f;
 	}
 	float wsum = 0.0f, fsum = 0.0f;
 	for (int q = 0; q < (1 << a.ndim); ++q) {

@@ -127,8 +127,8 @@ bool GpuLatticeField::add_gradient_constraint(const float pos[], const float gra
 	for (size_t d = 0; d < sizes_.size(); ++d) {
 		const float fl = std::floor(lin ? pos[d] - 0.5f : pos[d]);
 		if (lin) {
-			// kept samples need 0 <= q and q + 1 < size for q in {fl, fl + 1}
-			if (!(fl >= -1.0f && fl + 1.0f < static_cast<float>(sizes_[d]))) { return false; }
+			// kept samples need 0 <= q and q + 1 < size for q in {fl, fl + 1}: none on an axis of one point
+			if (!(sizes_[d] >= 2 && fl >= -1.0f && fl + 1.0f < static_cast<float>(sizes_[d]))) { return false; }
 		} else if (!(fl >= 0.0f && fl + 1.0f < static_cast<float>(sizes_[d]))) {
 			return false;  // cell_index, field_interpolation.cpp:116
 		}

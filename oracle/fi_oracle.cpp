@@ -7,11 +7,15 @@
 // and bench.py's cpu_baseline leg may load this library; the product
 // (field_interpolation_amd/, include/) never links, imports or calls it.
 //
-// PARITY STATUS: **parity unpinned by reference tests** -- the reference ships no
-// tests, golden vectors or fixtures, and its sources cannot be
-// built in this image (they need <loguru.hpp> from an absent submodule and
-// Eigen 3, which is not installed; no stand-ins are written for either).  The
-// only known answers that exist are pinned in tests/test_oracle_known_answers.py:
+// PARITY STATUS.  Assembly half (everything up to and including upscale): held bit
+// for bit to the reference's OWN compiled field_interpolation.cpp, add_equation and
+// operator<< -- oracle/_ref/libfi_ref.so, built by oracle/Makefile where the
+// reference's sources are at hand, and its recorded output
+// tests/golden/reference_rows.npz (tests/test_reference_rows.py).  Solve half:
+// **parity unpinned by reference tests** -- the reference ships no tests, golden
+// vectors or fixtures, and sparse_linear.cpp needs Eigen 3,
+// which is not installed.  The known answers that exist are pinned in
+// tests/test_oracle_known_answers.py:
 //   * README.md:29-40  -- the 8x6 worked example (matrix A and rhs b),
 //   * SURVEY.md 8(c)   -- survey-time outputs of the reference assembly for the
 //                         field_1d.cpp:20-29 default input (14 rows/38 triplets and

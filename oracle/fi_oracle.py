@@ -1,7 +1,8 @@
 """ctypes front end of oracle/libfi_oracle.so (the C++ restatement in fi_oracle.cpp).
 
-TEST INFRASTRUCTURE ONLY -- see the header of fi_oracle.cpp for the parity status
-("parity unpinned by reference tests") and the reference file:line citations.
+TEST INFRASTRUCTURE ONLY -- see the header of fi_oracle.cpp for the parity status (the assembly half is held to
+the reference's own compiled code, oracle/fi_ref.py; the solvers are "parity unpinned by reference tests") and
+the reference file:line citations.
 """
 import ctypes as C
 import os

@@ -5,8 +5,9 @@ known_answers.json  the only numbers that come from the REFERENCE: the README's 
                     (README.md:11-40) and the survey-time probe of the reference assembly for the field_1d.cpp
                     default input, plus the closed-form row counts of SURVEY.md section 8.
                     Typed in from those documents; this script only re-writes them in one place.
-oracle_cases.npz    regression vectors made by THIS repository's oracle (the reference cannot be built in this
-                    image: it needs loguru and Eigen -- DESIGN.md section 2), for a matrix of small cases: the
+oracle_cases.npz    regression vectors made by THIS repository's oracle (the reference's solvers cannot be built in
+                    this image: they need Eigen -- DESIGN.md section 2; what its own compiled assembly gives is
+                    recorded by make_golden_reference.py), for a matrix of small cases: the
                     inputs themselves, row / triplet counts, A^T b, diag(A^T A), (A^T A) x for a stored x, and
                     the float64 least-squares solution.  They pin the oracle against drift and give the GPU tests
                     vectors to compare with that do not need the oracle at run time.
