@@ -29,6 +29,8 @@ SYMBOLS = [
     "fi_knn", "fi_points_knn", "fi_estimate_normals", "fi_points_estimate_normals",
     "fi_orient_normals", "fi_points_orient_normals",
     "fi_surface_create", "fi_surface_from_mesh", "fi_surface_distance", "fi_surface_distance_field", "fi_surface_destroy",
+    "fi_surface_raycast", "fi_surface_count_hits", "fi_surface_contains", "fi_surface_signed_distance",
+    "fi_surface_signed_distance_field",
     "fi_redistance", "fi_redistance_field",
     "fi_point_count", "fi_point_residuals", "fi_robust_reweight", "fi_reset_point_weights", "fi_solve_robust",
 ]
@@ -176,6 +178,11 @@ def lib():
     L.fi_surface_distance.argtypes = [vp, C.c_long, fp, C.c_float, fp, vp, fp, C.c_int]
     L.fi_surface_distance_field.argtypes = [vp, ip, C.c_float, fp, vp, C.c_int]
     L.fi_surface_destroy.argtypes = [vp]
+    L.fi_surface_raycast.argtypes = [vp, C.c_long, fp, fp, C.c_float, C.c_float, fp, vp, fp, C.c_int]
+    L.fi_surface_count_hits.argtypes = [vp, C.c_long, fp, fp, C.c_float, C.c_float, C.c_int, vp, C.c_int]
+    L.fi_surface_contains.argtypes = [vp, C.c_long, fp, C.POINTER(C.c_float), vp, C.c_int]
+    L.fi_surface_signed_distance.argtypes = [vp, C.c_long, fp, C.c_float, fp, vp, fp, C.c_int]
+    L.fi_surface_signed_distance_field.argtypes = [vp, ip, C.c_float, fp, vp, C.c_int]
     L.fi_redistance.argtypes = [vp, fp, C.c_float, C.c_int, C.c_float, fp, vp, C.POINTER(vp), C.c_int]
     L.fi_redistance_field.argtypes = [fp, C.c_int, ip, C.c_float, C.c_int, C.c_float, fp, vp, C.POINTER(vp), C.c_int]
     L.fi_point_count.argtypes = [vp, C.POINTER(C.c_long)]

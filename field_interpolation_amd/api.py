@@ -607,6 +607,119 @@ class SurfaceIndex:
             return _capi.lib().fi_surface_distance_field(self._h, sz, float(max_distance), d, i, mem)
         return _distance_field(call, int(np.prod(sizes)), primitives, device)
 
+    # ---- rays (include/fi_hip.h fi_surface_raycast) ----
+    def _rows(self, what, a):
+        """(pointer, memory, keep-alive, rows) of an (n, ndim) float32 input"""
+        p, mem, keep = _buf(a)
+        count = keep.numel() if hasattr(keep, "numel") else keep.size
+        if count % self.ndim:
+            raise ValueError("%s: %d values, not a multiple of ndim = %d (x fastest)" % (what, count, self.ndim))
+        return p, mem, keep, count // self.ndim
+
+    def _rays(self, origins, directions):
+        o, omem, okeep, n = self._rows("origins", origins)
+        d, dmem, dkeep, nd = self._rows("directions", directions)
+        if nd != n:
+            raise ValueError("%d origins, %d directions" % (n, nd))
+        return o, d, _same_memory(omem, dmem), (okeep, dkeep), n
+
+    @staticmethod
+    def _like(keep, shape, dtype):
+        """an output of `shape` where the input `keep` lives, and its pointer"""
+        if hasattr(keep, "data_ptr"):
+            import torch
+            out = torch.empty(shape, dtype=getattr(torch, dtype), device=keep.device)
+            return out, C.c_void_p(out.data_ptr())
+        out = np.empty(shape, getattr(np, dtype))
+        return out, C.c_void_p(out.ctypes.data)
+
+    def raycast(self, origins, directions, t_min=0.0, t_max=math.inf, bary=False):
+        """The closest hit of each ray origins[i] + t directions[i] (n x ndim each, directions not normalised) with
+        t_min <= t <= t_max: (t (n,) float32, primitives (n,) int64), with bary=True also the barycentrics (n, ndim - 1)
+        float32.  No hit: +inf, -1, NaN; a ray with a non-finite origin or direction, or a zero direction: NaN, -1, NaN.
+        Outputs live where the rays live (include/fi_hip.h fi_surface_raycast)."""
+        o, d, mem, keep, n = self._rays(origins, directions)
+        t, tp = self._like(keep[0], (n,), "float32")
+        prim, pp = self._like(keep[0], (n,), "int64")
+        b, bp = self._like(keep[0], (n, self.ndim - 1), "float32") if bary else (None, None)
+        if n:   # (an empty tensor has no storage to point at)
+            check(_capi.lib().fi_surface_raycast(self._h, n, o, d, float(t_min), float(t_max), tp, pp, bp, mem))
+        return (t, prim, b) if bary else (t, prim)
+
+    def count_hits(self, origins, directions, t_min=0.0, t_max=math.inf, limit=2**31 - 1):
+        """The hits (n,) int32 of each ray with t_min <= t <= t_max, saturated at limit >= 1 (limit=1: is anything in the
+        way); a ray that is none counts 0 (include/fi_hip.h fi_surface_count_hits)."""
+        o, d, mem, keep, n = self._rays(origins, directions)
+        c, cp = self._like(keep[0], (n,), "int32")
+        if n:
+            check(_capi.lib().fi_surface_count_hits(self._h, n, o, d, float(t_min), float(t_max), int(limit), cp, mem))
+        return c
+
+    def contains(self, points, direction=None):
+        """bool (n,): the parity of the crossings of the ray from each point along `direction` (ndim values; None: +x).  A
+        mesh that is not closed gives whatever the parity gives (include/fi_hip.h fi_surface_contains)."""
+        p, mem, keep, n = self._rows("points", points)
+        inside, ip = self._like(keep, (n,), "uint8")
+        dv = None
+        if direction is not None:
+            dv = (C.c_float * self.ndim)(*[float(x) for x in np.asarray(direction, np.float64).reshape(self.ndim)])
+        if n:
+            check(_capi.lib().fi_surface_contains(self._h, n, p, dv, ip, mem))
+        return inside.bool() if hasattr(inside, "data_ptr") else inside.astype(bool)
+
+    def signed_distance(self, queries, max_distance=math.inf, primitives=False, closest=False):
+        """SurfaceIndex.distance with the distances negated where contains(queries) holds along +x: negative inside a
+        closed mesh, -0.0 on it, -inf inside and beyond max_distance (include/fi_hip.h fi_surface_signed_distance)."""
+        q, mem, keep, n = self._rows("queries", queries)
+        dist, dp = self._like(keep, (n,), "float32")
+        idx, xp = self._like(keep, (n,), "int64") if primitives else (None, None)
+        cl, cp = self._like(keep, (n, self.ndim), "float32") if closest else (None, None)
+        if n:
+            check(_capi.lib().fi_surface_signed_distance(self._h, n, q, float(max_distance), dp, xp, cp, mem))
+        out = tuple(a for a in (dist, idx, cl) if a is not None)
+        return out if len(out) > 1 else dist
+
+    def signed_distance_field(self, sizes, max_distance=math.inf, primitives=False, device=False):
+        """SurfaceIndex.signed_distance of every point of a lattice of `sizes` (x fastest), flat: numpy arrays, or torch
+        tensors with device=True."""
+        if len(sizes) != self.ndim:
+            raise ValueError("sizes: %d extents for a %d-D surface" % (len(sizes), self.ndim))
+        sz = (C.c_int * len(sizes))(*[int(s) for s in sizes])
+
+        def call(d, i, mem):
+            return _capi.lib().fi_surface_signed_distance_field(self._h, sz, float(max_distance), d, i, mem)
+        return _distance_field(call, int(np.prod(sizes)), primitives, device)
+
+    def render_depth(self, eye, target, up, fov_y, width, height):
+        """A pinhole depth image of a 3-D surface: (t (height, width) float32, primitives (height, width) int64) of the
+        rays from `eye` through the pixel centres, looking at `target` with `up` up and a vertical field of view of fov_y
+        radians; row 0 is the top.  The directions have unit length, so t is the distance from the eye; +inf and -1 where
+        nothing is hit."""
+        if self.ndim != 3:
+            raise ValueError("render_depth needs a 3-D surface")
+        eye = np.asarray(eye, np.float64).reshape(3)
+        fwd = np.asarray(target, np.float64).reshape(3) - eye
+        fwd /= np.linalg.norm(fwd)
+        right = np.cross(fwd, np.asarray(up, np.float64).reshape(3))
+        right /= np.linalg.norm(right)
+        top = np.cross(right, fwd)
+        h = math.tan(0.5 * fov_y)
+        x = ((np.arange(width) + 0.5) / width * 2 - 1) * h * width / height
+        y = (1 - (np.arange(height) + 0.5) / height * 2) * h
+        d = fwd[None, None, :] + x[None, :, None] * right[None, None, :] + y[:, None, None] * top[None, None, :]
+        d /= np.linalg.norm(d, axis=2, keepdims=True)
+        d = d.reshape(-1, 3).astype(np.float32)
+        o = np.broadcast_to(eye.astype(np.float32), d.shape)
+        t, prim = self.raycast(o, d)
+        return t.reshape(height, width), prim.reshape(height, width)
+
+
+def mesh_to_sdf(mesh, sizes, max_distance=math.inf):
+    """The signed distance (flat, x fastest, float32) of every point of a lattice of `sizes` to a mesh -- an IsoMesh or
+    anything with `vertices` and `indices`, from a field or not: SurfaceIndex.signed_distance_field.  The sign is the parity
+    of the crossings along +x, so the mesh should be closed."""
+    return SurfaceIndex.from_mesh(mesh).signed_distance_field(sizes, max_distance)
+
 
 class LatticeField:
     """field_interpolation.hpp:97-114 `LatticeField{sizes}`: sizes[0] (x) is the fastest axis.

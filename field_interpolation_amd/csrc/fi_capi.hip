@@ -9,6 +9,7 @@
 #include "fi_knn.h"
 #include "fi_orient.h"
 #include "fi_surface.h"
+#include "fi_ray.h"
 #include "fi_robust.h"
 #include "fi_parts.h"
 
@@ -1598,6 +1599,70 @@ int fi_surface_distance_field(fi_surface* h, const int* sizes, float max_distanc
 }
 
 int fi_surface_destroy(fi_surface* h) { return fi::destroy_handle(h); }
+
+// ---- rays against a surface (fi_ray.hip) ---------------------------------------------------------
+namespace {
+void check_rays(long n, const float* origins, const float* directions, float t_min, float t_max, const void* out, int memory)
+{
+	FI_REQUIRE(n >= 0, FI_ERR_INVALID, "n = %ld", n);
+	FI_REQUIRE(origins != nullptr && directions != nullptr && out != nullptr, FI_ERR_INVALID, "null origins, directions or output");
+	FI_REQUIRE(t_min <= t_max, FI_ERR_INVALID, "t_min = %g, t_max = %g", static_cast<double>(t_min), static_cast<double>(t_max));  // (NaN fails)
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld rays in one call", n);
+}
+}  // namespace
+
+int fi_surface_raycast(fi_surface* h, long n, const float* origins, const float* directions, float t_min, float t_max, float* t,
+                       long long* primitives, float* bary, int memory)
+{
+	FI_API_BEGIN
+	check_surface(h);
+	check_rays(n, origins, directions, t_min, t_max, t, memory);
+	fi::ray_cast(h->t, n, origins, directions, t_min, t_max, t, primitives, bary, memory, nullptr);
+	FI_API_END
+}
+
+int fi_surface_count_hits(fi_surface* h, long n, const float* origins, const float* directions, float t_min, float t_max, int limit,
+                          int* counts, int memory)
+{
+	FI_API_BEGIN
+	check_surface(h);
+	check_rays(n, origins, directions, t_min, t_max, counts, memory);
+	FI_REQUIRE(limit >= 1, FI_ERR_INVALID, "limit = %d", limit);
+	fi::ray_count(h->t, n, origins, directions, t_min, t_max, limit, counts, memory, nullptr);
+	FI_API_END
+}
+
+int fi_surface_contains(fi_surface* h, long n, const float* points, const float* direction, unsigned char* inside, int memory)
+{
+	FI_API_BEGIN
+	check_surface(h);
+	check_rays(n, points, points, 0.0f, INFINITY, inside, memory);
+	fi::ray_contains(h->t, n, points, direction, inside, memory, nullptr);
+	FI_API_END
+}
+
+int fi_surface_signed_distance(fi_surface* h, long n, const float* queries, float max_distance, float* distances,
+                               long long* primitives, float* closest, int memory)
+{
+	FI_API_BEGIN
+	check_surface(h);
+	check_nearest(n, queries, max_distance, distances, memory);
+	fi::ray_signed_query(h->t, n, queries, max_distance, distances, primitives, closest, memory, nullptr);
+	FI_API_END
+}
+
+int fi_surface_signed_distance_field(fi_surface* h, const int* sizes, float max_distance, float* out, long long* primitives,
+                                     int memory)
+{
+	FI_API_BEGIN
+	check_surface(h);
+	FI_REQUIRE(sizes != nullptr, FI_ERR_INVALID, "sizes is null");
+	for (int d = 0; d < h->t.D; ++d) { FI_REQUIRE(sizes[d] >= 1, FI_ERR_INVALID, "sizes[%d] = %d", d, sizes[d]); }
+	check_field_out(max_distance, out, memory);
+	fi::ray_signed_lattice(h->t, sizes, max_distance, out, primitives, memory, nullptr);
+	FI_API_END
+}
 
 int fi_redistance(fi_ctx* c, const float* field, float iso, int method, float max_distance, float* out, long long* primitives,
                   fi_mesh** mesh, int memory)

@@ -507,6 +507,29 @@ bool GpuLatticeField::redistance(std::vector<float>* out, float iso, bool dual, 
 	return true;
 }
 
+bool GpuLatticeField::raycast(const std::vector<float>& origins, const std::vector<float>& directions, std::vector<float>* t,
+                              float iso, bool dual, float t_max, std::vector<long long>* primitives) const
+{
+	const size_t D = sizes_.size();
+	if (!t || origins.size() != directions.size() || origins.size() % D != 0) {
+		warn("raycast");
+		return false;
+	}
+	const size_t n = origins.size() / D;
+	t->resize(n);
+	if (primitives) { primitives->resize(n); }
+	fi_mesh*    mesh    = nullptr;
+	fi_surface* surface = nullptr;
+	bool        ok      = (dual ? fi_dual_contour(ctx_, nullptr, nullptr, iso, FI_HOST, &mesh) : fi_iso_extract(ctx_, nullptr, iso, FI_HOST, &mesh)) == FI_OK;
+	ok = ok && fi_surface_from_mesh(&surface, mesh) == FI_OK;
+	ok = ok && (n == 0 || fi_surface_raycast(surface, static_cast<long>(n), origins.data(), directions.data(), 0.0f, t_max, t->data(),
+	                                         primitives ? primitives->data() : nullptr, nullptr, FI_HOST) == FI_OK);
+	if (!ok) { warn("raycast"); }
+	fi_surface_destroy(surface);
+	fi_mesh_destroy(mesh);
+	return ok;
+}
+
 std::unique_ptr<GpuLatticeField> gpu_sdf_from_points(const std::vector<int>& sizes, const Weights& weights,
                                                      int num_points, const float positions[], const float* normals,
                                                      const float* point_weights)

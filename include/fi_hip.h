@@ -764,6 +764,51 @@ int fi_surface_distance_field(fi_surface* surface, const int* sizes, float max_d
                               int memory);
 int fi_surface_destroy(fi_surface* surface);
 
+/* ---- rays against a surface: hits, crossing counts, containment, signed distances --------------
+ * The contract ("Rays"; tests/ray_reference.py restates it in numpy) is this project's own, fixed to the
+ * operation (no FMA contraction), over the structure fi_surface_create built:
+ *   - a ray is o + t d with t_min <= t <= t_max, both ends closed; d is not normalised and t is in units of d.  A ray with a
+ *     non-finite o or d, or d = 0: t = NaN, primitive -1, NaN barycentrics; count 0.  t_min > t_max or a NaN bound:
+ *     FI_ERR_INVALID (infinite bounds are fine);
+ *   - the projection (Woop, Benthin, Wald: Watertight Ray/Triangle Intersection, JCGT 2013): kz = the axis of the largest
+ *     |d|, the lowest on ties; kx, ky the next two in cyclic order, swapped when d[kz] < 0; Sx = d[kx] / d[kz],
+ *     Sy = d[ky] / d[kz], Sz = 1 / d[kz] in fp32 (|Sx|, |Sy| <= 1).  Per vertex in fp32: p = v - o,
+ *     X = p[kx] - Sx p[kz], Y = p[ky] - Sy p[kz], Z = Sz p[kz];
+ *   - the inside test is exact: U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax in fp64 from the fp32 X, Y (exact
+ *     products, so exact signs and zeros).  A triangle is a candidate when U, V, W are all >= 0 ("positive") or all <= 0,
+ *     and not all zero: a projected triangle of zero area (edge on, coincident vertices) is never hit;
+ *   - counted once: a candidate with a zero edge function is hit only if it owns that edge.  Edge B->C belongs to U, C->A to
+ *     V, A->B to W; (dx, dy) = end - start in (X, Y), negated when the triangle is not positive; owned when dy > 0, or dy = 0
+ *     and dx < 0.  A ray through a shared edge or vertex meets exactly one of the triangles around it on each sheet of the
+ *     surface (both or neither at a fold);
+ *   - t = fp32(((U Az + V Bz) + W Cz) / ((U + V) + W)), evaluated in fp64, then clamped into [min Z, max Z] of the three
+ *     vertices (t < min Z: min Z; t > max Z: max Z); a hit when t_min <= t <= t_max.  Barycentrics: fp32(V / det),
+ *     fp32(W / det) with det = (U + V) + W: the weights of b and c;
+ *   - 2-D: kz as above, kx the other axis; X = p[kx] - Sx p[kz], Z = Sz p[kz].  A segment (a, b) is crossed when
+ *     (Xa > 0) != (Xb > 0) (a shared vertex counts once); in fp64 s = Xa / (Xa - Xb), t = fp32(Za + s (Zb - Za)), clamped
+ *     into [min Z, max Z]; the barycentric is fp32(s), the weight of b;
+ *   - fi_surface_raycast: t = the smallest hit t in range and the smallest primitive index reaching it; no hit: +inf, -1,
+ *     NaN barycentrics.  primitives (long long[n]) and bary (float[n][ndim - 1]) may be NULL;
+ *   - fi_surface_count_hits: the hits in range, saturated at limit >= 1 (limit = 1 asks whether anything is in the way);
+ *   - fi_surface_contains: inside[i] = the parity (0 / 1) of the unsaturated count of the ray from points[i] along
+ *     `direction` (ndim floats on the host whatever `memory`; NULL: +x) over t in [0, +inf).  A mesh that is not closed gives
+ *     whatever the parity gives;
+ *   - fi_surface_signed_distance(_field): fi_surface_distance(_field)'s values, negated (-0.0f at distance 0, -inf beyond
+ *     max_distance) where fi_surface_contains holds along +x; a non-finite query keeps its NaN;
+ *   - results in input order; they depend neither on the launch shape nor on timing.
+ * Error codes follow fi_surface_distance: n = 0 is fine; n < 0, NULL required buffers, a bad window, limit < 1, a NaN or
+ * negative max_distance, a bad memory kind: FI_ERR_INVALID; n >= 2^31: FI_ERR_UNSUPPORTED. */
+int fi_surface_raycast(fi_surface* surface, long n, const float* origins, const float* directions, float t_min, float t_max,
+                       float* t, long long* primitives, float* bary, int memory);
+int fi_surface_count_hits(fi_surface* surface, long n, const float* origins, const float* directions, float t_min, float t_max,
+                          int limit, int* counts, int memory);
+int fi_surface_contains(fi_surface* surface, long n, const float* points, const float* direction, unsigned char* inside,
+                        int memory);
+int fi_surface_signed_distance(fi_surface* surface, long n, const float* queries, float max_distance, float* distances,
+                               long long* primitives, float* closest, int memory);
+int fi_surface_signed_distance_field(fi_surface* surface, const int* sizes, float max_distance, float* out,
+                                     long long* primitives, int memory);
+
 /* Redistancing: the signed distance of every lattice point (x fastest) to the field's own iso-surface f = iso -- the mesh of
  * fi_iso_extract (method FI_SURFACE_ISO) or of fi_dual_contour with central differences (FI_SURFACE_DUAL) -- searched as
  * fi_surface_distance_field does.  out = +distance where the point is outside by that producer's rule, -distance (a

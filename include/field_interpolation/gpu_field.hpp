@@ -142,6 +142,13 @@ public:
 	// max_distance.  The contract is include/fi_hip.h fi_redistance.  false: no solution yet, or the library refused the call.
 	bool redistance(std::vector<float>* out, float iso = 0, bool dual = false,
 	                float max_distance = std::numeric_limits<float>::infinity(), std::vector<long long>* primitives = nullptr) const;
+	// The closest hit of each ray origins[i] + t directions[i] (ndim floats each, directions not normalised, 0 <= t <= t_max)
+	// with the last solution's own iso-surface f = iso -- the mesh redistance() searches, made the same way: t per ray, +inf
+	// without a hit, NaN for a ray that is none.  primitives (optional): the primitive of that mesh each ray hits, or -1.
+	// The contract is include/fi_hip.h fi_surface_raycast.  false: no solution yet, or the library refused the call.
+	bool raycast(const std::vector<float>& origins, const std::vector<float>& directions, std::vector<float>* t, float iso = 0,
+	             bool dual = false, float t_max = std::numeric_limits<float>::infinity(),
+	             std::vector<long long>* primitives = nullptr) const;
 
 	// Iteratively reweighted least squares for data with gross errors: a plain solve, then up to options.rounds solves, each
 	// after the data points were reweighted by their residuals against the previous field (fi_solve_robust; every solve as
