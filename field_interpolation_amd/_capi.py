@@ -23,7 +23,7 @@ SYMBOLS = [
     "fi_group_solve_cg", "fi_group_apply_AtA_f64", "fi_group_true_residual", "fi_group_get_solution_f64", "fi_group_tile_pass", "fi_group_error_map",
     "fi_group_iso_extract", "fi_iso_extract", "fi_iso_extract_field", "fi_mesh_info", "fi_mesh_copy", "fi_mesh_destroy",
     "fi_dual_contour", "fi_dual_contour_field",
-    "fi_mesh_create", "fi_mesh_parts", "fi_mesh_measure", "fi_mesh_select",
+    "fi_mesh_create", "fi_mesh_parts", "fi_mesh_measure", "fi_mesh_select", "fi_mesh_simplify",
     "fi_group_sample", "fi_sample", "fi_sample_field",
     "fi_nearest", "fi_distance_field", "fi_points_create", "fi_points_nearest", "fi_points_distance_field", "fi_points_destroy",
     "fi_knn", "fi_points_knn", "fi_estimate_normals", "fi_points_estimate_normals",
@@ -158,6 +158,7 @@ def lib():
     L.fi_mesh_parts.argtypes = [vp, C.POINTER(C.c_long), vp, vp, C.c_int]
     L.fi_mesh_measure.argtypes = [vp, C.c_long, vp, C.POINTER(C.c_long)]
     L.fi_mesh_select.argtypes = [vp, C.c_long, vp, C.POINTER(vp)]
+    L.fi_mesh_simplify.argtypes = [vp, C.c_float, vp, C.c_int, vp, C.c_int, C.POINTER(vp)]
     L.fi_group_sample.argtypes = [vp, fp, C.c_long, fp, C.c_int, C.c_float, fp, fp]
     L.fi_sample.argtypes = [vp, fp, C.c_long, fp, C.c_int, C.c_float, fp, fp, C.c_int]
     L.fi_sample_field.argtypes = [fp, C.c_int, ip, C.c_long, fp, C.c_int, C.c_float, fp, fp, C.c_int]

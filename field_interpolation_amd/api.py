@@ -228,10 +228,70 @@ def keep_parts(parts, largest=None, min_size=0.0, min_primitives=0, closed=None)
     return mask
 
 
-def _finish_mesh(h, ndim, normals, largest, min_size, parts):
+FI_PLACEMENT = {"quadric": 0, "mean": 1}
+
+
+def _placement(placement):
+    if placement not in FI_PLACEMENT:
+        raise ValueError("placement is 'quadric' or 'mean'")
+    return FI_PLACEMENT[placement]
+
+
+def _handle_simplify(h, ndim, cell, origin=None, placement="quadric", vertex_map=None, memory=FI_HOST):
+    """The simplified mesh of a device mesh handle, as a new handle; vertex_map: a pointer to int32 per input vertex in
+    `memory`, or None."""
+    o = None
+    if origin is not None:
+        o = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(-1))
+        if len(o) != ndim:
+            raise ValueError("origin has one entry per axis")
+    out = C.c_void_p()
+    check(_capi.lib().fi_mesh_simplify(h, float(cell), None if o is None else C.c_void_p(o.ctypes.data), _placement(placement),
+                                       vertex_map, memory, C.byref(out)))
+    return out
+
+
+def _simplify_args(simplify):
+    """(cell, placement) of the extractors' `simplify` keyword: a cell, or a (cell, placement) pair"""
+    if isinstance(simplify, (tuple, list)):
+        if len(simplify) != 2:
+            raise ValueError("simplify is a cell or a (cell, placement) pair")
+        return float(simplify[0]), simplify[1]
+    return float(simplify), "quadric"
+
+
+def simplify_mesh(mesh, cell, origin=None, placement="quadric", vertex_map=False):
+    """`mesh` (an IsoMesh of numpy arrays, or of torch CUDA tensors; normals and keys may be None) made coarser on the device by
+    vertex clustering: the vertices in one cube of edge `cell` (the grid starts at `origin`, default 0) become one vertex,
+    placed at the minimum of the cluster's quadric error ("quadric": corners and edges survive) or at the cluster's mean
+    ("mean"); primitives that collapse and repeated primitives are dropped.  With a cell below the vertex spacing this welds
+    the coincident vertices of a triangle soup.  keys of the result: the clusters' cell keys, ascending (include/fi_hip.h
+    fi_mesh_simplify).  -> IsoMesh where `mesh` lives; vertex_map=True: -> (IsoMesh, int32 per input vertex: its output vertex
+    or -1)."""
+    h, ndim, _mem, like = _mesh_handle(mesh)
+    try:
+        vm, vptr, mem = None, None, FI_HOST
+        if vertex_map:
+            nv = int(mesh.vertices.shape[0])
+            if like is not None and like.is_cuda:
+                import torch
+                vm = torch.empty(nv, dtype=torch.int32, device=like.device)
+                vptr, mem = (C.c_void_p(vm.data_ptr()) if nv else None), FI_DEVICE
+            else:
+                vm = np.empty(nv, np.int32)
+                vptr = C.c_void_p(vm.ctypes.data) if nv else None
+        out = _handle_simplify(h, ndim, cell, origin, placement, vptr, mem)
+    finally:
+        _capi.lib().fi_mesh_destroy(h)
+    res = _take_mesh_like(out, ndim, mesh.normals is not None, like)
+    return (res, vm) if vertex_map else res
+
+
+def _finish_mesh(h, ndim, normals, largest, min_size, parts, simplify=None):
     """What the extractors return for a device mesh handle: the mesh, filtered on the device if largest / min_size ask for
-    it (label -> measure -> select, one copy at the end), and with parts=True the MeshParts of the mesh returned."""
-    if largest is None and min_size is None and not parts:
+    it (label -> measure -> select), then simplified on the device if `simplify` asks for it (a cell, or a (cell, placement)
+    pair), with one copy at the end, and with parts=True the MeshParts of the mesh returned."""
+    if largest is None and min_size is None and not parts and simplify is None:
         return _take_mesh(h, ndim, normals)
     try:
         if largest is not None or min_size is not None:
@@ -239,6 +299,11 @@ def _finish_mesh(h, ndim, normals, largest, min_size, parts):
             kept = _handle_select(h, keep)
             _capi.lib().fi_mesh_destroy(h)
             h = kept
+        if simplify is not None:
+            cell, placement = _simplify_args(simplify)
+            coarse = _handle_simplify(h, ndim, cell, None, placement)
+            _capi.lib().fi_mesh_destroy(h)
+            h = coarse
         described = _handle_parts(h, ndim) if parts else None
     except BaseException:
         _capi.lib().fi_mesh_destroy(h)
@@ -994,33 +1059,35 @@ class LatticeField:
                                           C.byref(st), _same_memory(kg, ko)))
         return out, om, {f: getattr(st, f) for f, _ in st._fields_}
 
-    def iso_surface(self, solution=None, iso=0.0, normals=True, largest=None, min_size=None, parts=False):
+    def iso_surface(self, solution=None, iso=0.0, normals=True, largest=None, min_size=None, parts=False, simplify=None):
         """The iso-contour (2-D) / iso-surface (3-D) f = iso of `solution` (this context's owned values, host or device) or,
         with None, of the last solve's solution where it lives on the device -- the step src/sdf_field.cpp:605-613 takes
         after the solve.  A slab context returns its piece (merge_meshes joins them).  -> IsoMesh
         largest = k / min_size = s: only the k largest connected parts / the parts of at least that area (2-D: length) are
         kept (keep_parts), chosen and cut out on the device before the one copy to the host; parts=True: -> (IsoMesh,
-        MeshParts of that mesh)."""
+        MeshParts of that mesh).  simplify = cell or (cell, placement): the mesh (after the selection, if any) is made
+        coarser on the device by simplify_mesh's vertex clustering before the copy; parts=True then describes that mesh."""
         h = C.c_void_p()
         if solution is None:
             check(_capi.lib().fi_iso_extract(self._h, None, float(iso), FI_HOST, C.byref(h)))
         else:
             s, mem, _keep = _buf(solution)
             check(_capi.lib().fi_iso_extract(self._h, s, float(iso), mem, C.byref(h)))
-        return _finish_mesh(h, len(self.sizes), normals, largest, min_size, parts)
+        return _finish_mesh(h, len(self.sizes), normals, largest, min_size, parts, simplify)
 
-    def dual_contour(self, solution=None, iso=0.0, gradients=None, normals=True, largest=None, min_size=None, parts=False):
+    def dual_contour(self, solution=None, iso=0.0, gradients=None, normals=True, largest=None, min_size=None, parts=False,
+                     simplify=None):
         """The dual contour (2-D: segments, 3-D: triangles) of `solution` (this context's owned values, host or device) or,
         with None, of the last solve's solution where it lives on the device: one vertex per crossed cell, fitted to the
         corner gradients so that sharp corners survive (include/fi_hip.h fi_dual_contour).  gradients: (num_owned, ndim)
         in the same memory as `solution`, or None for central differences of f - iso.  Undivided contexts only.  -> IsoMesh
-        (keys: the lattice index of each vertex's cell).  largest, min_size, parts: as iso_surface's."""
+        (keys: the lattice index of each vertex's cell).  largest, min_size, parts, simplify: as iso_surface's."""
         s, smem, _ks = _buf(solution)
         g, gmem, _kg = _buf(gradients)
         mem = _same_memory(smem, gmem)
         h = C.c_void_p()
         check(_capi.lib().fi_dual_contour(self._h, s, g, float(iso), mem, C.byref(h)))
-        return _finish_mesh(h, len(self.sizes), normals, largest, min_size, parts)
+        return _finish_mesh(h, len(self.sizes), normals, largest, min_size, parts, simplify)
 
     def sample(self, positions, solution=None, gradients=False, cubic=False, fill=float("nan")):
         """Values (n,) -- and with gradients=True also gradients (n, ndim) -- of `solution` (this context's owned values) or,
@@ -1475,26 +1542,27 @@ def upscale_field(field, small_sizes, large_sizes):
     return out
 
 
-def iso_surface(field, sizes, iso=0.0, normals=True, largest=None, min_size=None, parts=False):
+def iso_surface(field, sizes, iso=0.0, normals=True, largest=None, min_size=None, parts=False, simplify=None):
     """The iso-contour (2-D) / iso-surface (3-D) f = iso of a whole lattice field (numpy array or torch CUDA tensor, x
-    fastest), e.g. the output of upscale_field.  -> IsoMesh.  largest, min_size, parts: as LatticeField.iso_surface's."""
+    fastest), e.g. the output of upscale_field.  -> IsoMesh.  largest, min_size, parts, simplify: as LatticeField.iso_surface's."""
     src, mem, _keep = _buf(field)
     sz = (C.c_int * len(sizes))(*[int(s) for s in sizes])
     h = C.c_void_p()
     check(_capi.lib().fi_iso_extract_field(src, len(sizes), sz, float(iso), mem, C.byref(h)))
-    return _finish_mesh(h, len(sizes), normals, largest, min_size, parts)
+    return _finish_mesh(h, len(sizes), normals, largest, min_size, parts, simplify)
 
 
-def dual_contour(field, sizes, iso=0.0, gradients=None, normals=True, largest=None, min_size=None, parts=False):
+def dual_contour(field, sizes, iso=0.0, gradients=None, normals=True, largest=None, min_size=None, parts=False, simplify=None):
     """LatticeField.dual_contour of a whole lattice field (numpy array or torch CUDA tensor, x fastest); gradients:
-    (prod(sizes), ndim) in the same memory, or None.  -> IsoMesh.  largest, min_size, parts: as LatticeField.iso_surface's."""
+    (prod(sizes), ndim) in the same memory, or None.  -> IsoMesh.  largest, min_size, parts, simplify: as
+    LatticeField.iso_surface's."""
     src, mem, _keep = _buf(field)
     g, gmem, _kg = _buf(gradients)
     mem = _same_memory(mem, gmem)
     sz = (C.c_int * len(sizes))(*[int(s) for s in sizes])
     h = C.c_void_p()
     check(_capi.lib().fi_dual_contour_field(src, g, len(sizes), sz, float(iso), mem, C.byref(h)))
-    return _finish_mesh(h, len(sizes), normals, largest, min_size, parts)
+    return _finish_mesh(h, len(sizes), normals, largest, min_size, parts, simplify)
 
 
 def redistance(field, sizes, iso=0.0, method="iso", max_distance=math.inf):

@@ -12,6 +12,7 @@
 #include "fi_ray.h"
 #include "fi_robust.h"
 #include "fi_parts.h"
+#include "fi_simplify.h"
 
 #include <memory>
 
@@ -1283,6 +1284,13 @@ int fi_mesh_select(const fi_mesh* m, long num_parts, const unsigned char* keep, 
 	FI_API_END
 }
 
+// ---- mesh simplification (fi_simplify.hip) ----------------------------------------------------------
+int fi_mesh_simplify(const fi_mesh* m, float cell, const float* origin, int placement, int* vertex_map, int memory, fi_mesh** out)
+{
+	FI_API_BEGIN
+	fi::mesh_simplify(m, cell, origin, placement, vertex_map, memory, out);
+	FI_API_END
+}
 
 
 // ---- point queries (fi_sample.hip) --------------------------------------------------------------

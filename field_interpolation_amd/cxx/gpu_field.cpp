@@ -318,6 +318,42 @@ bool GpuLatticeField::dual_contour(float iso, std::vector<float>* vertices, std:
 
 static_assert(sizeof(MeshPart) == sizeof(fi_mesh_part), "MeshPart mirrors fi_mesh_part");
 
+// the sub-mesh of the parts keep_parts' rule (field_interpolation_amd/api.py) chooses: size >= min_size and, with largest >= 0,
+// the `largest` largest of those
+static bool select_by_rule(const fi_mesh* m, int largest, double min_size, fi_mesh** kept)
+{
+	long count = 0;
+	bool ok = fi_mesh_measure(m, 0, nullptr, &count) == FI_OK || count > 0;
+	std::vector<fi_mesh_part> rows(static_cast<size_t>(count));
+	ok = ok && fi_mesh_measure(m, count, rows.data(), &count) == FI_OK;
+	if (!ok) { return false; }
+	std::vector<long> order;
+	for (long c = 0; c < count; ++c) {
+		if (rows[static_cast<size_t>(c)].size >= min_size) { order.push_back(c); }
+	}
+	if (largest >= 0) {
+		std::stable_sort(order.begin(), order.end(),
+		                 [&](long a, long b) { return rows[static_cast<size_t>(a)].size > rows[static_cast<size_t>(b)].size; });
+		if (order.size() > static_cast<size_t>(largest)) { order.resize(static_cast<size_t>(largest)); }
+	}
+	std::vector<unsigned char> keep(static_cast<size_t>(count), 0);
+	for (long c : order) { keep[static_cast<size_t>(c)] = 1; }
+	return fi_mesh_select(m, count, keep.data(), kept) == FI_OK;
+}
+
+// the arrays of a device mesh, on the host
+static bool copy_mesh(const fi_mesh* m, size_t D, std::vector<float>* vertices, std::vector<int>* indices, std::vector<float>* normals)
+{
+	long nv = 0, np = 0;
+	int  vpp = 0;
+	if (fi_mesh_info(m, &nv, &np, &vpp) != FI_OK) { return false; }
+	if (vertices) { vertices->resize(D * static_cast<size_t>(nv)); }
+	if (normals) { normals->resize(D * static_cast<size_t>(nv)); }
+	if (indices) { indices->resize(static_cast<size_t>(vpp) * static_cast<size_t>(np)); }
+	return fi_mesh_copy(m, vertices ? vertices->data() : nullptr, normals ? normals->data() : nullptr, indices ? indices->data() : nullptr,
+	                    nullptr, FI_HOST) == FI_OK;
+}
+
 bool GpuLatticeField::iso_surface_parts(float iso, bool dual, int largest, double min_size, std::vector<float>* vertices,
                                         std::vector<int>* indices, std::vector<float>* normals, std::vector<MeshPart>* parts) const
 {
@@ -326,37 +362,10 @@ bool GpuLatticeField::iso_surface_parts(float iso, bool dual, int largest, doubl
 		warn("iso_surface_parts");
 		return false;
 	}
-	// the rows of every part, the mask by keep_parts' rule (field_interpolation_amd/api.py), the sub-mesh, its own rows
-	long count = 0;
-	bool ok = fi_mesh_measure(m, 0, nullptr, &count) == FI_OK || count > 0;
-	std::vector<fi_mesh_part> rows(static_cast<size_t>(count));
-	ok = ok && fi_mesh_measure(m, count, rows.data(), &count) == FI_OK;
+	// the rows of every part, the mask by keep_parts' rule, the sub-mesh, its own rows
 	fi_mesh* kept = nullptr;
-	if (ok) {
-		std::vector<long> order;
-		for (long c = 0; c < count; ++c) {
-			if (rows[static_cast<size_t>(c)].size >= min_size) { order.push_back(c); }
-		}
-		if (largest >= 0) {
-			std::stable_sort(order.begin(), order.end(),
-			                 [&](long a, long b) { return rows[static_cast<size_t>(a)].size > rows[static_cast<size_t>(b)].size; });
-			if (order.size() > static_cast<size_t>(largest)) { order.resize(static_cast<size_t>(largest)); }
-		}
-		std::vector<unsigned char> keep(static_cast<size_t>(count), 0);
-		for (long c : order) { keep[static_cast<size_t>(c)] = 1; }
-		ok = fi_mesh_select(m, count, keep.data(), &kept) == FI_OK;
-	}
-	long nv = 0, np = 0;
-	int  vpp = 0;
-	ok = ok && fi_mesh_info(kept, &nv, &np, &vpp) == FI_OK;
-	const size_t D = sizes_.size();
-	if (ok) {
-		if (vertices) { vertices->resize(D * static_cast<size_t>(nv)); }
-		if (normals) { normals->resize(D * static_cast<size_t>(nv)); }
-		if (indices) { indices->resize(static_cast<size_t>(vpp) * static_cast<size_t>(np)); }
-		ok = fi_mesh_copy(kept, vertices ? vertices->data() : nullptr, normals ? normals->data() : nullptr,
-		                  indices ? indices->data() : nullptr, nullptr, FI_HOST) == FI_OK;
-	}
+	bool     ok   = select_by_rule(m, largest, min_size, &kept);
+	ok = ok && copy_mesh(kept, sizes_.size(), vertices, indices, normals);
 	if (ok && parts) {
 		long left = 0;
 		ok = fi_mesh_measure(kept, 0, nullptr, &left) == FI_OK || left > 0;
@@ -364,6 +373,28 @@ bool GpuLatticeField::iso_surface_parts(float iso, bool dual, int largest, doubl
 		ok = ok && fi_mesh_measure(kept, left, reinterpret_cast<fi_mesh_part*>(parts->data()), &left) == FI_OK;
 	}
 	if (!ok) { warn("iso_surface_parts"); }
+	fi_mesh_destroy(kept);
+	fi_mesh_destroy(m);
+	return ok;
+}
+
+bool GpuLatticeField::iso_surface_simplified(float iso, bool dual, float cell, int placement, int largest, double min_size,
+                                             std::vector<float>* vertices, std::vector<int>* indices, std::vector<float>* normals) const
+{
+	fi_mesh* m = nullptr;
+	if ((dual ? fi_dual_contour(ctx_, nullptr, nullptr, iso, FI_HOST, &m) : fi_iso_extract(ctx_, nullptr, iso, FI_DEVICE, &m)) != FI_OK) {
+		warn("iso_surface_simplified");
+		return false;
+	}
+	// extract -> (the parts iso_surface_parts' rule keeps, if it is asked to drop any) -> simplify, one copy at the end
+	fi_mesh* kept   = nullptr;
+	fi_mesh* coarse = nullptr;
+	bool     ok     = true;
+	if (largest >= 0 || min_size > 0.0) { ok = select_by_rule(m, largest, min_size, &kept); }
+	ok = ok && fi_mesh_simplify(kept ? kept : m, cell, nullptr, placement, nullptr, FI_HOST, &coarse) == FI_OK;
+	ok = ok && copy_mesh(coarse, sizes_.size(), vertices, indices, normals);
+	if (!ok) { warn("iso_surface_simplified"); }
+	fi_mesh_destroy(coarse);
 	fi_mesh_destroy(kept);
 	fi_mesh_destroy(m);
 	return ok;

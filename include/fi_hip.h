@@ -586,6 +586,48 @@ int fi_mesh_parts(const fi_mesh* m, long* num_parts, int* vertex_labels, int* pr
 int fi_mesh_measure(const fi_mesh* m, long capacity, fi_mesh_part* parts, long* num_parts);
 int fi_mesh_select(const fi_mesh* m, long num_parts, const unsigned char* keep, fi_mesh** out);
 
+/* ---- mesh simplification: vertex clustering with quadric placement ------------------------------
+ * Makes a device mesh coarser -- or, with a cell below the vertex spacing, welds the coincident vertices of a triangle soup
+ * -- without the mesh leaving the device: the vertices of one cube of a uniform grid become one vertex (Rossignac-Borrel),
+ * placed at the minimum of the cluster's quadric error function (Lindstrom 2000) or at the cluster's mean.  Any fi_mesh, 2-D
+ * segments or 3-D triangles, with or without normals.  The contract (tests/simplify_reference.py is its
+ * definition in numpy):
+ *   - cells: only USED vertices take part (those some primitive references).  c_a = floorf((p_a - o_a) / cell) in fp32, one
+ *     rounding per operation; origin: ndim floats on the HOST, NULL = 0.  A non-finite coordinate of a used vertex, or
+ *     |c_a| >= 2^20: FI_ERR_INVALID and no mesh.  The cell key is sum_a (c_a + 2^20) << 21 a (int64); the clusters are the
+ *     distinct keys, ascending; the cell centre g = o + (c + 1/2) cell in fp64;
+ *   - primitives: indices replaced by cluster numbers; a primitive with two equal indices is dropped; of the primitives with
+ *     the same ORIENTED tuple (3-D: the triple rotated so that its smallest index comes first; 2-D: the ordered pair) only
+ *     the lowest-numbered stays -- a primitive and its reverse are different tuples and both stay.  Survivors keep their
+ *     input order and winding;
+ *   - output vertices: the clusters a surviving primitive references, in ascending key order; their keys are the output
+ *     mesh's keys (ascending).  vertex_map (optional, int32 per input vertex, in `memory`): the output vertex of every input
+ *     vertex; -1 for an unused vertex and for a cluster that did not survive;
+ *   - placement: fp64 from the fp32 coordinates, relative to g (p' = p - g), one rounding per operation, every sum serial in
+ *     ascending order from 0.  mean = (sum of the cluster's used vertices in ascending vertex number) / their number.
+ *     FI_SIMPLIFY_MEAN: x' = mean.  FI_SIMPLIFY_QUADRIC: every input primitive adds to each DISTINCT cluster among its
+ *     vertices, in ascending primitive number, A += n n^T and b += n (n . a'), with n = (b' - a') x (c' - a') in 3-D
+ *     (n_x = u_y w_z - u_z w_y, ...; n . a' = (n_x a'_x + n_y a'_y) + n_z a'_z) and n = (-e_y, e_x), e = b' - a', in 2-D, not
+ *     normalised (squared-area weights; zero-area primitives add zeros).  r = b - A mean, row i as b_i - ((A_i0 mean_0 +
+ *     A_i1 mean_1) + A_i2 mean_2).  The eigenpairs (lambda_i, v_i) of A come from the cyclic Jacobi iteration of
+ *     fi_estimate_normals (6 sweeps over the pairs (0,1), (0,2), (1,2), no early exit; v_i the columns); x' = mean, then for
+ *     i = 0, 1, 2 with lambda_max > 0 and lambda_i > 1e-3 lambda_max: x' += v_i ((v_i . r) / lambda_i).  A non-finite x', or
+ *     any |x'_a| > cell, falls back to the mean: a vertex may leave its cell by half a cell, not more.
+ *     Position = (float)(g + x');
+ *   - normals, if the mesh has them: the fp64 sum of the members' normals in ascending vertex number, divided by its length
+ *     (sqrt of the squares summed in axis order), cast to fp32; a zero sum gives zeros.  A mesh without normals gives a mesh
+ *     without normals (fi_mesh_copy of it refuses a normals buffer);
+ *   - an empty mesh, or one whose primitives all collapse: an empty mesh and FI_OK (vertex_map all -1).  cell NaN or <= 0, a
+ *     bad placement, a bad memory kind, a NULL mesh or out: FI_ERR_INVALID.
+ * No floating-point atomics and no atomics in the outputs: a repeated call returns the same bytes.  A cell that swallows most
+ * of a mesh makes one thread sum most of it: correct, and slow.  Not offered: a target count (bisect on cell), edge-collapse
+ * decimation, boundary or topology preservation (clustering may pinch a thin sheet: fi_mesh_measure of the result reports
+ * it as irregular edges), slab groups (merge the pieces first), 1-D. */
+#define FI_SIMPLIFY_QUADRIC 0
+#define FI_SIMPLIFY_MEAN    1
+int fi_mesh_simplify(const fi_mesh* m, float cell, const float* origin, int placement, int* vertex_map, int memory,
+                     fi_mesh** out);
+
 /* ---- point queries: values and gradients at arbitrary positions --------------------------------
  * The contract ("Point queries") is this project's own:
  *   - positions: n points of ndim fp32 values, interleaved, in global lattice coordinates (x fastest, as fi_add_points);

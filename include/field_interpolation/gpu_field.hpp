@@ -100,6 +100,14 @@ public:
 	bool iso_surface_parts(float iso, bool dual, int largest, double min_size, std::vector<float>* vertices, std::vector<int>* indices,
 	                       std::vector<float>* normals = nullptr, std::vector<MeshPart>* parts = nullptr) const;
 
+	// iso_surface_parts' mesh (largest < 0 and min_size <= 0: every part) made coarser on the device before the one copy to the
+	// host: the vertices in one cube of edge `cell` (lattice units, the grid starts at 0) become one vertex, placed at the minimum
+	// of the cluster's quadric error (placement 0, FI_SIMPLIFY_QUADRIC: corners and edges survive) or at its mean (1,
+	// FI_SIMPLIFY_MEAN); collapsed and repeated primitives are dropped.  The contract is include/fi_hip.h fi_mesh_simplify.
+	// false: no solution yet, or the library refused the call.
+	bool iso_surface_simplified(float iso, bool dual, float cell, int placement, int largest, double min_size, std::vector<float>* vertices,
+	                            std::vector<int>* indices, std::vector<float>* normals = nullptr) const;
+
 	// Values (and, if asked, gradients: ndim floats per point) of the last solution at `positions` (ndim floats per point,
 	// global lattice coordinates, x fastest), sampled where the solution lives on the device: multilinear, or Catmull-Rom
 	// with cubic = true; points outside the lattice get NaN.  The contract is include/fi_hip.h fi_sample.  false: no
