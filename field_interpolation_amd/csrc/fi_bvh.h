@@ -232,12 +232,9 @@ void build(BvhIndex& t, const Items& it, int64_t n, hipStream_t st)
 	                   keys.as<uint64_t>(), vals.as<uint32_t>());
 	FI_HIP_TRY(hipGetLastError());
 	const int end_bit = D * morton_bits(D) + 1;
-	size_t    tb      = 0;
-	FI_HIP_TRY(prim::sort_pairs_u64(nullptr, tb, keys.as<uint64_t>(), keys2.as<uint64_t>(), vals.as<uint32_t>(), vals2.as<uint32_t>(),
-	                                static_cast<size_t>(n), 0, end_bit, st));
-	tmp.alloc(tb);
-	FI_HIP_TRY(prim::sort_pairs_u64(tmp.p, tb, keys.as<uint64_t>(), keys2.as<uint64_t>(), vals.as<uint32_t>(), vals2.as<uint32_t>(),
-	                                static_cast<size_t>(n), 0, end_bit, st));
+	tmp.alloc(prim::sort_bytes(n, 0, end_bit));
+	prim::sort_u64(keys.as<uint64_t>(), keys2.as<uint64_t>(), vals.as<uint32_t>(), vals2.as<uint32_t>(), n, 0, end_bit,
+	               prim::Scratch{tmp.p, tmp.bytes}, st);
 	uint32_t c[2] = {0, 0};
 	FI_HIP_TRY(hipMemcpyAsync(c, cnt.as<uint32_t>() + 2 * kBoundsBlocks, sizeof(c), hipMemcpyDeviceToHost, st));
 	FI_HIP_TRY(hipStreamSynchronize(st));

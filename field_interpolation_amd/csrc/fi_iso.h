@@ -5,6 +5,7 @@
 #include <mutex>
 
 #include "fi_internal.h"
+#include "fi_prim.h"
 
 namespace fi {
 struct MeshParts;  // the labelling of a mesh's connected parts and what hangs on it (fi_parts.hip)
@@ -73,6 +74,61 @@ __device__ inline uint32_t block_scan(uint32_t x, uint32_t* total)
 	}
 	*total = all;
 	return pre + inc - x;
+}
+
+// the scanned offsets an extractor's emit kernels start from: where work group b's vertices (sv[b]) and primitives (sp[b])
+// begin, entry nb of each the total.  They live in `scan` and die with it.
+struct ExtractScans {
+	DevBuf          wg, scan, tot, tmp;
+	const uint64_t *sv = nullptr, *sp = nullptr;
+};
+
+// The host sequence of an extractor up to its emit kernels, over nb work groups.  count(wg_v, wg_p, flag) launches the unit's
+// count kernel (the groups' vertex and primitive counts, uint32[nb + 1] each with a trailing zero; the non-finite flag),
+// totals(sv, sp, flag, tot) its totals kernel (tot: uint64[3] = vertices, primitives, flag).  Between them the two exclusive
+// scans (rocPRIM); behind them the one read-back, the checks, m's sizes and its arrays.  False: the mesh is empty.
+// (The four temporaries are allocations of their own, made where fi_iso.hip and fi_dual.hip made them before they shared this,
+// the workspace behind the count kernel's launch.  With all of them made first, as one block or as four, the extraction took
+// the same time but fi_mesh_copy of the finished mesh to the host took 1.7 ms instead of 0.65 and fi.iso_surface 25 ms instead
+// of 16; why is not understood.  profiles/iso_surface.md has the variants and their figures.)
+template <int D, class Count, class Totals>
+bool extract_sizes(int64_t nb, hipStream_t st, fi_mesh* m, ExtractScans& s, Count&& count, Totals&& totals)
+{
+	FI_REQUIRE(nb < (int64_t(1) << 31), FI_ERR_UNSUPPORTED, "lattice too large");
+	s.wg.alloc(sizeof(uint32_t) * (2 * (nb + 1) + 1));
+	s.scan.alloc(sizeof(uint64_t) * 2 * (nb + 1));
+	s.tot.alloc(sizeof(uint64_t) * 3);
+	uint32_t* wg_v = s.wg.as<uint32_t>();
+	uint32_t* wg_p = wg_v + (nb + 1);
+	uint32_t* flag = wg_p + (nb + 1);
+	uint64_t* sv   = s.scan.as<uint64_t>();
+	uint64_t* sp   = sv + (nb + 1);
+	uint64_t* tot  = s.tot.as<uint64_t>();
+	FI_HIP_TRY(hipMemsetAsync(s.wg.p, 0, s.wg.bytes, st));  // (the trailing zero of each total list, the flag)
+	count(wg_v, wg_p, flag);
+	FI_HIP_TRY(hipGetLastError());
+	s.tmp.alloc(prim::scan_bytes<uint64_t>(nb + 1));  // (here, behind the count kernel's launch: see above)
+	const prim::Scratch tmp{s.tmp.p, s.tmp.bytes};
+	prim::scan_u32(wg_v, sv, nb + 1, tmp, st);
+	prim::scan_u32(wg_p, sp, nb + 1, tmp, st);
+	totals(sv, sp, flag, tot);
+	FI_HIP_TRY(hipGetLastError());
+	uint64_t h[3] = {0, 0, 0};
+	FI_HIP_TRY(hipMemcpyAsync(h, tot, sizeof(h), hipMemcpyDeviceToHost, st));
+	FI_HIP_TRY(hipStreamSynchronize(st));
+	FI_REQUIRE(h[2] == 0, FI_ERR_INVALID, "the field holds a non-finite value");
+	FI_REQUIRE(h[0] < (uint64_t(1) << 31), FI_ERR_UNSUPPORTED, "the mesh would have %llu vertices (int32 indices)",
+	           static_cast<unsigned long long>(h[0]));
+	m->nv = static_cast<int64_t>(h[0]);
+	m->np = static_cast<int64_t>(h[1]);
+	if (m->nv == 0) { return false; }
+	m->pos.alloc(sizeof(float) * D * m->nv);
+	m->nrm.alloc(sizeof(float) * D * m->nv);
+	m->key.alloc(sizeof(int64_t) * m->nv);
+	m->idx.alloc(sizeof(int) * D * (m->np > 0 ? m->np : 1));
+	s.sv = sv;
+	s.sp = sp;
+	return true;
 }
 
 }  // namespace fi

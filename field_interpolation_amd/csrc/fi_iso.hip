@@ -282,45 +282,21 @@ void run_view(const IsoView& v0, hipStream_t st, fi_mesh* m)
 	if (empty) { return; }
 	v.npts = v.plane * (v.chi - v.clo + 1);
 	const int64_t nb = (v.npts + kIsoThreads - 1) / kIsoThreads;
-	FI_REQUIRE(nb < (int64_t(1) << 31), FI_ERR_UNSUPPORTED, "lattice too large");
-	DevBuf wg, scan, base, tot, tmp;
-	wg.alloc(sizeof(uint32_t) * (2 * (nb + 1) + 1));
-	scan.alloc(sizeof(uint64_t) * 2 * (nb + 1));
-	tot.alloc(sizeof(uint64_t) * 3);
-	uint32_t* wg_v = wg.as<uint32_t>();
-	uint32_t* wg_p = wg_v + (nb + 1);
-	uint32_t* flag = wg_p + (nb + 1);
-	uint64_t* sv = scan.as<uint64_t>();
-	uint64_t* sp = sv + (nb + 1);
-	FI_HIP_TRY(hipMemsetAsync(wg.p, 0, wg.bytes, st));  // (the trailing zero of each total list, the flag)
-	hipLaunchKernelGGL((k_iso_count<D>), dim3(static_cast<unsigned>(nb)), dim3(kIsoThreads), 0, st, v, wg_v, wg_p, flag);
-	FI_HIP_TRY(hipGetLastError());
-	size_t tb = 0;
-	FI_HIP_TRY(prim::exclusive_sum(nullptr, tb, wg_v, sv, nb + 1, st));
-	tmp.alloc(tb);
-	FI_HIP_TRY(prim::exclusive_sum(tmp.p, tb, wg_v, sv, nb + 1, st));
-	FI_HIP_TRY(prim::exclusive_sum(tmp.p, tb, wg_p, sp, nb + 1, st));
-	hipLaunchKernelGGL(k_iso_totals, dim3(1), dim3(1), 0, st, sv, sp, flag, nb, tot.as<uint64_t>());
-	FI_HIP_TRY(hipGetLastError());
-	uint64_t h[3] = {0, 0, 0};
-	FI_HIP_TRY(hipMemcpyAsync(h, tot.p, sizeof(h), hipMemcpyDeviceToHost, st));
-	FI_HIP_TRY(hipStreamSynchronize(st));
-	FI_REQUIRE(h[2] == 0, FI_ERR_INVALID, "the field holds a non-finite value");
-	FI_REQUIRE(h[0] < (uint64_t(1) << 31), FI_ERR_UNSUPPORTED, "the mesh would have %llu vertices (int32 indices)",
-	           static_cast<unsigned long long>(h[0]));
-	m->nv = static_cast<int64_t>(h[0]);
-	m->np = static_cast<int64_t>(h[1]);
-	if (m->nv == 0) { return; }
+	const dim3    groups(static_cast<unsigned>(nb)), threads(kIsoThreads);
+	ExtractScans  s;
+	const bool    any = extract_sizes<D>(
+		nb, st, m, s,
+		[&](uint32_t* wg_v, uint32_t* wg_p, uint32_t* flag) { hipLaunchKernelGGL((k_iso_count<D>), groups, threads, 0, st, v, wg_v, wg_p, flag); },
+		[&](const uint64_t* sv, const uint64_t* sp, const uint32_t* flag, uint64_t* tot) {
+			hipLaunchKernelGGL(k_iso_totals, dim3(1), dim3(1), 0, st, sv, sp, flag, nb, tot);
+		});
+	if (!any) { return; }
+	DevBuf base;
 	base.alloc(sizeof(uint32_t) * v.npts);
-	m->pos.alloc(sizeof(float) * D * m->nv);
-	m->nrm.alloc(sizeof(float) * D * m->nv);
-	m->key.alloc(sizeof(int64_t) * m->nv);
-	m->idx.alloc(sizeof(int) * D * (m->np > 0 ? m->np : 1));
-	hipLaunchKernelGGL((k_iso_vertices<D>), dim3(static_cast<unsigned>(nb)), dim3(kIsoThreads), 0, st, v, sv, base.as<uint32_t>(),
-	                   m->pos.as<float>(), m->nrm.as<float>(), m->key.as<int64_t>());
+	hipLaunchKernelGGL((k_iso_vertices<D>), groups, threads, 0, st, v, s.sv, base.as<uint32_t>(), m->pos.as<float>(), m->nrm.as<float>(),
+	                   m->key.as<int64_t>());
 	FI_HIP_TRY(hipGetLastError());
-	hipLaunchKernelGGL((k_iso_prims<D>), dim3(static_cast<unsigned>(nb)), dim3(kIsoThreads), 0, st, v, sp, base.as<uint32_t>(),
-	                   m->idx.as<int>());
+	hipLaunchKernelGGL((k_iso_prims<D>), groups, threads, 0, st, v, s.sp, base.as<uint32_t>(), m->idx.as<int>());
 	FI_HIP_TRY(hipGetLastError());
 	FI_HIP_TRY(hipStreamSynchronize(st));
 }

@@ -14,14 +14,13 @@
 #include "fi_solver_internal.h"
 #include "fi_knn.h"
 #include "fi_bvh.h"
+#include "fi_jacobi.h"
 
 namespace fi {
 
 namespace {
 
 using namespace bvh;
-
-constexpr int kSweeps = 6;
 
 __device__ inline bool pair_less(float s, uint32_t j, float s1, uint32_t j1) { return s < s1 || (s == s1 && j < j1); }
 
@@ -132,35 +131,6 @@ __global__ __launch_bounds__(kThreads) void k_knn_query(KnnArgs a)
 
 // ---- normals ----------------------------------------------------------------------------------------------------------
 
-// one Jacobi rotation of the pair (P, Q) of the symmetric matrix A (both triangles kept) and the vector matrix V (columns)
-template <int D, int P, int Q>
-__device__ inline void rotate(double (&A)[D][D], double (&V)[D][D])
-{
-	const double apq = A[P][Q];
-	if (apq == 0.0) { return; }
-	const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
-	const double t     = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-	const double c     = 1.0 / sqrt(t * t + 1.0);
-	const double s     = t * c;
-	const double tap   = t * apq;
-	A[P][P] = A[P][P] - tap;
-	A[Q][Q] = A[Q][Q] + tap;
-	A[P][Q] = A[Q][P] = 0.0;
-#pragma unroll
-	for (int r = 0; r < D; ++r) {
-		if (r == P || r == Q) { continue; }
-		const double arp = A[r][P], arq = A[r][Q];
-		A[r][P] = A[P][r] = c * arp - s * arq;
-		A[r][Q] = A[Q][r] = s * arp + c * arq;
-	}
-#pragma unroll
-	for (int r = 0; r < D; ++r) {
-		const double vrp = V[r][P], vrq = V[r][Q];
-		V[r][P] = c * vrp - s * vrq;
-		V[r][Q] = s * vrp + c * vrq;
-	}
-}
-
 enum { kOrientNone = 0, kOrientViewpoints = 1, kOrientDirections = 2 };
 
 struct NormalArgs {
@@ -247,15 +217,7 @@ __global__ __launch_bounds__(kThreads) void k_knn_normals(NormalArgs a)
 		for (int y = 0; y < x; ++y) { A[x][y] = A[y][x]; }
 	}
 
-	// a fixed number of sweeps, no early exit: the result is defined by the count alone
-#pragma unroll 1
-	for (int sweep = 0; sweep < kSweeps; ++sweep) {
-		rotate<D, 0, 1>(A, V);
-		if constexpr (D == 3) {
-			rotate<D, 0, 2>(A, V);
-			rotate<D, 1, 2>(A, V);
-		}
-	}
+	jacobi::jacobi_sweeps<D>(A, V);
 
 	// the column of the smallest diagonal entry (the lowest on a tie) ...
 	int    col  = 0;

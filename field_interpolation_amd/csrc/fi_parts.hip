@@ -24,6 +24,7 @@
 #include "fi_parts.h"
 #include "fi_prim.h"
 
+#include <algorithm>
 #include <memory>
 
 namespace fi {
@@ -483,31 +484,10 @@ __global__ __launch_bounds__(kThreads) void k_parts_gather_prims(int64_t np, con
 
 // ---- host side --------------------------------------------------------------------------------------------------------
 
-inline dim3 grid(int64_t n) { return dim3(static_cast<unsigned>(blocks_for(n > 0 ? n : 1))); }
+using namespace prim;  // Arena, Scratch, scan_u32, sort_u64, read_u32, bits_for, grid
+static_assert(kThreads == kGridThreads, "grid() counts work groups of kThreads");
 
-// out = the exclusive prefix sums of n uint32
-void scan_u32(const uint32_t* in, uint32_t* out, int64_t n, DevBuf& tmp, hipStream_t st)
-{
-	size_t tb = 0;
-	FI_HIP_TRY(prim::exclusive_sum(nullptr, tb, in, out, static_cast<size_t>(n), st));
-	tmp.alloc(tb);
-	FI_HIP_TRY(prim::exclusive_sum(tmp.p, tb, in, out, static_cast<size_t>(n), st));
-}
-
-uint32_t read_u32(const uint32_t* dev, hipStream_t st)
-{
-	uint32_t h = 0;
-	FI_HIP_TRY(hipMemcpyAsync(&h, dev, sizeof(h), hipMemcpyDeviceToHost, st));
-	FI_HIP_TRY(hipStreamSynchronize(st));
-	return h;
-}
-
-int bits_for(int64_t count)  // key bits that tell `count` values apart (at least one)
-{
-	int b = 1;
-	while ((int64_t(1) << b) < count) { ++b; }
-	return b;
-}
+// Each call lays its temporaries out in one block (fi_arena.h), the zeroed ones first, the primitives' workspace last.
 
 template <int D>
 void label(const fi_mesh* m, MeshParts* P, hipStream_t st)
@@ -517,26 +497,29 @@ void label(const fi_mesh* m, MeshParts* P, hipStream_t st)
 	P->plabel.alloc(sizeof(int) * (np > 0 ? np : 1));
 	P->count = 0;
 	if (nv == 0) { return; }
-	DevBuf parent, used, flag, number, tmp;
-	parent.alloc(sizeof(uint32_t) * nv);
-	used.alloc(sizeof(uint32_t) * (nv + 1));
-	flag.alloc(sizeof(uint32_t) * (nv + 1));
-	number.alloc(sizeof(uint32_t) * (nv + 1));
-	hipLaunchKernelGGL(k_parts_start, grid(nv + 1), dim3(kThreads), 0, st, nv, parent.as<uint32_t>(), used.as<uint32_t>());
-	if (np > 0) {
-		hipLaunchKernelGGL(k_parts_union<D>, grid(np), dim3(kThreads), 0, st, np, m->idx.as<int>(), parent.as<uint32_t>(), used.as<uint32_t>());
-	}
-	hipLaunchKernelGGL(k_parts_jump, grid(nv), dim3(kThreads), 0, st, nv, parent.as<uint32_t>());
-	hipLaunchKernelGGL(k_parts_roots, grid(nv + 1), dim3(kThreads), 0, st, nv, parent.as<uint32_t>(), used.as<uint32_t>(), flag.as<uint32_t>());
+	uint32_t *parent = nullptr, *used = nullptr, *flag = nullptr, *number = nullptr;
+	Scratch   tmp;
+	tmp.bytes = scan_bytes(nv + 1);
+	DevBuf block;
+	arena_alloc(block, [&](Arena& a) {
+		parent = a.take<uint32_t>(nv);
+		used   = a.take<uint32_t>(nv + 1);
+		flag   = a.take<uint32_t>(nv + 1);
+		number = a.take<uint32_t>(nv + 1);
+		tmp.p  = a.take<char>(static_cast<int64_t>(tmp.bytes));
+	});
+	hipLaunchKernelGGL(k_parts_start, grid(nv + 1), dim3(kThreads), 0, st, nv, parent, used);
+	if (np > 0) { hipLaunchKernelGGL(k_parts_union<D>, grid(np), dim3(kThreads), 0, st, np, m->idx.as<int>(), parent, used); }
+	hipLaunchKernelGGL(k_parts_jump, grid(nv), dim3(kThreads), 0, st, nv, parent);
+	hipLaunchKernelGGL(k_parts_roots, grid(nv + 1), dim3(kThreads), 0, st, nv, parent, used, flag);
 	FI_HIP_TRY(hipGetLastError());
-	scan_u32(flag.as<uint32_t>(), number.as<uint32_t>(), nv + 1, tmp, st);
-	hipLaunchKernelGGL(k_parts_label_vertices, grid(nv), dim3(kThreads), 0, st, nv, parent.as<uint32_t>(), used.as<uint32_t>(),
-	                   number.as<uint32_t>(), P->vlabel.as<int>());
+	scan_u32(flag, number, nv + 1, tmp, st);
+	hipLaunchKernelGGL(k_parts_label_vertices, grid(nv), dim3(kThreads), 0, st, nv, parent, used, number, P->vlabel.as<int>());
 	if (np > 0) {
 		hipLaunchKernelGGL(k_parts_label_prims<D>, grid(np), dim3(kThreads), 0, st, np, m->idx.as<int>(), P->vlabel.as<int>(), P->plabel.as<int>());
 	}
 	FI_HIP_TRY(hipGetLastError());
-	P->count = read_u32(number.as<uint32_t>() + nv, st);  // (synchronises: the temporaries die here)
+	P->count = read_u32(number + nv, st);  // (synchronises: the temporaries die here)
 }
 
 template <int D>
@@ -548,39 +531,55 @@ void measure(const fi_mesh* m, MeshParts* P, hipStream_t st)
 		P->measured = true;
 		return;
 	}
-	const int* vlabel = P->vlabel.as<int>();
-	const int* plabel = P->plabel.as<int>();
-	const int* idx    = m->idx.as<int>();
-	DevBuf     table, tmp;
-	table.alloc(sizeof(unsigned long long) * kCols * C);
-	FI_HIP_TRY(hipMemsetAsync(table.p, 0, table.bytes, st));
-	unsigned long long* T = table.as<unsigned long long>();
+	const int*    vlabel = P->vlabel.as<int>();
+	const int*    plabel = P->plabel.as<int>();
+	const int*    idx    = m->idx.as<int>();
+	const int64_t ne     = D == 3 ? 3 * np : 0;  // half-edges
+	FI_REQUIRE(ne < (int64_t(1) << 32), FI_ERR_UNSUPPORTED, "the mesh has %lld half-edges", static_cast<long long>(ne));
+
+	unsigned long long* T = nullptr;  // the counter table
+	uint32_t *          deg = nullptr, *order0 = nullptr, *order = nullptr, *first = nullptr, *nchunks = nullptr, *chunk_first = nullptr;
+	uint64_t *          key = nullptr, *key2 = nullptr, *skey = nullptr, *skey2 = nullptr;
+	uint8_t *           dir = nullptr, *dir2 = nullptr;
+	fi_mesh_part*       rows   = nullptr;
+	size_t              zeroed = 0;
+	Scratch             tmp;
+	tmp.bytes = std::max(sort_bytes(np, 0, bits_for(C)), scan_bytes(C + 1));
+	if (D == 3) { tmp.bytes = std::max(tmp.bytes, sort_bytes<uint8_t>(ne, 0, 64)); }
+	DevBuf block;
+	arena_alloc(block, [&](Arena& a) {
+		T      = a.take<unsigned long long>(kCols * C);
+		deg    = D == 2 ? a.take<uint32_t>(2 * nv) : nullptr;
+		zeroed = a.bytes();
+		if (D == 3) {
+			key  = a.take<uint64_t>(ne);
+			key2 = a.take<uint64_t>(ne);
+			dir  = a.take<uint8_t>(ne);
+			dir2 = a.take<uint8_t>(ne);
+		}
+		skey        = a.take<uint64_t>(np);
+		skey2       = a.take<uint64_t>(np);
+		order0      = a.take<uint32_t>(np);
+		order       = a.take<uint32_t>(np);
+		first       = a.take<uint32_t>(C + 1);
+		nchunks     = a.take<uint32_t>(C + 1);
+		chunk_first = a.take<uint32_t>(C + 1);
+		rows        = a.take<fi_mesh_part>(C);
+		tmp.p       = a.take<char>(static_cast<int64_t>(tmp.bytes));
+	});
+	FI_HIP_TRY(hipMemsetAsync(block.p, 0, zeroed, st));
 
 	// the counts
-	DevBuf key, key2, dir, dir2, deg;
 	hipLaunchKernelGGL(k_parts_count_prims, grid(np), dim3(kThreads), 0, st, np, plabel, T);
 	if (D == 3) {
-		const int64_t ne = 3 * np;
-		FI_REQUIRE(ne < (int64_t(1) << 32), FI_ERR_UNSUPPORTED, "the mesh has %lld half-edges", static_cast<long long>(ne));
-		key.alloc(sizeof(uint64_t) * ne);
-		key2.alloc(sizeof(uint64_t) * ne);
-		dir.alloc(ne);
-		dir2.alloc(ne);
-		hipLaunchKernelGGL(k_parts_halfedges, grid(np), dim3(kThreads), 0, st, np, idx, key.as<uint64_t>(), dir.as<uint8_t>());
+		hipLaunchKernelGGL(k_parts_halfedges, grid(np), dim3(kThreads), 0, st, np, idx, key, dir);
 		FI_HIP_TRY(hipGetLastError());
-		size_t tb = 0;
-		FI_HIP_TRY(prim::sort_pairs_u64(nullptr, tb, key.as<uint64_t>(), key2.as<uint64_t>(), dir.as<uint8_t>(), dir2.as<uint8_t>(),
-		                                static_cast<size_t>(ne), 0, 64, st));
-		tmp.alloc(tb);
-		FI_HIP_TRY(prim::sort_pairs_u64(tmp.p, tb, key.as<uint64_t>(), key2.as<uint64_t>(), dir.as<uint8_t>(), dir2.as<uint8_t>(),
-		                                static_cast<size_t>(ne), 0, 64, st));
-		hipLaunchKernelGGL(k_parts_classify, grid(ne), dim3(kThreads), 0, st, ne, key2.as<uint64_t>(), dir2.as<uint8_t>(), vlabel, T);
+		sort_u64(key, key2, dir, dir2, ne, 0, 64, tmp, st);
+		hipLaunchKernelGGL(k_parts_classify, grid(ne), dim3(kThreads), 0, st, ne, key2, dir2, vlabel, T);
 		hipLaunchKernelGGL(k_parts_count_vertices, grid(nv), dim3(kThreads), 0, st, nv, vlabel, static_cast<const uint32_t*>(nullptr),
 		                   static_cast<const uint32_t*>(nullptr), T);
 	} else {
-		deg.alloc(sizeof(uint32_t) * 2 * nv);
-		FI_HIP_TRY(hipMemsetAsync(deg.p, 0, deg.bytes, st));
-		uint32_t* din  = deg.as<uint32_t>();
+		uint32_t* din  = deg;
 		uint32_t* dout = din + nv;
 		hipLaunchKernelGGL(k_parts_degrees, grid(np), dim3(kThreads), 0, st, np, idx, plabel, din, dout, T);
 		hipLaunchKernelGGL(k_parts_count_vertices, grid(nv), dim3(kThreads), 0, st, nv, vlabel, static_cast<const uint32_t*>(din),
@@ -589,37 +588,21 @@ void measure(const fi_mesh* m, MeshParts* P, hipStream_t st)
 	FI_HIP_TRY(hipGetLastError());
 
 	// the measures: primitive numbers by part, chunks of a part, a part's chunks in order
-	DevBuf skey, skey2, order0, order, first, nchunks, chunk_first, partial, rows;
-	skey.alloc(sizeof(uint64_t) * np);
-	skey2.alloc(sizeof(uint64_t) * np);
-	order0.alloc(sizeof(uint32_t) * np);
-	order.alloc(sizeof(uint32_t) * np);
-	first.alloc(sizeof(uint32_t) * (C + 1));
-	nchunks.alloc(sizeof(uint32_t) * (C + 1));
-	chunk_first.alloc(sizeof(uint32_t) * (C + 1));
-	hipLaunchKernelGGL(k_parts_sort_keys, grid(np), dim3(kThreads), 0, st, np, plabel, skey.as<uint64_t>(), order0.as<uint32_t>());
+	hipLaunchKernelGGL(k_parts_sort_keys, grid(np), dim3(kThreads), 0, st, np, plabel, skey, order0);
 	FI_HIP_TRY(hipGetLastError());
-	{
-		size_t tb = 0;
-		FI_HIP_TRY(prim::sort_pairs_u64(nullptr, tb, skey.as<uint64_t>(), skey2.as<uint64_t>(), order0.as<uint32_t>(), order.as<uint32_t>(),
-		                                static_cast<size_t>(np), 0, bits_for(C), st));
-		tmp.alloc(tb);
-		FI_HIP_TRY(prim::sort_pairs_u64(tmp.p, tb, skey.as<uint64_t>(), skey2.as<uint64_t>(), order0.as<uint32_t>(), order.as<uint32_t>(),
-		                                static_cast<size_t>(np), 0, bits_for(C), st));
-	}
-	hipLaunchKernelGGL(k_parts_first, grid(np + 1), dim3(kThreads), 0, st, np, C, skey2.as<uint64_t>(), first.as<uint32_t>());
-	hipLaunchKernelGGL(k_parts_chunk_counts, grid(C + 1), dim3(kThreads), 0, st, C, first.as<uint32_t>(), nchunks.as<uint32_t>());
+	sort_u64(skey, skey2, order0, order, np, 0, bits_for(C), tmp, st);
+	hipLaunchKernelGGL(k_parts_first, grid(np + 1), dim3(kThreads), 0, st, np, C, skey2, first);
+	hipLaunchKernelGGL(k_parts_chunk_counts, grid(C + 1), dim3(kThreads), 0, st, C, first, nchunks);
 	FI_HIP_TRY(hipGetLastError());
-	scan_u32(nchunks.as<uint32_t>(), chunk_first.as<uint32_t>(), C + 1, tmp, st);
-	const uint32_t total = read_u32(chunk_first.as<uint32_t>() + C, st);
+	scan_u32(nchunks, chunk_first, C + 1, tmp, st);
+	const uint32_t total = read_u32(chunk_first + C, st);
+	DevBuf         partial;  // (its size is known only now)
 	partial.alloc(sizeof(ChunkPartial) * total);
-	rows.alloc(sizeof(fi_mesh_part) * C);
-	hipLaunchKernelGGL(k_parts_chunks<D>, dim3(total), dim3(kChunk), 0, st, C, first.as<uint32_t>(), chunk_first.as<uint32_t>(),
-	                   order.as<uint32_t>(), idx, m->pos.as<float>(), partial.as<ChunkPartial>());
-	hipLaunchKernelGGL(k_parts_rows, grid(C), dim3(kThreads), 0, st, C, chunk_first.as<uint32_t>(), partial.as<ChunkPartial>(), T,
-	                   rows.as<fi_mesh_part>());
+	hipLaunchKernelGGL(k_parts_chunks<D>, dim3(total), dim3(kChunk), 0, st, C, first, chunk_first, order, idx, m->pos.as<float>(),
+	                   partial.as<ChunkPartial>());
+	hipLaunchKernelGGL(k_parts_rows, grid(C), dim3(kThreads), 0, st, C, chunk_first, partial.as<ChunkPartial>(), T, rows);
 	FI_HIP_TRY(hipGetLastError());
-	FI_HIP_TRY(hipMemcpyAsync(P->rows.data(), rows.p, sizeof(fi_mesh_part) * C, hipMemcpyDeviceToHost, st));
+	FI_HIP_TRY(hipMemcpyAsync(P->rows.data(), rows, sizeof(fi_mesh_part) * C, hipMemcpyDeviceToHost, st));
 	FI_HIP_TRY(hipStreamSynchronize(st));
 	P->measured = true;
 }
@@ -650,29 +633,34 @@ template <int D>
 void select(const fi_mesh* m, const MeshParts* P, const uint8_t* keep, fi_mesh* o, hipStream_t st)
 {
 	const int64_t nv = m->nv, np = m->np;
-	DevBuf vflag, pflag, vto, pto, tmp;
-	vflag.alloc(sizeof(uint32_t) * (nv + 1));
-	pflag.alloc(sizeof(uint32_t) * (np + 1));
-	vto.alloc(sizeof(uint32_t) * (nv + 1));
-	pto.alloc(sizeof(uint32_t) * (np + 1));
-	hipLaunchKernelGGL(k_parts_keep_flags, grid(nv + 1), dim3(kThreads), 0, st, nv, P->vlabel.as<int>(), keep, vflag.as<uint32_t>());
-	hipLaunchKernelGGL(k_parts_keep_flags, grid(np + 1), dim3(kThreads), 0, st, np, P->plabel.as<int>(), keep, pflag.as<uint32_t>());
+	uint32_t *vflag = nullptr, *pflag = nullptr, *vto = nullptr, *pto = nullptr;
+	Scratch   tmp;
+	tmp.bytes = scan_bytes(std::max(nv, np) + 1);
+	DevBuf block;
+	arena_alloc(block, [&](Arena& a) {
+		vflag = a.take<uint32_t>(nv + 1);
+		pflag = a.take<uint32_t>(np + 1);
+		vto   = a.take<uint32_t>(nv + 1);
+		pto   = a.take<uint32_t>(np + 1);
+		tmp.p = a.take<char>(static_cast<int64_t>(tmp.bytes));
+	});
+	hipLaunchKernelGGL(k_parts_keep_flags, grid(nv + 1), dim3(kThreads), 0, st, nv, P->vlabel.as<int>(), keep, vflag);
+	hipLaunchKernelGGL(k_parts_keep_flags, grid(np + 1), dim3(kThreads), 0, st, np, P->plabel.as<int>(), keep, pflag);
 	FI_HIP_TRY(hipGetLastError());
-	scan_u32(vflag.as<uint32_t>(), vto.as<uint32_t>(), nv + 1, tmp, st);
-	scan_u32(pflag.as<uint32_t>(), pto.as<uint32_t>(), np + 1, tmp, st);
-	o->nv = read_u32(vto.as<uint32_t>() + nv, st);
-	o->np = read_u32(pto.as<uint32_t>() + np, st);
+	scan_u32(vflag, vto, nv + 1, tmp, st);
+	scan_u32(pflag, pto, np + 1, tmp, st);
+	o->nv = read_u32(vto + nv, st);
+	o->np = read_u32(pto + np, st);
 	if (o->nv == 0) { return; }
 	o->pos.alloc(sizeof(float) * D * o->nv);
 	if (m->has_normals) { o->nrm.alloc(sizeof(float) * D * o->nv); }
 	o->key.alloc(sizeof(int64_t) * o->nv);
 	o->idx.alloc(sizeof(int) * D * (o->np > 0 ? o->np : 1));
-	hipLaunchKernelGGL(k_parts_gather_vertices<D>, grid(nv), dim3(kThreads), 0, st, nv, vflag.as<uint32_t>(), vto.as<uint32_t>(),
-	                   m->pos.as<float>(), m->has_normals ? m->nrm.as<float>() : nullptr, m->key.as<long long>(), o->pos.as<float>(),
-	                   o->nrm.as<float>(), o->key.as<long long>());
+	hipLaunchKernelGGL(k_parts_gather_vertices<D>, grid(nv), dim3(kThreads), 0, st, nv, vflag, vto, m->pos.as<float>(),
+	                   m->has_normals ? m->nrm.as<float>() : nullptr, m->key.as<long long>(), o->pos.as<float>(), o->nrm.as<float>(),
+	                   o->key.as<long long>());
 	if (np > 0) {
-		hipLaunchKernelGGL(k_parts_gather_prims<D>, grid(np), dim3(kThreads), 0, st, np, pflag.as<uint32_t>(), pto.as<uint32_t>(),
-		                   vto.as<uint32_t>(), m->idx.as<int>(), o->idx.as<int>());
+		hipLaunchKernelGGL(k_parts_gather_prims<D>, grid(np), dim3(kThreads), 0, st, np, pflag, pto, vto, m->idx.as<int>(), o->idx.as<int>());
 	}
 	FI_HIP_TRY(hipGetLastError());
 	FI_HIP_TRY(hipStreamSynchronize(st));

@@ -1,6 +1,7 @@
 // fi_prim.h -- the device-wide primitives of the assembly (scans, run-length encoding, selection, 64-bit
 // pair sorts) straight on rocPRIM, ROCm's own primitive library (rounds 1-4 went through hipCUB, the CUB-shaped layer over
-// it).  Same call shape as the library's: a first call with a null workspace returns the bytes it wants.
+// it).  Same call shape as the library's: a first call with a null workspace returns the bytes it wants.  Below them the
+// host side the mesh units share: a call's temporaries as pieces of one block, the size-then-run pairs around the sorts and scans.
 #pragma once
 
 #include <cstring>
@@ -8,6 +9,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "fi_arena.h"
 #include "fi_internal.h"
 
 namespace fi {
@@ -51,6 +53,84 @@ inline hipError_t sort_pairs_u64(void* tmp, size_t& bytes, const uint64_t* keys_
 	return rocprim::radix_sort_pairs<detail::onesweep64>(tmp, bytes, keys_in, keys_out, values_in, values_out, static_cast<unsigned int>(n),
 	                                                     static_cast<unsigned int>(begin_bit), static_cast<unsigned int>(end_bit), st);
 }
+
+// ---- the host side of a unit built on these: one arena (fi_arena.h) for a call's temporaries, a piece of it as workspace ---
+
+// the primitives' workspace: a piece of the arena sized (scan_bytes, sort_bytes) for the call's largest sort and scan
+struct Scratch {
+	void*  p     = nullptr;
+	size_t bytes = 0;
+};
+
+// lay_out(arena) takes a call's pieces: run once for their size, then over `block` allocated to that size
+template <class F>
+inline void arena_alloc(DevBuf& block, F&& lay_out)
+{
+	Arena sizing(nullptr);
+	lay_out(sizing);
+	block.alloc(sizing.bytes());
+	Arena arena(block.p);
+	lay_out(arena);
+}
+
+template <typename Out = uint32_t>
+inline size_t scan_bytes(int64_t n)
+{
+	size_t tb = 0;
+	FI_HIP_TRY(exclusive_sum(nullptr, tb, static_cast<const uint32_t*>(nullptr), static_cast<Out*>(nullptr), static_cast<size_t>(n), nullptr));
+	return tb;
+}
+
+// out = the exclusive prefix sums of n uint32
+template <typename Out>
+inline void scan_u32(const uint32_t* in, Out* out, int64_t n, const Scratch& tmp, hipStream_t st)
+{
+	size_t tb = 0;
+	FI_HIP_TRY(exclusive_sum(nullptr, tb, in, out, static_cast<size_t>(n), st));
+	DevBuf more;  // (should the library want more for fewer items or bits than the sizing pass asked about)
+	if (tb > tmp.bytes) { more.alloc(tb); }
+	FI_HIP_TRY(exclusive_sum(more.p ? more.p : tmp.p, tb, in, out, static_cast<size_t>(n), st));
+}
+
+template <typename V = uint32_t>
+inline size_t sort_bytes(int64_t n, int begin_bit, int end_bit)
+{
+	size_t tb = 0;
+	FI_HIP_TRY(sort_pairs_u64(nullptr, tb, static_cast<const uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr), static_cast<const V*>(nullptr),
+	                          static_cast<V*>(nullptr), static_cast<size_t>(n), begin_bit, end_bit, nullptr));
+	return tb;
+}
+
+// (kout, vout) = the pairs (kin, vin) in ascending order of key bits [begin_bit, end_bit), stable
+template <typename V>
+inline void sort_u64(const uint64_t* kin, uint64_t* kout, const V* vin, V* vout, int64_t n, int begin_bit, int end_bit, const Scratch& tmp,
+                     hipStream_t st)
+{
+	size_t tb = 0;
+	FI_HIP_TRY(sort_pairs_u64(nullptr, tb, kin, kout, vin, vout, static_cast<size_t>(n), begin_bit, end_bit, st));
+	DevBuf more;
+	if (tb > tmp.bytes) { more.alloc(tb); }
+	FI_HIP_TRY(sort_pairs_u64(more.p ? more.p : tmp.p, tb, kin, kout, vin, vout, static_cast<size_t>(n), begin_bit, end_bit, st));
+}
+
+inline uint32_t read_u32(const uint32_t* dev, hipStream_t st)
+{
+	uint32_t h = 0;
+	FI_HIP_TRY(hipMemcpyAsync(&h, dev, sizeof(h), hipMemcpyDeviceToHost, st));
+	FI_HIP_TRY(hipStreamSynchronize(st));
+	return h;
+}
+
+inline int bits_for(int64_t count)  // key bits that tell `count` values apart (at least one)
+{
+	int b = 1;
+	while ((int64_t(1) << b) < count) { ++b; }
+	return b;
+}
+
+// one thread per item in work groups of kGridThreads (the kThreads of the units that launch with it), at least one group
+constexpr int kGridThreads = 256;
+inline dim3   grid(int64_t n) { return dim3(static_cast<unsigned>(((n > 0 ? n : 1) + kGridThreads - 1) / kGridThreads)); }
 
 }  // namespace prim
 }  // namespace fi

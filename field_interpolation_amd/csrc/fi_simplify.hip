@@ -15,14 +15,15 @@
 //              primitive's keep flag.  Kept primitives flag their clusters; two scans number what stays.
 //   placement  QUADRIC: (cluster, primitive) pairs, one per distinct cluster of a primitive, sorted by cluster (stable: a
 //              cluster's primitives ascend).  One thread per surviving cluster walks its vertex run (mean, normal sum) and
-//              its primitive run (A, b), solves the 3 x 3 (2 x 2) system by the Jacobi iteration of fi_knn.hip, and writes
+//              its primitive run (A, b), solves the 3 x 3 (2 x 2) system by the Jacobi iteration of fi_jacobi.h, and writes
 //              the cluster's position and normal.  Neighbouring clusters are neighbours in x: their gathers share lines.
 //   gather     surviving clusters and primitives to their scanned places, indices remapped; the vertex map.
 // No floating-point atomics, no atomics writing an output, one read-back per size the host needs, one device allocation for
-// every temporary of a call.
+// every temporary of a call (fi_arena.h; the host helpers around the sorts and scans are fi_prim.h's).
 #include "fi_solver_internal.h"
 #include "fi_simplify.h"
 #include "fi_prim.h"
+#include "fi_jacobi.h"
 
 #include <algorithm>
 #include <memory>
@@ -31,7 +32,6 @@ namespace fi {
 namespace {
 
 constexpr int      kCellBias    = 1 << 20;  // |cell coordinate| < 2^20: 21 bits an axis
-constexpr int      kSweeps      = 6;        // of the Jacobi iteration: fi_knn.hip's, tests/normals_reference.py's SWEEPS
 constexpr double   kRankCut     = 1e-3;     // eigenvalues <= kRankCut * the largest take no part in the minimiser
 constexpr uint32_t kErrNonFinite = 1u, kErrRange = 2u;
 
@@ -215,36 +215,6 @@ __global__ __launch_bounds__(kThreads) void k_simp_pair_first(int64_t n, int64_t
 	if (s == 0 || key[s - 1] != k) { first[k] = static_cast<uint32_t>(s); }
 }
 
-// one Jacobi rotation of the pair (P, Q) of the symmetric matrix A (both triangles kept) and the vector matrix V (columns):
-// fi_knn.hip's, operation for operation
-template <int D, int P, int Q>
-__device__ inline void rotate(double (&A)[D][D], double (&V)[D][D])
-{
-	const double apq = A[P][Q];
-	if (apq == 0.0) { return; }
-	const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
-	const double t     = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-	const double c     = 1.0 / sqrt(t * t + 1.0);
-	const double s     = t * c;
-	const double tap   = t * apq;
-	A[P][P] = A[P][P] - tap;
-	A[Q][Q] = A[Q][Q] + tap;
-	A[P][Q] = A[Q][P] = 0.0;
-#pragma unroll
-	for (int r = 0; r < D; ++r) {
-		if (r == P || r == Q) { continue; }
-		const double arp = A[r][P], arq = A[r][Q];
-		A[r][P] = A[P][r] = c * arp - s * arq;
-		A[r][Q] = A[Q][r] = s * arp + c * arq;
-	}
-#pragma unroll
-	for (int r = 0; r < D; ++r) {
-		const double vrp = V[r][P], vrq = V[r][Q];
-		V[r][P] = c * vrp - s * vrq;
-		V[r][Q] = s * vrp + c * vrq;
-	}
-}
-
 struct PlaceArgs {
 	int64_t          nc;
 	Grid             g;
@@ -351,15 +321,7 @@ __global__ __launch_bounds__(kThreads) void k_simp_place(PlaceArgs a)
 			for (int j = 1; j < D; ++j) { t = t + A[i][j] * mean[j]; }
 			r[i] = b[i] - t;
 		}
-		// a fixed number of sweeps, no early exit: the result is defined by the count alone
-#pragma unroll 1
-		for (int sweep = 0; sweep < kSweeps; ++sweep) {
-			rotate<D, 0, 1>(A, V);
-			if constexpr (D == 3) {
-				rotate<D, 0, 2>(A, V);
-				rotate<D, 1, 2>(A, V);
-			}
-		}
+		jacobi::jacobi_sweeps<D>(A, V);
 		double lmax = A[0][0];
 #pragma unroll
 		for (int i = 1; i < D; ++i) { lmax = A[i][i] > lmax ? A[i][i] : lmax; }
@@ -437,81 +399,8 @@ __global__ __launch_bounds__(kThreads) void k_simp_vertex_map(int64_t nv, const 
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
 
-inline dim3 grid(int64_t n) { return dim3(static_cast<unsigned>(blocks_for(n > 0 ? n : 1))); }
-
-// Every temporary of a call is a piece of one block: a call makes some thirty of them, and thirty device allocations and
-// releases cost several times what its kernels do (profiles/simplify.md).  A first pass with no block adds the sizes up.
-class Arena {
-	char*  base_;
-	size_t used_ = 0;
-
-public:
-	explicit Arena(void* base) : base_(static_cast<char*>(base)) {}
-	template <typename T>
-	T* take(int64_t count)
-	{
-		T* p = base_ ? reinterpret_cast<T*>(base_ + used_) : nullptr;
-		used_ += (sizeof(T) * static_cast<size_t>(count > 0 ? count : 1) + 255) & ~size_t(255);
-		return p;
-	}
-	size_t bytes() const { return used_; }
-};
-
-// the primitives' workspace: a piece of the arena sized for the call's largest sort and scan
-struct Scratch {
-	void*  p     = nullptr;
-	size_t bytes = 0;
-};
-
-void scan_u32(const uint32_t* in, uint32_t* out, int64_t n, const Scratch& tmp, hipStream_t st)
-{
-	size_t tb = 0;
-	FI_HIP_TRY(prim::exclusive_sum(nullptr, tb, in, out, static_cast<size_t>(n), st));
-	DevBuf more;  // (should the library want more for fewer items or bits than the sizing pass asked about)
-	if (tb > tmp.bytes) { more.alloc(tb); }
-	FI_HIP_TRY(prim::exclusive_sum(more.p ? more.p : tmp.p, tb, in, out, static_cast<size_t>(n), st));
-}
-
-void sort_u64(const uint64_t* kin, uint64_t* kout, const uint32_t* vin, uint32_t* vout, int64_t n, int end_bit, const Scratch& tmp,
-              hipStream_t st)
-{
-	size_t tb = 0;
-	FI_HIP_TRY(prim::sort_pairs_u64(nullptr, tb, kin, kout, vin, vout, static_cast<size_t>(n), 0, end_bit, st));
-	DevBuf more;
-	if (tb > tmp.bytes) { more.alloc(tb); }
-	FI_HIP_TRY(prim::sort_pairs_u64(more.p ? more.p : tmp.p, tb, kin, kout, vin, vout, static_cast<size_t>(n), 0, end_bit, st));
-}
-
-size_t scan_bytes(int64_t n)
-{
-	size_t tb = 0;
-	FI_HIP_TRY(prim::exclusive_sum(nullptr, tb, static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), static_cast<size_t>(n), nullptr));
-	return tb;
-}
-
-size_t sort_bytes(int64_t n, int end_bit)
-{
-	size_t tb = 0;
-	FI_HIP_TRY(prim::sort_pairs_u64(nullptr, tb, static_cast<const uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr),
-	                                static_cast<const uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), static_cast<size_t>(n), 0, end_bit,
-	                                nullptr));
-	return tb;
-}
-
-uint32_t read_u32(const uint32_t* dev, hipStream_t st)
-{
-	uint32_t h = 0;
-	FI_HIP_TRY(hipMemcpyAsync(&h, dev, sizeof(h), hipMemcpyDeviceToHost, st));
-	FI_HIP_TRY(hipStreamSynchronize(st));
-	return h;
-}
-
-int bits_for(int64_t count)  // key bits that tell `count` values apart (at least one)
-{
-	int b = 1;
-	while ((int64_t(1) << b) < count) { ++b; }
-	return b;
-}
+using namespace prim;  // Arena, Scratch, scan_u32, sort_u64, read_u32, bits_for, grid
+static_assert(kThreads == kGridThreads, "grid() counts work groups of kThreads");
 
 // the temporaries of a call; what depends on the number of clusters has room for one cluster per vertex
 struct Work {
@@ -579,22 +468,18 @@ void simplify(const fi_mesh* m, const Grid& g, bool quadric, int* dmap, fi_mesh*
 	FI_REQUIRE(np * D < (int64_t(1) << 32), FI_ERR_UNSUPPORTED, "the mesh has %lld primitive corners", static_cast<long long>(np * D));
 
 	// the workspace of the largest primitive call, then everything in one block
-	size_t tmp_bytes = std::max(sort_bytes(nv, 21 * D + 1), std::max(sort_bytes(np, 2 * vbits), scan_bytes(std::max(nv, np) + 1)));
-	if (quadric) { tmp_bytes = std::max(tmp_bytes, sort_bytes(np * D, bits_for(nv + 1))); }
-	Work  w{};
-	Arena sizing(nullptr);
-	lay_out<D>(sizing, nv, np, quadric, nrm != nullptr, tmp_bytes, w);
+	size_t tmp_bytes = std::max(sort_bytes(nv, 0, 21 * D + 1), std::max(sort_bytes(np, 0, 2 * vbits), scan_bytes(std::max(nv, np) + 1)));
+	if (quadric) { tmp_bytes = std::max(tmp_bytes, sort_bytes(np * D, 0, bits_for(nv + 1))); }
+	Work   w{};
 	DevBuf block;
-	block.alloc(sizing.bytes());
-	Arena arena(block.p);
-	lay_out<D>(arena, nv, np, quadric, nrm != nullptr, tmp_bytes, w);
+	arena_alloc(block, [&](Arena& a) { lay_out<D>(a, nv, np, quadric, nrm != nullptr, tmp_bytes, w); });
 	FI_HIP_TRY(hipMemsetAsync(block.p, 0, w.zeroed, st));
 
 	// clusters
 	hipLaunchKernelGGL(k_simp_mark, grid(np * D), dim3(kThreads), 0, st, np * D, idx, w.used);
 	hipLaunchKernelGGL(k_simp_keys<D>, grid(nv), dim3(kThreads), 0, st, nv, pos, w.used, g, sentinel, w.key, w.val, w.err);
 	FI_HIP_TRY(hipGetLastError());
-	sort_u64(w.key, w.key2, w.val, w.vorder, nv, 21 * D + 1, w.tmp, st);
+	sort_u64(w.key, w.key2, w.val, w.vorder, nv, 0, 21 * D + 1, w.tmp, st);
 	hipLaunchKernelGGL(k_simp_heads, grid(nv + 1), dim3(kThreads), 0, st, nv, w.key2, sentinel, w.head);
 	FI_HIP_TRY(hipGetLastError());
 	scan_u32(w.head, w.number, nv + 1, w.tmp, st);
@@ -610,10 +495,10 @@ void simplify(const fi_mesh* m, const Grid& g, bool quadric, int* dmap, fi_mesh*
 	const int cbits = bits_for(nc);
 	hipLaunchKernelGGL(k_simp_tuple_low<D>, grid(np), dim3(kThreads), 0, st, np, cbits, idx, w.vcl, w.tkey, w.tval);
 	FI_HIP_TRY(hipGetLastError());
-	sort_u64(w.tkey, w.tkey2, w.tval, w.tval2, np, D == 3 ? 2 * cbits : cbits, w.tmp, st);
+	sort_u64(w.tkey, w.tkey2, w.tval, w.tval2, np, 0, D == 3 ? 2 * cbits : cbits, w.tmp, st);
 	hipLaunchKernelGGL(k_simp_tuple_high<D>, grid(np), dim3(kThreads), 0, st, np, w.tval2, idx, w.vcl, w.tkey);
 	FI_HIP_TRY(hipGetLastError());
-	sort_u64(w.tkey, w.tkey2, w.tval2, w.tval, np, cbits, w.tmp, st);
+	sort_u64(w.tkey, w.tkey2, w.tval2, w.tval, np, 0, cbits, w.tmp, st);
 	hipLaunchKernelGGL(k_simp_keep<D>, grid(np), dim3(kThreads), 0, st, np, w.tval, idx, w.vcl, w.keep);
 	hipLaunchKernelGGL(k_simp_cluster_flags<D>, grid(np), dim3(kThreads), 0, st, np, w.keep, idx, w.vcl, w.cused);
 	FI_HIP_TRY(hipGetLastError());
@@ -637,7 +522,7 @@ void simplify(const fi_mesh* m, const Grid& g, bool quadric, int* dmap, fi_mesh*
 		const int64_t n = np * D;
 		hipLaunchKernelGGL(k_simp_pairs<D>, grid(np), dim3(kThreads), 0, st, np, nc, idx, w.vcl, w.pkey, w.pval);
 		FI_HIP_TRY(hipGetLastError());
-		sort_u64(w.pkey, w.pkey2, w.pval, w.porder, n, bits_for(nc + 1), w.tmp, st);
+		sort_u64(w.pkey, w.pkey2, w.pval, w.porder, n, 0, bits_for(nc + 1), w.tmp, st);
 		hipLaunchKernelGGL(k_simp_pair_first, grid(n + 1), dim3(kThreads), 0, st, n, nc, w.pkey2, w.pfirst);
 		FI_HIP_TRY(hipGetLastError());
 	}
