@@ -325,7 +325,8 @@ __global__ __launch_bounds__(kThreads) void k_dot(int64_t n, const T* __restrict
 	if (threadIdx.x == 0) { partial[blockIdx.x] = out[0]; }
 }
 
-// p = z + beta p
+// p = z + beta p; the first direction of a solve (or of a restart) is z itself: what p holds then -- the last solve's direction,
+// the argument of fi_apply_AtA_f64, possibly not finite -- is not read (0 * NaN is NaN)
 template <typename T>
 __global__ __launch_bounds__(kThreads) void k_mg_direction(int64_t n, const CgScalars* __restrict__ sc,
                                                             const T* __restrict__ z, T* __restrict__ p, int first)
@@ -333,7 +334,7 @@ __global__ __launch_bounds__(kThreads) void k_mg_direction(int64_t n, const CgSc
 	const T beta = first ? T(0) : static_cast<T>(sc->beta);
 	for (int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; i < n;
 	     i += static_cast<int64_t>(gridDim.x) * kThreads) {
-		p[i] = z[i] + beta * p[i];
+		p[i] = first ? z[i] : z[i] + beta * p[i];
 	}
 }
 
@@ -413,7 +414,8 @@ __global__ __launch_bounds__(kThreads) void k_mg_direction_mixed(int64_t n, cons
 	const int64_t piece = ((n + gridDim.x - 1) / gridDim.x + kThreads - 1) / kThreads * kThreads;  // (contiguous pieces: k_mg_step_mixed)
 	const int64_t i0 = static_cast<int64_t>(blockIdx.x) * piece, i1 = i0 + piece < n ? i0 + piece : n;
 	for (int64_t i = i0 + threadIdx.x; i < i1; i += kThreads) {
-		stv<NT>(s * static_cast<double>(ldv<NT>(z32 + i)) + beta * ldv<NT>(p + i), p + i);
+		const double zi = s * static_cast<double>(ldv<NT>(z32 + i));
+		stv<NT>(first ? zi : zi + beta * ldv<NT>(p + i), p + i);  // (first: p is not read, see k_mg_direction)
 	}
 }
 

@@ -497,7 +497,8 @@ def test_border_prior_is_refused_on_a_slab(fi):
 def test_memory_of_destroyed_contexts_is_reused(fi, monkeypatch):
     """fi_memory_pool: the blocks of a destroyed context serve the next one (same answers, bit for bit -- a pooled block
     is handed out only after the device-wide synchronisation of fi_ctx_destroy, and every buffer is written before it is
-    read); FI_NO_POOL frees them instead; trimming empties the pool."""
+    read); FI_NO_POOL frees them instead; trimming empties the pool.
+    (The same problem three times: a stale block holds the right numbers.  tests/test_gpu_history.py pollutes the history.)"""
     import gc
     sizes = [48, 40, 36]
     rng = np.random.default_rng(8)
