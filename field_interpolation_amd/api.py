@@ -287,11 +287,66 @@ def simplify_mesh(mesh, cell, origin=None, placement="quadric", vertex_map=False
     return (res, vm) if vertex_map else res
 
 
-def _finish_mesh(h, ndim, normals, largest, min_size, parts, simplify=None):
+FI_BOUNDARY = {"fixed": 0, "slide": 1, "free": 2}
+FI_SMOOTH_NORMALS = {"recompute": 0, "keep": 1}
+
+
+def _handle_smooth(h, iterations=10, lam=0.5, mu=-0.53, boundary="fixed", max_move=None, normals="recompute"):
+    """The smoothed mesh of a device mesh handle, as a new handle (smooth_mesh's keywords)."""
+    if boundary not in FI_BOUNDARY:
+        raise ValueError("boundary is 'fixed', 'slide' or 'free'")
+    if normals not in FI_SMOOTH_NORMALS:
+        raise ValueError("normals is 'recompute' or 'keep'")
+    opt = _capi.FiSmoothOptions(int(iterations), float(lam), float(mu), FI_BOUNDARY[boundary],
+                                0.0 if max_move is None else float(max_move), FI_SMOOTH_NORMALS[normals])
+    out = C.c_void_p()
+    check(_capi.lib().fi_mesh_smooth(h, C.byref(opt), C.byref(out)))
+    return out
+
+
+def _smooth_args(smooth):
+    """smooth_mesh's keywords of the extractors' `smooth` keyword: an iteration count, or a dict of them"""
+    if isinstance(smooth, dict):
+        return dict(smooth)
+    return {"iterations": int(smooth)}
+
+
+def smooth_mesh(mesh, iterations=10, lam=0.5, mu=-0.53, boundary="fixed", max_move=None, normals="recompute"):
+    """`mesh` (an IsoMesh of numpy arrays, or of torch CUDA tensors; normals and keys may be None) made smoother on the device
+    by Taubin's fairing with uniform weights: `iterations` times, every vertex moves towards the average of its neighbours
+    by the factor lam and then by the factor mu (negative: it undoes the shrinking of the first step; mu = 0 is plain
+    Laplacian smoothing).  boundary: "fixed" (the vertices of open edges stay), "slide" (they are faired along the rim) or
+    "free"; max_move: no vertex ends further than this from where it started (None: no limit); normals: "recompute" (from
+    the smoothed triangles, area-weighted: mesh_normals) or "keep" -- a mesh without normals stays without.  Vertex count,
+    indices and keys are the input's (include/fi_hip.h fi_mesh_smooth).  -> IsoMesh where `mesh` lives"""
+    h, ndim, _mem, like = _mesh_handle(mesh)
+    try:
+        out = _handle_smooth(h, iterations, lam, mu, boundary, max_move, normals)
+    finally:
+        _capi.lib().fi_mesh_destroy(h)
+    return _take_mesh_like(out, ndim, mesh.normals is not None, like)
+
+
+def mesh_normals(mesh):
+    """`mesh` with vertex normals computed on the device from its primitives: the area- (2-D: length-) weighted sum of the
+    normals of the primitives around each vertex, normalised, pointing from the extractors' inside to their outside; zeros
+    for a vertex no primitive uses (include/fi_hip.h fi_mesh_normals).  Works on a mesh that has no normals.  -> IsoMesh
+    where `mesh` lives"""
+    h, ndim, _mem, like = _mesh_handle(mesh)
+    try:
+        out = C.c_void_p()
+        check(_capi.lib().fi_mesh_normals(h, C.byref(out)))
+    finally:
+        _capi.lib().fi_mesh_destroy(h)
+    return _take_mesh_like(out, ndim, True, like)
+
+
+def _finish_mesh(h, ndim, normals, largest, min_size, parts, simplify=None, smooth=None):
     """What the extractors return for a device mesh handle: the mesh, filtered on the device if largest / min_size ask for
-    it (label -> measure -> select), then simplified on the device if `simplify` asks for it (a cell, or a (cell, placement)
-    pair), with one copy at the end, and with parts=True the MeshParts of the mesh returned."""
-    if largest is None and min_size is None and not parts and simplify is None:
+    it (label -> measure -> select), then smoothed on the device if `smooth` asks for it (an iteration count, or a dict of
+    smooth_mesh's keywords), then simplified on the device if `simplify` asks for it (a cell, or a (cell, placement) pair),
+    with one copy at the end, and with parts=True the MeshParts of the mesh returned."""
+    if largest is None and min_size is None and not parts and simplify is None and smooth is None:
         return _take_mesh(h, ndim, normals)
     try:
         if largest is not None or min_size is not None:
@@ -299,6 +354,10 @@ def _finish_mesh(h, ndim, normals, largest, min_size, parts, simplify=None):
             kept = _handle_select(h, keep)
             _capi.lib().fi_mesh_destroy(h)
             h = kept
+        if smooth is not None:
+            faired = _handle_smooth(h, **_smooth_args(smooth))
+            _capi.lib().fi_mesh_destroy(h)
+            h = faired
         if simplify is not None:
             cell, placement = _simplify_args(simplify)
             coarse = _handle_simplify(h, ndim, cell, None, placement)
@@ -1059,35 +1118,38 @@ class LatticeField:
                                           C.byref(st), _same_memory(kg, ko)))
         return out, om, {f: getattr(st, f) for f, _ in st._fields_}
 
-    def iso_surface(self, solution=None, iso=0.0, normals=True, largest=None, min_size=None, parts=False, simplify=None):
+    def iso_surface(self, solution=None, iso=0.0, normals=True, largest=None, min_size=None, parts=False, simplify=None,
+                    smooth=None):
         """The iso-contour (2-D) / iso-surface (3-D) f = iso of `solution` (this context's owned values, host or device) or,
         with None, of the last solve's solution where it lives on the device -- the step src/sdf_field.cpp:605-613 takes
         after the solve.  A slab context returns its piece (merge_meshes joins them).  -> IsoMesh
         largest = k / min_size = s: only the k largest connected parts / the parts of at least that area (2-D: length) are
         kept (keep_parts), chosen and cut out on the device before the one copy to the host; parts=True: -> (IsoMesh,
         MeshParts of that mesh).  simplify = cell or (cell, placement): the mesh (after the selection, if any) is made
-        coarser on the device by simplify_mesh's vertex clustering before the copy; parts=True then describes that mesh."""
+        coarser on the device by simplify_mesh's vertex clustering before the copy; parts=True then describes that mesh.
+        smooth = iterations or a dict of smooth_mesh's keywords: the mesh is faired on the device by smooth_mesh after the
+        selection and before the simplification (whose quadrics then fit the faired surface)."""
         h = C.c_void_p()
         if solution is None:
             check(_capi.lib().fi_iso_extract(self._h, None, float(iso), FI_HOST, C.byref(h)))
         else:
             s, mem, _keep = _buf(solution)
             check(_capi.lib().fi_iso_extract(self._h, s, float(iso), mem, C.byref(h)))
-        return _finish_mesh(h, len(self.sizes), normals, largest, min_size, parts, simplify)
+        return _finish_mesh(h, len(self.sizes), normals, largest, min_size, parts, simplify, smooth)
 
     def dual_contour(self, solution=None, iso=0.0, gradients=None, normals=True, largest=None, min_size=None, parts=False,
-                     simplify=None):
+                     simplify=None, smooth=None):
         """The dual contour (2-D: segments, 3-D: triangles) of `solution` (this context's owned values, host or device) or,
         with None, of the last solve's solution where it lives on the device: one vertex per crossed cell, fitted to the
         corner gradients so that sharp corners survive (include/fi_hip.h fi_dual_contour).  gradients: (num_owned, ndim)
         in the same memory as `solution`, or None for central differences of f - iso.  Undivided contexts only.  -> IsoMesh
-        (keys: the lattice index of each vertex's cell).  largest, min_size, parts, simplify: as iso_surface's."""
+        (keys: the lattice index of each vertex's cell).  largest, min_size, parts, simplify, smooth: as iso_surface's."""
         s, smem, _ks = _buf(solution)
         g, gmem, _kg = _buf(gradients)
         mem = _same_memory(smem, gmem)
         h = C.c_void_p()
         check(_capi.lib().fi_dual_contour(self._h, s, g, float(iso), mem, C.byref(h)))
-        return _finish_mesh(h, len(self.sizes), normals, largest, min_size, parts, simplify)
+        return _finish_mesh(h, len(self.sizes), normals, largest, min_size, parts, simplify, smooth)
 
     def sample(self, positions, solution=None, gradients=False, cubic=False, fill=float("nan")):
         """Values (n,) -- and with gradients=True also gradients (n, ndim) -- of `solution` (this context's owned values) or,
@@ -1542,27 +1604,29 @@ def upscale_field(field, small_sizes, large_sizes):
     return out
 
 
-def iso_surface(field, sizes, iso=0.0, normals=True, largest=None, min_size=None, parts=False, simplify=None):
+def iso_surface(field, sizes, iso=0.0, normals=True, largest=None, min_size=None, parts=False, simplify=None, smooth=None):
     """The iso-contour (2-D) / iso-surface (3-D) f = iso of a whole lattice field (numpy array or torch CUDA tensor, x
-    fastest), e.g. the output of upscale_field.  -> IsoMesh.  largest, min_size, parts, simplify: as LatticeField.iso_surface's."""
+    fastest), e.g. the output of upscale_field.  -> IsoMesh.  largest, min_size, parts, simplify, smooth: as
+    LatticeField.iso_surface's."""
     src, mem, _keep = _buf(field)
     sz = (C.c_int * len(sizes))(*[int(s) for s in sizes])
     h = C.c_void_p()
     check(_capi.lib().fi_iso_extract_field(src, len(sizes), sz, float(iso), mem, C.byref(h)))
-    return _finish_mesh(h, len(sizes), normals, largest, min_size, parts, simplify)
+    return _finish_mesh(h, len(sizes), normals, largest, min_size, parts, simplify, smooth)
 
 
-def dual_contour(field, sizes, iso=0.0, gradients=None, normals=True, largest=None, min_size=None, parts=False, simplify=None):
+def dual_contour(field, sizes, iso=0.0, gradients=None, normals=True, largest=None, min_size=None, parts=False, simplify=None,
+                 smooth=None):
     """LatticeField.dual_contour of a whole lattice field (numpy array or torch CUDA tensor, x fastest); gradients:
-    (prod(sizes), ndim) in the same memory, or None.  -> IsoMesh.  largest, min_size, parts, simplify: as
-    LatticeField.iso_surface's."""
+    (prod(sizes), ndim) in the same memory, or None.  -> IsoMesh.  largest, min_size, parts, simplify, smooth:
+    as LatticeField.iso_surface's."""
     src, mem, _keep = _buf(field)
     g, gmem, _kg = _buf(gradients)
     mem = _same_memory(mem, gmem)
     sz = (C.c_int * len(sizes))(*[int(s) for s in sizes])
     h = C.c_void_p()
     check(_capi.lib().fi_dual_contour_field(src, g, len(sizes), sz, float(iso), mem, C.byref(h)))
-    return _finish_mesh(h, len(sizes), normals, largest, min_size, parts, simplify)
+    return _finish_mesh(h, len(sizes), normals, largest, min_size, parts, simplify, smooth)
 
 
 def redistance(field, sizes, iso=0.0, method="iso", max_distance=math.inf):

@@ -13,6 +13,7 @@
 #include "fi_robust.h"
 #include "fi_parts.h"
 #include "fi_simplify.h"
+#include "fi_smooth.h"
 
 #include <memory>
 
@@ -1292,6 +1293,20 @@ int fi_mesh_simplify(const fi_mesh* m, float cell, const float* origin, int plac
 	FI_API_END
 }
 
+// ---- mesh smoothing (fi_smooth.hip) -------------------------------------------------------------------
+int fi_mesh_smooth(const fi_mesh* m, const fi_smooth_options* opt, fi_mesh** out)
+{
+	FI_API_BEGIN
+	fi::mesh_smooth(m, opt, out);
+	FI_API_END
+}
+
+int fi_mesh_normals(const fi_mesh* m, fi_mesh** out)
+{
+	FI_API_BEGIN
+	fi::mesh_normals(m, out);
+	FI_API_END
+}
 
 // ---- point queries (fi_sample.hip) --------------------------------------------------------------
 int fi_sample(fi_ctx* c, const float* field, long n, const float* positions, int mode, float fill, float* values,

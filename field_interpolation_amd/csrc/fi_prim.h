@@ -54,6 +54,14 @@ inline hipError_t sort_pairs_u64(void* tmp, size_t& bytes, const uint64_t* keys_
 	                                                     static_cast<unsigned int>(begin_bit), static_cast<unsigned int>(end_bit), st);
 }
 
+// the same sort of bare keys (fi_smooth.hip's directed vertex pairs: the key is all there is)
+inline hipError_t sort_keys_u64(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t* keys_out, size_t n, int begin_bit, int end_bit,
+                                hipStream_t st)
+{
+	return rocprim::radix_sort_keys<detail::onesweep64>(tmp, bytes, keys_in, keys_out, static_cast<unsigned int>(n),
+	                                                    static_cast<unsigned int>(begin_bit), static_cast<unsigned int>(end_bit), st);
+}
+
 // ---- the host side of a unit built on these: one arena (fi_arena.h) for a call's temporaries, a piece of it as workspace ---
 
 // the primitives' workspace: a piece of the arena sized (scan_bytes, sort_bytes) for the call's largest sort and scan
@@ -111,6 +119,24 @@ inline void sort_u64(const uint64_t* kin, uint64_t* kout, const V* vin, V* vout,
 	DevBuf more;
 	if (tb > tmp.bytes) { more.alloc(tb); }
 	FI_HIP_TRY(sort_pairs_u64(more.p ? more.p : tmp.p, tb, kin, kout, vin, vout, static_cast<size_t>(n), begin_bit, end_bit, st));
+}
+
+inline size_t sort_keys_bytes(int64_t n, int begin_bit, int end_bit)
+{
+	size_t tb = 0;
+	FI_HIP_TRY(sort_keys_u64(nullptr, tb, static_cast<const uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr), static_cast<size_t>(n), begin_bit,
+	                         end_bit, nullptr));
+	return tb;
+}
+
+// kout = the keys kin in ascending order of bits [begin_bit, end_bit)
+inline void sort_keys(const uint64_t* kin, uint64_t* kout, int64_t n, int begin_bit, int end_bit, const Scratch& tmp, hipStream_t st)
+{
+	size_t tb = 0;
+	FI_HIP_TRY(sort_keys_u64(nullptr, tb, kin, kout, static_cast<size_t>(n), begin_bit, end_bit, st));
+	DevBuf more;
+	if (tb > tmp.bytes) { more.alloc(tb); }
+	FI_HIP_TRY(sort_keys_u64(more.p ? more.p : tmp.p, tb, kin, kout, static_cast<size_t>(n), begin_bit, end_bit, st));
 }
 
 inline uint32_t read_u32(const uint32_t* dev, hipStream_t st)

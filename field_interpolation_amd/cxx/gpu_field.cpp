@@ -400,6 +400,36 @@ bool GpuLatticeField::iso_surface_simplified(float iso, bool dual, float cell, i
 	return ok;
 }
 
+bool GpuLatticeField::iso_surface_smoothed(float iso, bool dual, int iterations, float lambda, float mu, float max_move, int largest,
+                                           double min_size, std::vector<float>* vertices, std::vector<int>* indices,
+                                           std::vector<float>* normals) const
+{
+	fi_mesh* m = nullptr;
+	if ((dual ? fi_dual_contour(ctx_, nullptr, nullptr, iso, FI_HOST, &m) : fi_iso_extract(ctx_, nullptr, iso, FI_DEVICE, &m)) != FI_OK) {
+		warn("iso_surface_smoothed");
+		return false;
+	}
+	// extract -> (the parts iso_surface_parts' rule keeps, if it is asked to drop any) -> smooth, one copy at the end
+	fi_mesh* kept   = nullptr;
+	fi_mesh* faired = nullptr;
+	bool     ok     = true;
+	if (largest >= 0 || min_size > 0.0) { ok = select_by_rule(m, largest, min_size, &kept); }
+	fi_smooth_options opt{};
+	opt.iterations = iterations;
+	opt.lambda     = lambda;
+	opt.mu         = mu;
+	opt.boundary   = FI_SMOOTH_BOUNDARY_FIXED;
+	opt.max_move   = max_move;
+	opt.normals    = FI_SMOOTH_NORMALS_RECOMPUTE;
+	ok = ok && fi_mesh_smooth(kept ? kept : m, &opt, &faired) == FI_OK;
+	ok = ok && copy_mesh(faired, sizes_.size(), vertices, indices, normals);
+	if (!ok) { warn("iso_surface_smoothed"); }
+	fi_mesh_destroy(faired);
+	fi_mesh_destroy(kept);
+	fi_mesh_destroy(m);
+	return ok;
+}
+
 bool GpuLatticeField::sample(const std::vector<float>& positions, std::vector<float>* values, std::vector<float>* gradients,
                              bool cubic) const
 {

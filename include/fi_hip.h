@@ -628,6 +628,60 @@ int fi_mesh_select(const fi_mesh* m, long num_parts, const unsigned char* keep, 
 int fi_mesh_simplify(const fi_mesh* m, float cell, const float* origin, int placement, int* vertex_map, int memory,
                      fi_mesh** out);
 
+/* ---- mesh smoothing: Taubin fairing, normals recomputed from the primitives -----------------------
+ * Makes a device mesh smoother without the mesh leaving the device: Taubin's lambda | mu fairing with uniform ("umbrella")
+ * weights (Taubin 1995; mu = 0: plain Laplacian smoothing), and vertex normals that fit the positions.  Any fi_mesh, 2-D
+ * segments or 3-D triangles, with or without normals.  Both calls return a new immutable mesh with the input's vertex count,
+ * keys and indices, copied (the keys stay ascending); nothing is kept with either handle.  The contract (DESIGN.md 4.16;
+ * tests/smooth_reference.py is its definition in numpy) -- all arithmetic fp64 on the fp32 coordinates converted exactly, one
+ * rounding per operation, every sum serial from 0 in the stated order:
+ *   - half-edges: those of fi_mesh_parts ((a,b), (b,c), (c,a) of a triangle, (a,b) of a segment; equal ends are ignored).
+ *     N(v): the distinct vertices a half-edge joins to v, in either direction, in ascending index order;
+ *   - boundary.  3-D: a boundary edge is an unordered pair used by exactly one half-edge (fi_mesh_measure's `boundary`), a
+ *     boundary vertex an end of one; an edge used three times or more, or twice in one direction, counts as interior.  2-D: a
+ *     boundary vertex has total degree 1 (one half-edge touches it).  The set S(v) a vertex averages over:
+ *       every mode                 N(v) empty (every unused vertex): S(v) empty;
+ *       FI_SMOOTH_BOUNDARY_FIXED   boundary vertices: S(v) empty; others: N(v);
+ *       FI_SMOOTH_BOUNDARY_SLIDE   3-D boundary vertices: B(v), the neighbours across v's boundary edges (ascending) -- a rim is
+ *                                  faired as a curve and stays in a plane it lies in; others: N(v).  2-D: as FIXED;
+ *       FI_SMOOTH_BOUNDARY_FREE    N(v) for every vertex.
+ *     A vertex with empty S(v) never moves;
+ *   - one step with factor f (lambda or mu as double), every vertex from the positions before the step (two buffers), per
+ *     axis a: avg = (sum of x_w,a over w in S(v), ascending) / |S(v)|; t = avg - x_a; t = f t; x'_a = x_a + t;
+ *   - one iteration: a lambda step; a mu step unless mu == 0; then, if max_move > 0, the clamp -- ONCE an iteration, behind
+ *     its last step, not behind every step: d = x' - x0 per axis (x0 the input position), s2 = (d_x d_x + d_y d_y) + d_z d_z
+ *     (2-D: the first two), m = max_move as double; if s2 > m m: x' = x0 + d (m / sqrt(s2)).  No vertex ends further than
+ *     max_move from where it started (plus the rounding of the cast);
+ *   - positions: (float)x after the last iteration; iterations == 0: the input's bytes;
+ *   - normals.  FI_SMOOTH_NORMALS_KEEP: the input's, copied.  FI_SMOOTH_NORMALS_RECOMPUTE: those fi_mesh_normals gives for the
+ *     output.  Either way a mesh without normals gives a mesh without normals.  fi_mesh_normals always gives normals (and
+ *     the input's positions): for vertex v the primitives that reference v in ascending primitive number, one that names v
+ *     twice counted once; n_p from the mesh's fp32 positions, 3-D (b - a) x (c - a) (n_x = u_y w_z - u_z w_y, ..., as in
+ *     fi_mesh_simplify), 2-D (e_y, -e_x) with e = b - a -- not normalised (area / length weights), pointing from the
+ *     extractors' inside to their outside; the sum divided by its length (sqrt of the squares summed in axis order), cast to
+ *     fp32; a zero sum and an unused vertex give zeros;
+ *   - an empty mesh: an empty mesh and FI_OK.  A NULL mesh, options or out; iterations < 0; lambda outside [0, 1], mu outside
+ *     [-2, 0], max_move < 0, or any of them NaN; a bad boundary or normals code; a non-finite coordinate of a USED vertex
+ *     (both calls; an unused vertex may hold anything and keeps it): FI_ERR_INVALID and no mesh.
+ * No floating-point atomics and no atomics in the outputs: a repeated call returns the same bytes.  A vertex with very many
+ * neighbours makes one thread sum them all: correct, and slow.  Not offered: cotangent or other geometry-dependent weights,
+ * feature-preserving or bilateral filtering, implicit (solved) fairing, an adjacency cached with the handle, slab groups
+ * (merge the pieces first: a seam is a boundary and stays jagged under FIXED), 1-D. */
+#define FI_SMOOTH_BOUNDARY_FIXED 0
+#define FI_SMOOTH_BOUNDARY_SLIDE 1
+#define FI_SMOOTH_BOUNDARY_FREE  2
+#define FI_SMOOTH_NORMALS_RECOMPUTE 0
+#define FI_SMOOTH_NORMALS_KEEP      1
+typedef struct fi_smooth_options {
+	int   iterations;   /* >= 0 */
+	float lambda, mu;   /* 0 <= lambda <= 1;  -2 <= mu <= 0;  mu == 0: no second step (plain Laplacian) */
+	int   boundary;     /* FI_SMOOTH_BOUNDARY_* */
+	float max_move;     /* > 0: no vertex ends further than this from where it started;  0: no limit */
+	int   normals;      /* FI_SMOOTH_NORMALS_* */
+} fi_smooth_options;
+int fi_mesh_smooth(const fi_mesh* m, const fi_smooth_options* opt, fi_mesh** out);
+int fi_mesh_normals(const fi_mesh* m, fi_mesh** out);
+
 /* ---- point queries: values and gradients at arbitrary positions --------------------------------
  * The contract ("Point queries") is this project's own:
  *   - positions: n points of ndim fp32 values, interleaved, in global lattice coordinates (x fastest, as fi_add_points);

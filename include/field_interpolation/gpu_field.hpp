@@ -108,6 +108,15 @@ public:
 	bool iso_surface_simplified(float iso, bool dual, float cell, int placement, int largest, double min_size, std::vector<float>* vertices,
 	                            std::vector<int>* indices, std::vector<float>* normals = nullptr) const;
 
+	// iso_surface_parts' mesh (largest < 0 and min_size <= 0: every part) made smoother on the device before the one copy to the
+	// host: `iterations` times, every vertex moves towards the average of its neighbours by the factor lambda and then by the
+	// factor mu (Taubin's fairing; mu = 0: plain Laplacian smoothing), the vertices of open edges stay where they are
+	// (FI_SMOOTH_BOUNDARY_FIXED), no vertex ends further than max_move from where it started (0: no limit), and the normals are
+	// recomputed from the smoothed primitives.  The contract is include/fi_hip.h fi_mesh_smooth.  false: no solution yet, or the
+	// library refused the call.
+	bool iso_surface_smoothed(float iso, bool dual, int iterations, float lambda, float mu, float max_move, int largest, double min_size,
+	                          std::vector<float>* vertices, std::vector<int>* indices, std::vector<float>* normals = nullptr) const;
+
 	// Values (and, if asked, gradients: ndim floats per point) of the last solution at `positions` (ndim floats per point,
 	// global lattice coordinates, x fastest), sampled where the solution lives on the device: multilinear, or Catmull-Rom
 	// with cubic = true; points outside the lattice get NaN.  The contract is include/fi_hip.h fi_sample.  false: no
