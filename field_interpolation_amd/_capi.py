@@ -24,7 +24,7 @@ SYMBOLS = [
     "fi_group_iso_extract", "fi_iso_extract", "fi_iso_extract_field", "fi_mesh_info", "fi_mesh_copy", "fi_mesh_destroy",
     "fi_dual_contour", "fi_dual_contour_field",
     "fi_mesh_create", "fi_mesh_parts", "fi_mesh_measure", "fi_mesh_select", "fi_mesh_simplify",
-    "fi_mesh_smooth", "fi_mesh_normals",
+    "fi_mesh_smooth", "fi_mesh_normals", "fi_mesh_sample", "fi_mesh_deviation",
     "fi_group_sample", "fi_sample", "fi_sample_field",
     "fi_nearest", "fi_distance_field", "fi_points_create", "fi_points_nearest", "fi_points_distance_field", "fi_points_destroy",
     "fi_knn", "fi_points_knn", "fi_estimate_normals", "fi_points_estimate_normals",
@@ -86,6 +86,11 @@ class FiMeshPart(C.Structure):
 class FiSmoothOptions(C.Structure):
     _fields_ = [("iterations", C.c_int), ("lam", C.c_float), ("mu", C.c_float), ("boundary", C.c_int),
                 ("max_move", C.c_float), ("normals", C.c_int)]
+
+
+class FiDeviation(C.Structure):
+    _fields_ = [("queries", C.c_longlong), ("counted", C.c_longlong), ("beyond", C.c_longlong), ("invalid", C.c_longlong),
+                ("at", C.c_longlong), ("max", C.c_double), ("mean", C.c_double), ("rms", C.c_double), ("where", C.c_float * 3)]
 
 
 class FiError(RuntimeError):
@@ -167,6 +172,9 @@ def lib():
     L.fi_mesh_simplify.argtypes = [vp, C.c_float, vp, C.c_int, vp, C.c_int, C.POINTER(vp)]
     L.fi_mesh_smooth.argtypes = [vp, C.POINTER(FiSmoothOptions), C.POINTER(vp)]
     L.fi_mesh_normals.argtypes = [vp, C.POINTER(vp)]
+    L.fi_mesh_sample.argtypes = [vp, C.c_long, C.c_ulonglong, C.c_int, fp, fp, vp, C.c_int]
+    L.fi_mesh_deviation.argtypes = [vp, vp, C.c_long, C.c_ulonglong, C.c_float, C.POINTER(FiDeviation), C.POINTER(FiDeviation), fp,
+                                    C.c_int]
     L.fi_group_sample.argtypes = [vp, fp, C.c_long, fp, C.c_int, C.c_float, fp, fp]
     L.fi_sample.argtypes = [vp, fp, C.c_long, fp, C.c_int, C.c_float, fp, fp, C.c_int]
     L.fi_sample_field.argtypes = [fp, C.c_int, ip, C.c_long, fp, C.c_int, C.c_float, fp, fp, C.c_int]

@@ -838,6 +838,111 @@ class SurfaceIndex:
         return t.reshape(height, width), prim.reshape(height, width)
 
 
+FI_SAMPLE_NORMALS = {"face": 0, "vertex": 1}
+
+
+def _like_array(like, shape, dtype):
+    """an uninitialised array of `shape`: a torch tensor on like's device when `like` is a CUDA tensor, else numpy
+    -> (array, pointer or None for an empty one)"""
+    if like is not None and like.is_cuda:
+        import torch
+        t = torch.empty(shape, dtype={np.float32: torch.float32, np.int64: torch.int64}[dtype], device=like.device)
+        return t, (C.c_void_p(t.data_ptr()) if t.numel() else None)
+    a = np.empty(shape, dtype)
+    return a, (C.c_void_p(a.ctypes.data) if a.size else None)
+
+
+def sample_mesh(mesh, n, seed=0, normals="face", primitives=False):
+    """`n` points spread over `mesh` (an IsoMesh of numpy arrays, or of torch CUDA tensors; keys may be None) by area (2-D: by
+    length) on the device: sample i lies in the i-th of n equal strata of the total area, placed by a counter-based hash of
+    `seed`, so the points come out in ascending primitive order and a call is repeatable.  normals: "face" (the primitive's
+    unit normal), "vertex" (the mesh's vertex normals interpolated and normalised; the mesh must have normals) or None;
+    primitives=True: also the primitive each point lies on, int64.  Zero-area primitives are never sampled; a mesh with
+    nothing to sample is refused (include/fi_hip.h fi_mesh_sample).  -> positions (n, ndim) float32, or a tuple (positions,
+    normals, primitives) of what was asked for, where `mesh` lives"""
+    if normals is not None and normals not in FI_SAMPLE_NORMALS:
+        raise ValueError("normals is 'face', 'vertex' or None")
+    n = int(n)
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    h, ndim, _mem, like = _mesh_handle(mesh)
+    try:
+        mem = FI_DEVICE if like is not None and like.is_cuda else FI_HOST
+        pos, ppos = _like_array(like, (n, ndim), np.float32)
+        nrm, pnrm = _like_array(like, (n, ndim), np.float32) if normals is not None else (None, None)
+        prim, pprim = _like_array(like, (n,), np.int64) if primitives else (None, None)
+        if n:
+            check(_capi.lib().fi_mesh_sample(h, n, int(seed) & (2 ** 64 - 1), FI_SAMPLE_NORMALS[normals or "face"], ppos, pnrm, pprim, mem))
+    finally:
+        _capi.lib().fi_mesh_destroy(h)
+    out = tuple(a for a in (pos, nrm, prim) if a is not None)
+    return out if len(out) > 1 else pos
+
+
+def _deviation_dict(r, ndim):
+    return {"queries": int(r.queries), "counted": int(r.counted), "beyond": int(r.beyond), "invalid": int(r.invalid), "at": int(r.at),
+            "max": float(r.max), "mean": float(r.mean), "rms": float(r.rms), "where": np.array(list(r.where)[:ndim], np.float32)}
+
+
+def _deviation(h, surface, ndim, nv, like, samples, seed, max_distance, vertex_distances):
+    """fi_mesh_deviation of a device mesh handle against a surface handle -> the dict of one direction"""
+    of_s, of_v = _capi.FiDeviation(), _capi.FiDeviation()
+    vd, pvd, mem = None, None, FI_HOST
+    if vertex_distances:
+        vd, pvd = _like_array(like, (nv,), np.float32)
+        mem = FI_DEVICE if like is not None and like.is_cuda else FI_HOST
+    check(_capi.lib().fi_mesh_deviation(h, surface, int(samples), int(seed) & (2 ** 64 - 1), float(max_distance), C.byref(of_s),
+                                        C.byref(of_v), pvd, mem))
+    out = {"samples": _deviation_dict(of_s, ndim), "vertices": _deviation_dict(of_v, ndim)}
+    if vertex_distances:
+        out["vertex_distances"] = vd
+    return out
+
+
+def mesh_deviation(a, b, samples=100_000, seed=0, max_distance=math.inf, symmetric=True, vertex_distances=False):
+    """How far mesh `a` lies from surface `b`, measured on the device: the exact distances (SurfaceIndex.distance) of `samples`
+    points spread over `a` (sample_mesh(a, samples, seed)) and of the vertices `a` uses, each list reduced to a dict of
+    queries, counted, beyond (further than max_distance), invalid (a non-finite vertex), max, mean, rms, at (the first query
+    holding max; -1 when nothing is counted) and where (its position) -- the same bytes on every run.  `a` and `b` are
+    IsoMeshes of numpy arrays or of torch CUDA tensors; `b` may also be a SurfaceIndex, which holds no mesh: symmetric=True
+    then raises ValueError.  vertex_distances=True adds the distance of every vertex (NaN for an unused one), where the mesh
+    lives.  -> {"a_to_b": {"samples": ..., "vertices": ...[, "vertex_distances": ...]}, "b_to_a": the same the other way or
+    None, "hausdorff": the largest max of all} (include/fi_hip.h fi_mesh_deviation)"""
+    if int(samples) < 0:
+        raise ValueError("samples must be >= 0")
+    L = _capi.lib()
+    given = isinstance(b, SurfaceIndex)
+    if given and symmetric:
+        raise ValueError("symmetric=True needs b as a mesh: a SurfaceIndex holds no mesh to sample")
+    ha, ndim, _mem, like_a = _mesh_handle(a)
+    hb, sa, sb = None, C.c_void_p(), C.c_void_p()
+    try:
+        if given:
+            if b.ndim != ndim:
+                raise ValueError("a is %d-D, b is %d-D" % (ndim, b.ndim))
+            surface = b._h
+        else:
+            hb, ndim_b, _mem, like_b = _mesh_handle(b)
+            if ndim_b != ndim:
+                raise ValueError("a is %d-D, b is %d-D" % (ndim, ndim_b))
+            check(L.fi_surface_from_mesh(C.byref(sb), hb))
+            surface = sb
+        out = {"a_to_b": _deviation(ha, surface, ndim, int(a.vertices.shape[0]), like_a, samples, seed, max_distance, vertex_distances),
+               "b_to_a": None}
+        if symmetric:
+            check(L.fi_surface_from_mesh(C.byref(sa), ha))
+            out["b_to_a"] = _deviation(hb, sa, ndim, int(b.vertices.shape[0]), like_b, samples, seed, max_distance, vertex_distances)
+    finally:
+        for s in (sa, sb):
+            if s:
+                L.fi_surface_destroy(s)
+        for h in (ha, hb):
+            if h:
+                L.fi_mesh_destroy(h)
+    out["hausdorff"] = max(d[k]["max"] for d in (out["a_to_b"], out["b_to_a"]) if d is not None for k in ("samples", "vertices"))
+    return out
+
+
 def mesh_to_sdf(mesh, sizes, max_distance=math.inf):
     """The signed distance (flat, x fastest, float32) of every point of a lattice of `sizes` to a mesh -- an IsoMesh or
     anything with `vertices` and `indices`, from a field or not: SurfaceIndex.signed_distance_field.  The sign is the parity

@@ -14,6 +14,7 @@
 #include "fi_parts.h"
 #include "fi_simplify.h"
 #include "fi_smooth.h"
+#include "fi_meshpts.h"
 
 #include <memory>
 
@@ -1305,6 +1306,23 @@ int fi_mesh_normals(const fi_mesh* m, fi_mesh** out)
 {
 	FI_API_BEGIN
 	fi::mesh_normals(m, out);
+	FI_API_END
+}
+
+// ---- points on a mesh, mesh-to-surface deviation (fi_meshpts.hip) ---------------------------------------
+int fi_mesh_sample(const fi_mesh* m, long n, unsigned long long seed, int normals_mode, float* positions, float* normals,
+                   long long* primitives, int memory)
+{
+	FI_API_BEGIN
+	fi::mesh_sample(m, n, seed, normals_mode, positions, normals, primitives, memory);
+	FI_API_END
+}
+
+int fi_mesh_deviation(const fi_mesh* a, fi_surface* b, long samples, unsigned long long seed, float max_distance, fi_deviation* of_samples,
+                      fi_deviation* of_vertices, float* vertex_distances, int memory)
+{
+	FI_API_BEGIN
+	fi::mesh_deviation(a, b, samples, seed, max_distance, of_samples, of_vertices, vertex_distances, memory);
 	FI_API_END
 }
 

@@ -100,6 +100,23 @@ inline void scan_u32(const uint32_t* in, Out* out, int64_t n, const Scratch& tmp
 	FI_HIP_TRY(exclusive_sum(more.p ? more.p : tmp.p, tb, in, out, static_cast<size_t>(n), st));
 }
 
+// the same scan of n uint64 (fi_meshpts.hip's integer weights reach 2^32: one bit more than a uint32 holds)
+inline size_t scan_u64_bytes(int64_t n)
+{
+	size_t tb = 0;
+	FI_HIP_TRY(exclusive_sum(nullptr, tb, static_cast<const uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr), static_cast<size_t>(n), nullptr));
+	return tb;
+}
+
+inline void scan_u64(const uint64_t* in, uint64_t* out, int64_t n, const Scratch& tmp, hipStream_t st)
+{
+	size_t tb = 0;
+	FI_HIP_TRY(exclusive_sum(nullptr, tb, in, out, static_cast<size_t>(n), st));
+	DevBuf more;
+	if (tb > tmp.bytes) { more.alloc(tb); }
+	FI_HIP_TRY(exclusive_sum(more.p ? more.p : tmp.p, tb, in, out, static_cast<size_t>(n), st));
+}
+
 template <typename V = uint32_t>
 inline size_t sort_bytes(int64_t n, int begin_bit, int end_bit)
 {

@@ -430,6 +430,26 @@ bool GpuLatticeField::iso_surface_smoothed(float iso, bool dual, int iterations,
 	return ok;
 }
 
+bool GpuLatticeField::iso_surface_points(float iso, bool dual, long n, unsigned long long seed, std::vector<float>* positions,
+                                         std::vector<float>* normals) const
+{
+	fi_mesh* m = nullptr;
+	if (!positions || n < 0 ||
+	    (dual ? fi_dual_contour(ctx_, nullptr, nullptr, iso, FI_HOST, &m) : fi_iso_extract(ctx_, nullptr, iso, FI_DEVICE, &m)) != FI_OK) {
+		warn("iso_surface_points");
+		return false;
+	}
+	// extract -> sample with the extractor's vertex normals, one copy at the end
+	const size_t count = sizes_.size() * static_cast<size_t>(n);
+	positions->resize(count);
+	if (normals) { normals->resize(count); }
+	const bool ok = fi_mesh_sample(m, n, seed, FI_SAMPLE_NORMALS_VERTEX, positions->data(), normals ? normals->data() : nullptr, nullptr,
+	                               FI_HOST) == FI_OK;
+	if (!ok) { warn("iso_surface_points"); }
+	fi_mesh_destroy(m);
+	return ok;
+}
+
 bool GpuLatticeField::sample(const std::vector<float>& positions, std::vector<float>* values, std::vector<float>* gradients,
                              bool cubic) const
 {

@@ -446,6 +446,7 @@ int fi_time_apply(fi_ctx* ctx, int reps, double* ms_per_launch);
 typedef struct fi_group fi_group;
 typedef struct fi_mesh fi_mesh;
 typedef struct fi_points fi_points;
+typedef struct fi_surface fi_surface;
 int     fi_group_create(fi_group** out, int ndim, const int* sizes, int dtype, int nranks);
 int     fi_group_destroy(fi_group* g);
 int     fi_group_size(const fi_group* g);
@@ -682,6 +683,60 @@ typedef struct fi_smooth_options {
 int fi_mesh_smooth(const fi_mesh* m, const fi_smooth_options* opt, fi_mesh** out);
 int fi_mesh_normals(const fi_mesh* m, fi_mesh** out);
 
+/* ---- points on a mesh, and how far one mesh lies from another surface ----------------------------
+ * fi_mesh_sample spreads n points over a device mesh by area (2-D: by length), with normals and the primitive each lies on;
+ * fi_mesh_deviation measures the distances of such points and of the mesh's vertices to a surface (fi_surface_*) and reduces
+ * them to the same bytes on every run.  Any fi_mesh, 2-D segments or 3-D triangles.  The contract (DESIGN.md 4.17;
+ * tests/meshpts_reference.py is its definition in numpy) -- all floating-point work fp64 on the fp32 coordinates converted
+ * exactly, one rounding per operation; all integer work uint64, wrapping:
+ *   - weights.  3-D: w_p = sqrt((n_x n_x + n_y n_y) + n_z n_z) of fi_mesh_normals' n_p = (b - a) x (c - a), its components formed
+ *     as there; 2-D: w_p = sqrt(e_x e_x + e_y e_y), e = b - a.  A non-finite w_p counts as 0.  wmax = the largest w_p;
+ *   - integer weights.  k = min(32, 52 - bits(np)), bits(np) the smallest b >= 1 with 2^b >= np;
+ *     q_p = (uint64) floor((w_p / wmax) 2^k), 0 for every p when wmax = 0.  C = the inclusive prefix sums of q, T = their total
+ *     (<= 2^52: exact as doubles).  A primitive with q_p = 0 is never sampled;
+ *   - uniforms.  u(c) = (mix(seed + (c + 1) 0x9E3779B97F4A7C15) >> 11) 2^-53 with splitmix64's finaliser mix(z): z ^= z >> 30;
+ *     z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31.  Sample i draws xi = u(3 i), r1 = u(3 i + 1),
+ *     r2 = u(3 i + 2) (2-D: the same counters, r2 unused);
+ *   - stratum.  y = (((double)i + xi) / (double)n) (double)T; t = (uint64)y, T - 1 if t >= T; the primitive p = the number of
+ *     entries of C that are <= t.  t never falls as i rises: the samples come out in ascending primitive order;
+ *   - point.  3-D: if r1 + r2 > 1: r1 = 1 - r1, r2 = 1 - r2; per axis x = (a + r1 (b - a)) + r2 (c - a).  2-D: x = a + r1 (b - a).
+ *     positions = (float)x;
+ *   - normals.  FI_SAMPLE_NORMALS_FACE: n_p (2-D: (e_y, -e_x)) divided per component by w_p, pointing from the extractors'
+ *     inside to their outside.  FI_SAMPLE_NORMALS_VERTEX: m = (w0 n_a + r1 n_b) + r2 n_c per axis from the mesh's vertex normals
+ *     as doubles, w0 = (1 - r1) - r2 (2-D: w0 = 1 - r1, no n_c term), divided by its length (the squares summed in axis
+ *     order); a zero or non-finite length: the face normal.  Both cast to fp32.
+ * fi_mesh_sample: positions float[n][ndim] (required when n > 0), normals float[n][ndim] or NULL, primitives long long[n] or
+ * NULL, all in `memory`.  n = 0: FI_OK, nothing written.  A NULL mesh, n < 0, NULL positions with n > 0, a bad mode or memory
+ * kind, FI_SAMPLE_NORMALS_VERTEX with normals asked of a mesh that has none, T = 0 with n > 0 (an empty mesh, or nothing of
+ * positive finite measure): FI_ERR_INVALID; n >= 2^31: FI_ERR_UNSUPPORTED.
+ *
+ * fi_mesh_deviation: two lists of queries against surface b -- the `samples` points of fi_mesh_sample(a, samples, seed), in
+ * sample order (skipped when samples == 0 or of_samples is NULL; a mesh with nothing to sample: all of of_samples zero and
+ * at = -1, no error), and the used vertices of a (those some primitive references), in ascending index order.  Every query's
+ * d is what fi_surface_distance(b, ..., max_distance) returns for it.  A finite d is counted, +inf goes to `beyond`, NaN (a
+ * non-finite vertex) to `invalid`.  max = the largest counted d, at = the first query that holds it, where = its position;
+ * S1 = sum (double)d, S2 = sum (double)d (double)d over the list, uncounted entries contributing 0.0, both in a fixed order:
+ * every block of 256 consecutive queries by the tree s[t] += s[t + w], w = 128, 64, ..., 1 (the tail padded with 0.0), the
+ * block sums then added one after the other, ascending, from 0.0; mean = S1 / counted, rms = sqrt(S2 / counted); all three 0
+ * when nothing is counted.  vertex_distances: float[a's vertex count] in `memory` or NULL, d for a used vertex and NaN for an
+ * unused one.  The two structs are host memory.  NULL a or b; both structs and vertex_distances NULL; meshes of different
+ * dimension or on different devices; samples < 0; a NaN or negative max_distance; a bad memory kind: FI_ERR_INVALID;
+ * samples >= 2^31: FI_ERR_UNSUPPORTED.
+ * No floating-point atomics and no atomics writing an output: a repeated call returns the same bytes.  Not offered: a walk
+ * fused with the sampler, blue-noise or Poisson-disk spacing, per-vertex attribute transfer, slab groups (merge the pieces
+ * first), 1-D. */
+#define FI_SAMPLE_NORMALS_FACE   0
+#define FI_SAMPLE_NORMALS_VERTEX 1
+typedef struct fi_deviation {
+	long long queries, counted, beyond, invalid, at;  /* at: the first query holding max; -1 when counted == 0 */
+	double    max, mean, rms;
+	float     where[3];                               /* that query's position (2-D: where[2] = 0) */
+} fi_deviation;
+int fi_mesh_sample(const fi_mesh* m, long n, unsigned long long seed, int normals_mode, float* positions, float* normals,
+                   long long* primitives, int memory);
+int fi_mesh_deviation(const fi_mesh* a, fi_surface* b, long samples, unsigned long long seed, float max_distance,
+                      fi_deviation* of_samples, fi_deviation* of_vertices, float* vertex_distances, int memory);
+
 /* ---- point queries: values and gradients at arbitrary positions --------------------------------
  * The contract ("Point queries") is this project's own:
  *   - positions: n points of ndim fp32 values, interleaved, in global lattice coordinates (x fastest, as fi_add_points);
@@ -848,7 +903,6 @@ int fi_points_orient_normals(fi_points* points, int k, float max_distance, int a
  * the device it was created on. */
 #define FI_SURFACE_ISO 0  /* the mesh of fi_iso_extract: inside is f < iso */
 #define FI_SURFACE_DUAL 1 /* the mesh of fi_dual_contour with central differences: inside is f - iso <= 0 */
-typedef struct fi_surface fi_surface;
 int fi_surface_create(fi_surface** out, int ndim, long num_vertices, const float* vertices, long num_primitives,
                       const int* indices, int memory);
 /* the same from a mesh of fi_iso_extract* / fi_dual_contour* on the device (no host round trip) */

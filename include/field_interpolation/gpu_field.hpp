@@ -117,6 +117,15 @@ public:
 	bool iso_surface_smoothed(float iso, bool dual, int iterations, float lambda, float mu, float max_move, int largest, double min_size,
 	                          std::vector<float>* vertices, std::vector<int>* indices, std::vector<float>* normals = nullptr) const;
 
+	// `n` oriented points spread over iso_surface (dual = false) or dual_contour (dual = true) of the last solution by area
+	// (2-D: by length), made on the device with one copy to the host at the end: positions and, if asked, normals (the
+	// extractor's vertex normals interpolated and normalised, FI_SAMPLE_NORMALS_VERTEX), ndim floats per point, in ascending
+	// primitive order; the same `seed` gives the same points.  What sdf_from_points wants of another lattice: a field re-fitted
+	// or re-meshed at another resolution.  The contract is include/fi_hip.h fi_mesh_sample.  false: no solution yet, a surface
+	// with nothing to sample, or the library refused the call.
+	bool iso_surface_points(float iso, bool dual, long n, unsigned long long seed, std::vector<float>* positions,
+	                        std::vector<float>* normals = nullptr) const;
+
 	// Values (and, if asked, gradients: ndim floats per point) of the last solution at `positions` (ndim floats per point,
 	// global lattice coordinates, x fastest), sampled where the solution lives on the device: multilinear, or Catmull-Rom
 	// with cubic = true; points outside the lattice get NaN.  The contract is include/fi_hip.h fi_sample.  false: no
