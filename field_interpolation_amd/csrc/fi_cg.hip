@@ -582,11 +582,9 @@ void cg_run(RankSet& R, int max_iterations, float tol)
 {
 	fi_ctx* c0 = R[0];
 	hipStream_t st = c0->stream;
-	if (max_iterations <= 0) {
-		const int64_t dflt = 2 * static_cast<int64_t>(c0->g.gn[0]) * c0->g.gn[1] * c0->g.gn[2];  // Eigen: 2 * cols
-		max_iterations = dflt > std::numeric_limits<int>::max() ? std::numeric_limits<int>::max() : static_cast<int>(dflt);
-	}
-	const double tolerance = tol > 0 ? static_cast<double>(tol) : static_cast<double>(std::numeric_limits<float>::epsilon());
+	SolveFrame frame(R, max_iterations, tol);
+	max_iterations = frame.max_iterations;
+	const double tolerance = frame.tolerance;
 
 	// A level of a coarse-to-fine start that has just been solved WITHOUT a look at its stop flag (below): what the flag
 	// said comes in now -- the copy went to pinned memory behind that solve's last kernel, long since done.
@@ -618,9 +616,7 @@ void cg_run(RankSet& R, int max_iterations, float tol)
 	                       c0->last_cg_iterations <= max_iterations && c0->last_cg_iterations <= 64 && c0->last_cg_tol == tolerance && !test_switch("FI_LOOK_ALWAYS");
 	c0->last_cg_tol = tolerance;
 
-	EventPair timer;  // (destroyed on every way out: a coarse level's breakdown, a timeout)
-	const hipEvent_t e0 = timer.e0, e1 = timer.e1;
-	if (!unwatched) { FI_HIP_TRY(hipEventRecord(e0, st)); }
+	if (!unwatched) { frame.begin(); }  // (an unwatched solve returns before anybody asks for the time)
 
 	CgScalars init{};
 	init.tol2     = tolerance * tolerance;
@@ -631,29 +627,22 @@ void cg_run(RankSet& R, int max_iterations, float tol)
 	auto nb_apply  = [](fi_ctx* c) { return apply_num_partials(c); };
 	auto zero      = [](fi_ctx*) { return 0; };
 
-	// r0 = b - A x0
-	halo_exchange(R, &fi_ctx::x);
-	for (fi_ctx* c : R) { apply_AtA(c, c->x.p, c->q.p, nullptr); }
-	for (fi_ctx* c : R) {
-		const int64_t o = c->g.own_first;
-		hipLaunchKernelGGL((k_cg_init<T>), dim3(nbv(c)), dim3(kThreads), 0, c->stream, c->g.nown, c->atb.as<T>() + o,
-		                   c->q.as<T>() + o, c->dinv.as<T>() + o, c->r.as<T>() + o, c->p.as<T>() + o,
-		                   c->partial.as<double>(), nbv(c));
-	}
+	// r = b - A x, p = Dinv r and their partials: the start (r0 = b - A x0) and the residual replacement
+	auto true_residual = [&]() {
+		halo_exchange(R, &fi_ctx::x);
+		for (fi_ctx* c : R) { apply_AtA(c, c->x.p, c->q.p, nullptr); }
+		for (fi_ctx* c : R) {
+			const int64_t o = c->g.own_first;
+			hipLaunchKernelGGL((k_cg_init<T>), dim3(nbv(c)), dim3(kThreads), 0, c->stream, c->g.nown, c->atb.as<T>() + o,
+			                   c->q.as<T>() + o, c->dinv.as<T>() + o, c->r.as<T>() + o, c->p.as<T>() + o,
+			                   c->partial.as<double>(), nbv(c));
+		}
+	};
+	true_residual();
 	reduce_phase(R, 3, nbv, nbv, kPhaseInit);
 
 	int samples = 0;
-	while (static_cast<int>(c0->ev.size()) < 2 * kMaxSamples) {
-		hipEvent_t e;
-		FI_HIP_TRY(hipEventCreate(&e));
-		c0->ev.push_back(e);
-	}
-	// wall-clock guard: a solve that cannot reach its tolerance (fp32 stagnation with the default 2N
-	// iteration cap) must not hold the GPU for hours.  FI_SOLVE_TIMEOUT_S overrides the 600 s default.
-	double limit_s = 600.0;
-	if (const char* env = getenv("FI_SOLVE_TIMEOUT_S")) { limit_s = atof(env); }
-	const auto wall0 = std::chrono::steady_clock::now();
-	bool timed_out = false;
+	top_up_events(c0->ev, 2 * kMaxSamples);
 	CgScalars* sc0 = c0->scal.as<CgScalars>();
 	auto vec_ok = [](fi_ctx* c) {
 		constexpr int N = Vec16<T>::N;
@@ -662,7 +651,30 @@ void cg_run(RankSet& R, int max_iterations, float tol)
 	// one context, one process: the dot-product reductions are folded into the vector kernels (3 launches per step)
 	const bool folded = R.size() == 1 && c0->nranks == 1 && !tuning_switch("FI_NO_FOLD");
 	const bool folded_set = !folded && !tuning_switch("FI_NO_FOLD");  // slabs: the same kernels behind a reduction over the rank set
+	auto nbf_of = [&](fi_ctx* c) { return nbv(c) > 1024 ? 1024 : nbv(c); };  // folded: every block re-reads all partials: keep them few
 	int issued = 0;         // CG steps enqueued so far (the device runs step k only while it is not done)
+	// the halves of a step on one member, in the kernel's 16-byte or scalar form.  pq / npq: the apply's p.q partials, or
+	// their sum over the slabs in slot 2; the residual's partials go to `pr` (folded: a region of their own, the apply's
+	// are still being read) and come back to the second half from `sums` / `nsums`
+	auto resid_f = [&](fi_ctx* c, const double* pq, int npq) {
+		const int64_t o   = c->g.own_first;
+		const int     nbf = nbf_of(c);
+		CgScalars*    sc  = c->scal.as<CgScalars>();
+		auto go = [&](auto kernel) {
+			hipLaunchKernelGGL(kernel, dim3(nbf), dim3(kThreads), 0, c->stream, c->g.nown, sc, sc + 1, issued, pq, npq,
+			                   c->q.as<T>() + o, c->dinv.as<T>() + o, c->r.as<T>() + o, c->partial.as<double>() + c->max_blocks, nbf);
+		};
+		if (vec_ok(c)) { go(k_cg_resid_f<T, true>); } else { go(k_cg_resid_f<T, false>); }
+	};
+	auto xp_f = [&](fi_ctx* c, const double* sums, int nsums) {
+		const int64_t o  = c->g.own_first;
+		CgScalars*    sc = c->scal.as<CgScalars>();
+		auto go = [&](auto kernel) {
+			hipLaunchKernelGGL(kernel, dim3(nbf_of(c)), dim3(kThreads), 0, c->stream, c->g.nown, sc + 1, sc, issued, sums, nsums,
+			                   c->r.as<T>() + o, c->dinv.as<T>() + o, c->x.as<T>() + o, c->p.as<T>() + o);
+		};
+		if (vec_ok(c)) { go(k_cg_xp_f<T, true>); } else { go(k_cg_xp_f<T, false>); }
+	};
 	int restarts_left = c0->verify_residual ? 3 : 0;
 	// Coarser levels of a coarse-to-fine start (launches of 2-25 us: the host issues them no faster than the GPU retires
 	// them): the first look at the stop flag comes when this level's previous solve had finished -- a re-assembled problem
@@ -689,8 +701,7 @@ void cg_run(RankSet& R, int max_iterations, float tol)
 		}
 		++looks;
 		if (!skip_look) {
-			FI_HIP_TRY(hipMemcpyAsync(c0->scal_host, sc0, sizeof(CgScalars), hipMemcpyDeviceToHost, st));
-			FI_HIP_TRY(hipStreamSynchronize(st));
+			frame.look(sc0);
 		} else {
 			c0->scal_host->done = 0;
 		}
@@ -704,21 +715,11 @@ void cg_run(RankSet& R, int max_iterations, float tol)
 			for (fi_ctx* c : R) {  // the apply kernels exit at once while the flag is up
 				hipLaunchKernelGGL(k_set_done, dim3(1), dim3(1), 0, c->stream, c->scal.as<CgScalars>(), 0);
 			}
-			halo_exchange(R, &fi_ctx::x);
-			for (fi_ctx* c : R) { apply_AtA(c, c->x.p, c->q.p, nullptr); }
-			for (fi_ctx* c : R) {
-				const int64_t o = c->g.own_first;
-				hipLaunchKernelGGL((k_cg_init<T>), dim3(nbv(c)), dim3(kThreads), 0, c->stream, c->g.nown, c->atb.as<T>() + o,
-				                   c->q.as<T>() + o, c->dinv.as<T>() + o, c->r.as<T>() + o, c->p.as<T>() + o,
-				                   c->partial.as<double>(), nbv(c));
-			}
+			true_residual();
 			reduce_phase(R, 2, nbv, nbv, kPhaseRestart);
 			continue;
 		}
-		if (timed_out_anywhere(R, std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() > limit_s)) {
-			timed_out = true;
-			break;
-		}
+		if (frame.guard(R)) { break; }
 		// (a coarser level of a coarse-to-fine start is done within a few steps: shorter bursts between two looks at the flag
 		// leave fewer launches behind that only find the flag up -- 31 of 48 iterations of config 4's three levels)
 		int burst = kCheckEvery;
@@ -737,128 +738,50 @@ void cg_run(RankSet& R, int max_iterations, float tol)
 				++samples;
 			}
 			if (folded) {
-				fi_ctx* c = c0;
-				const int64_t o   = c->g.own_first;
-				const int     nbf = nbv(c) > 1024 ? 1024 : nbv(c);  // every block re-reads all partials: keep them few
-				CgScalars*    sc  = c->scal.as<CgScalars>();
-				double*       pp  = c->partial.as<double>();
-				double*       pr  = pp + c->max_blocks;  // the apply partials are still being read: separate region
-				if (vec_ok(c)) {
-					hipLaunchKernelGGL((k_cg_resid_f<T, true>), dim3(nbf), dim3(kThreads), 0, st, c->g.nown, sc, sc + 1, issued, pp,
-					                   nb_apply(c), c->q.as<T>() + o, c->dinv.as<T>() + o, c->r.as<T>() + o, pr, nbf);
-					hipLaunchKernelGGL((k_cg_xp_f<T, true>), dim3(nbf), dim3(kThreads), 0, st, c->g.nown, sc + 1, sc, issued, pr, nbf,
-					                   c->r.as<T>() + o, c->dinv.as<T>() + o, c->x.as<T>() + o, c->p.as<T>() + o);
-				} else {
-					hipLaunchKernelGGL((k_cg_resid_f<T, false>), dim3(nbf), dim3(kThreads), 0, st, c->g.nown, sc, sc + 1, issued, pp,
-					                   nb_apply(c), c->q.as<T>() + o, c->dinv.as<T>() + o, c->r.as<T>() + o, pr, nbf);
-					hipLaunchKernelGGL((k_cg_xp_f<T, false>), dim3(nbf), dim3(kThreads), 0, st, c->g.nown, sc + 1, sc, issued, pr, nbf,
-					                   c->r.as<T>() + o, c->dinv.as<T>() + o, c->x.as<T>() + o, c->p.as<T>() + o);
-				}
+				resid_f(c0, c0->partial.as<double>(), nb_apply(c0));
+				xp_f(c0, c0->partial.as<double>() + c0->max_blocks, nbf_of(c0));
 				continue;
 			}
 			if (folded_set) {
 				// rank sets: the folded kernels on every member, fed with the dot products summed over the slabs
-				auto nbf_of = [&](fi_ctx* c) { return nbv(c) > 1024 ? 1024 : nbv(c); };
 				reduce_to_slot2(R, 1, nb_apply, zero, +[](fi_ctx* c) -> const double* { return c->partial.as<double>(); });
-				for (fi_ctx* c : R) {
-					const int64_t o   = c->g.own_first;
-					const int     nbf = nbf_of(c);
-					CgScalars*    sc  = c->scal.as<CgScalars>();
-					double*       pr  = c->partial.as<double>() + c->max_blocks;
-					if (vec_ok(c)) {
-						hipLaunchKernelGGL((k_cg_resid_f<T, true>), dim3(nbf), dim3(kThreads), 0, c->stream, c->g.nown, sc, sc + 1, issued,
-						                   (sc + 2)->sums, 1, c->q.as<T>() + o, c->dinv.as<T>() + o, c->r.as<T>() + o, pr, nbf);
-					} else {
-						hipLaunchKernelGGL((k_cg_resid_f<T, false>), dim3(nbf), dim3(kThreads), 0, c->stream, c->g.nown, sc, sc + 1, issued,
-						                   (sc + 2)->sums, 1, c->q.as<T>() + o, c->dinv.as<T>() + o, c->r.as<T>() + o, pr, nbf);
-					}
-				}
+				for (fi_ctx* c : R) { resid_f(c, (c->scal.as<CgScalars>() + 2)->sums, 1); }
 				reduce_to_slot2(R, 2, nbf_of, nbf_of,
 				                +[](fi_ctx* c) -> const double* { return c->partial.as<double>() + c->max_blocks; });
-				for (fi_ctx* c : R) {
-					const int64_t o   = c->g.own_first;
-					const int     nbf = nbf_of(c);
-					CgScalars*    sc  = c->scal.as<CgScalars>();
-					if (vec_ok(c)) {
-						hipLaunchKernelGGL((k_cg_xp_f<T, true>), dim3(nbf), dim3(kThreads), 0, c->stream, c->g.nown, sc + 1, sc, issued,
-						                   (sc + 2)->sums, 1, c->r.as<T>() + o, c->dinv.as<T>() + o, c->x.as<T>() + o, c->p.as<T>() + o);
-					} else {
-						hipLaunchKernelGGL((k_cg_xp_f<T, false>), dim3(nbf), dim3(kThreads), 0, c->stream, c->g.nown, sc + 1, sc, issued,
-						                   (sc + 2)->sums, 1, c->r.as<T>() + o, c->dinv.as<T>() + o, c->x.as<T>() + o, c->p.as<T>() + o);
-					}
-				}
+				for (fi_ctx* c : R) { xp_f(c, (c->scal.as<CgScalars>() + 2)->sums, 1); }
 				continue;
 			}
 			reduce_phase(R, 1, nb_apply, zero, kPhaseSpmv);
 			for (fi_ctx* c : R) {
 				const int64_t o = c->g.own_first;
-				if (vec_ok(c)) {
-					hipLaunchKernelGGL((k_cg_resid<T, true>), dim3(nbv(c)), dim3(kThreads), 0, c->stream, c->g.nown,
-					                   c->scal.as<CgScalars>(), c->q.as<T>() + o, c->dinv.as<T>() + o, c->r.as<T>() + o,
-					                   c->partial.as<double>(), nbv(c));
-				} else {
-					hipLaunchKernelGGL((k_cg_resid<T, false>), dim3(nbv(c)), dim3(kThreads), 0, c->stream, c->g.nown,
-					                   c->scal.as<CgScalars>(), c->q.as<T>() + o, c->dinv.as<T>() + o, c->r.as<T>() + o,
-					                   c->partial.as<double>(), nbv(c));
-				}
+				auto go = [&](auto kernel) {
+					hipLaunchKernelGGL(kernel, dim3(nbv(c)), dim3(kThreads), 0, c->stream, c->g.nown, c->scal.as<CgScalars>(),
+					                   c->q.as<T>() + o, c->dinv.as<T>() + o, c->r.as<T>() + o, c->partial.as<double>(), nbv(c));
+				};
+				if (vec_ok(c)) { go(k_cg_resid<T, true>); } else { go(k_cg_resid<T, false>); }
 			}
 			reduce_phase(R, 2, nbv, nbv, kPhaseUpdate);
 			for (fi_ctx* c : R) {
 				const int64_t o = c->g.own_first;
-				if (vec_ok(c)) {
-					hipLaunchKernelGGL((k_cg_xp<T, true>), dim3(nbv(c)), dim3(kThreads), 0, c->stream, c->g.nown,
-					                   c->scal.as<CgScalars>(), issued, c->r.as<T>() + o, c->dinv.as<T>() + o,
-					                   c->x.as<T>() + o, c->p.as<T>() + o);
-				} else {
-					hipLaunchKernelGGL((k_cg_xp<T, false>), dim3(nbv(c)), dim3(kThreads), 0, c->stream, c->g.nown,
-					                   c->scal.as<CgScalars>(), issued, c->r.as<T>() + o, c->dinv.as<T>() + o,
-					                   c->x.as<T>() + o, c->p.as<T>() + o);
-				}
+				auto go = [&](auto kernel) {
+					hipLaunchKernelGGL(kernel, dim3(nbv(c)), dim3(kThreads), 0, c->stream, c->g.nown, c->scal.as<CgScalars>(), issued,
+					                   c->r.as<T>() + o, c->dinv.as<T>() + o, c->x.as<T>() + o, c->p.as<T>() + o);
+				};
+				if (vec_ok(c)) { go(k_cg_xp<T, true>); } else { go(k_cg_xp<T, false>); }
 			}
 		}
 		FI_HIP_TRY(hipGetLastError());
 	}
-	FI_HIP_TRY(hipEventRecord(e1, st));
-	FI_HIP_TRY(hipEventSynchronize(e1));
-	float ms = 0;
-	FI_HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-
-	const CgScalars h = *c0->scal_host;
+	const CgScalars h = frame.end();
 	int used = samples;  // samples of iterations that actually ran (kernels of later iterations exited on the flag)
 	if ((h.iter + 3) / 4 < used) { used = (h.iter + 3) / 4; }  // sample k belongs to iteration 4k + 1
-	double sum_ms = 0;
-	for (int k = 0; k < used; ++k) {
-		float t = 0;
-		FI_HIP_TRY(hipEventElapsedTime(&t, c0->ev[2 * k], c0->ev[2 * k + 1]));
-		sum_ms += t;
-	}
+	frame.stats<T>(R, h, used, !c0->verify_residual);
 	for (fi_ctx* c : R) {
-		c->stats.spmv_samples = used;
-		c->stats.spmv_ms_avg  = used ? sum_ms / used : 0.0;
-		c->stats.spmv_bytes   = apply_algorithmic_bytes(c);
-		c->stats.prec_samples = 0;
-		c->stats.prec_ms_avg  = 0.0;
-		c->stats.prec_bytes   = 0.0;
-		c->stats.operator_applies = h.iter + 1 + h.restarts;
-		c->stats.solve_ms     = ms;
-		c->stats.iterations   = h.iter;
-		c->last_cg_iterations = timed_out ? 0 : h.iter;  // the same on every rank: the scalars are sums over all of them
-		c->cg_count_recalled  = false;                   // (this context's own history from here on)
-		if (R.size() == 1 && c->level > 0 && !timed_out && (h.done == 1 || h.done == 5)) { remember_iterations(c, 0, tolerance, h.iter); }
-		// with the verified stop on, "converged" means b - A x itself met the tolerance (done == 5); a recurrence
-		// that converged while the true residual stagnated above it (fp32 on an ill-conditioned system) is not
-		c->stats.converged    = (!timed_out && (h.done == 4 || h.done == 5 || (h.done == 1 && !c0->verify_residual))) ? 1 : 0;
-		c->stats.rel_residual = h.bb > 0 ? std::sqrt(h.rr / h.bb) : 0.0;
-		c->stats.restarts     = h.restarts;
-		c->stats.verified_residual = (h.restarts > 0 && h.bb > 0) ? std::sqrt(h.true_rr / h.bb) : -1.0;
-		residual_rule_stats(c->stats);
-		if (h.done == 4) {  // rhs == 0  ->  x = 0 (Eigen's early return)
-			FI_HIP_TRY(hipMemsetAsync(c->x.p, 0, sizeof(T) * c->g.nloc, c->stream));
-		}
+		c->last_cg_iterations = frame.timed_out ? 0 : h.iter;  // the same on every rank: the scalars are sums over all of them
+		c->cg_count_recalled  = false;                         // (this context's own history from here on)
+		if (R.size() == 1 && c->level > 0 && !frame.timed_out && (h.done == 1 || h.done == 5)) { remember_iterations(c, 0, tolerance, h.iter); }
 	}
-	FI_REQUIRE(h.done != 2, FI_ERR_BREAKDOWN, "CG breakdown: non-finite or non-positive curvature (p.AtA p = %g)", h.pq);
-	FI_REQUIRE(!timed_out, FI_ERR_TIMEOUT, "solve stopped by the wall-clock guard (FI_SOLVE_TIMEOUT_S = %g s) after %d iterations, "
-	           "relative residual %g", limit_s, h.iter, h.bb > 0 ? std::sqrt(h.rr / h.bb) : 0.0);
+	frame.require_ok(h);
 }
 
 template <typename T>

@@ -1,6 +1,7 @@
 // fi_multigrid.hip -- the coarse-to-fine start (src/sdf_field.cpp:272-288 generalised to several levels), the smoothers,
 // the V-cycle and V-cycle preconditioned CG (fp64 CG around an fp32 V-cycle in mixed precision).
 #include "fi_solver_internal.h"
+#include "fi_cheb.h"
 
 namespace fi {
 
@@ -602,8 +603,8 @@ void swap_vectors(RankSet& R, Vec a, Vec b)
 template <typename T>
 void cheb_smooth_fused(RankSet& R, Vec b, Vec x, int degree, double ratio, bool from_zero)
 {
-	const double hi = 1.1 * R[0]->lambda_max, lo = hi / ratio;
-	const double theta = 0.5 * (hi + lo), delta = 0.5 * (hi - lo), sigma = theta / delta;
+	const ChebInterval iv(R[0]->lambda_max, ratio);
+	const double theta = iv.theta;
 	const Vec ring[3] = {x, &fi_ctx::mg_d, &fi_ctx::mg_r};
 	int cur = 0, prev = -1;  // ring positions of x_k and x_{k-1} (-1: x_{k-1} = 0, or the first step of a smoother that starts at x)
 	auto step = [&](double a, double c1, double c2) {
@@ -627,14 +628,12 @@ void cheb_smooth_fused(RankSet& R, Vec b, Vec x, int degree, double ratio, bool 
 		step(1.0, 0.0, 1.0 / theta);  // x_1 = x_0 + Dinv (b - A x_0) / theta
 		have_prev = true;
 	}
-	double rho = 1.0 / sigma;
+	ChebRecurrence rec(iv);
 	for (int k = 1; k < degree; ++k) {
-		const double rho_new = 1.0 / (2.0 * sigma - rho);
-		const double c1 = rho_new * rho, c2 = 2.0 * rho_new / delta;
+		rec.next();
 		if (!have_prev) { prev = -1; }  // x_0 = 0: its term drops out, a = 1 + c1 stays
-		step(1.0 + c1, c1, c2);
+		step(1.0 + rec.c1, rec.c1, rec.c2);
 		have_prev = true;
-		rho = rho_new;
 	}
 	swap_vectors(R, x, ring[cur]);
 }
@@ -647,8 +646,8 @@ void cheb_smooth(RankSet& R, Vec b, Vec x, int degree, double ratio, bool from_z
 		cheb_smooth_fused<T>(R, b, x, degree, ratio, from_zero);
 		return;
 	}
-	const double hi = 1.1 * R[0]->lambda_max, lo = hi / ratio;
-	const double theta = 0.5 * (hi + lo), delta = 0.5 * (hi - lo), sigma = theta / delta;
+	const ChebInterval iv(R[0]->lambda_max, ratio);
+	const double theta = iv.theta;
 	auto nbv = [](fi_ctx* c) { return stream_blocks(c->g.nown); };
 	if (from_zero) {
 		// x == d and r == b until the first update: only d is written (straight into x when the polynomial ends here)
@@ -665,9 +664,9 @@ void cheb_smooth(RankSet& R, Vec b, Vec x, int degree, double ratio, bool from_z
 			                   vown<T>(c, &fi_ctx::mg_d), vown<T>(c, x), static_cast<T>(1.0 / theta), 0);
 		}
 	}
-	double rho = 1.0 / sigma;
+	ChebRecurrence rec(iv);
 	for (int k = 1; k < degree; ++k) {
-		const double rho_new = 1.0 / (2.0 * sigma - rho);
+		rec.next();
 		apply_all(R, &fi_ctx::mg_d, &fi_ctx::q, false);
 		const bool first = from_zero && k == 1, last = k == degree - 1;
 		for (fi_ctx* c : R) {
@@ -676,9 +675,8 @@ void cheb_smooth(RankSet& R, Vec b, Vec x, int degree, double ratio, bool from_z
 			hipLaunchKernelGGL((k_cheb_iter<T>), dim3(nbv(c)), dim3(kThreads), 0, c->stream, c->g.nown, vown<T>(c, &fi_ctx::q),
 			                   vown<T>(c, &fi_ctx::dinv), first ? static_cast<const T*>(vown<T>(c, b)) : static_cast<const T*>(r), r,
 			                   d, first ? static_cast<const T*>(d) : static_cast<const T*>(vown<T>(c, x)), vown<T>(c, x),
-			                   static_cast<T>(rho_new * rho), static_cast<T>(2.0 * rho_new / delta), last ? 0 : 1);
+			                   static_cast<T>(rec.c1), static_cast<T>(rec.c2), last ? 0 : 1);
 		}
-		rho = rho_new;
 	}
 }
 
@@ -733,9 +731,8 @@ Vec poly_chain(RankSet& R, Vec r, Vec za, Vec zb, double* chain_bytes = nullptr,
 	// (vcycle), delivered when that step runs in the marching kernel on one undivided context
 	if (dotv && !(onto && R.size() == 1 && c0->nranks == 1 && c0->march.valid && !stencil_cheb_direct(c0))) { dotv = nullptr; }
 	c0->bx_dot_done = dotv != nullptr;
-	const double lam = c0->poly_lambda > 1.0 ? c0->poly_lambda : 1.0;
-	const double hi = 1.1 * lam, lo = hi / mg_poly_ratio(c0);
-	const double theta = 0.5 * (hi + lo), delta = 0.5 * (hi - lo), sigma = theta / delta;
+	const ChebInterval iv(c0->poly_lambda > 1.0 ? c0->poly_lambda : 1.0, mg_poly_ratio(c0));
+	const double theta = iv.theta;
 	const bool single = R.size() == 1 && c0->nranks == 1;
 	bool ghosts_scaled = true;
 	for (const fi_ctx* c : R) { ghosts_scaled = ghosts_scaled && c->scaling_ghosts; }
@@ -783,10 +780,10 @@ Vec poly_chain(RankSet& R, Vec r, Vec za, Vec zb, double* chain_bytes = nullptr,
 			return base + ((d & 1) ? 2 * static_cast<size_t>(c->g.nloc) : 0);
 		};
 		const unsigned short* sc = c->dinv16s.as<unsigned short>();
-		double rho = 1.0 / sigma;
+		ChebRecurrence rec(iv);
 		for (int k = 1; k <= n; ++k) {
-			const double rho_new = 1.0 / (2.0 * sigma - rho);
-			const double c1 = rho_new * rho, c2 = 2.0 * rho_new / delta;
+			rec.next();
+			const double c1 = rec.c1, c2 = rec.c2;
 			void* out = k == n ? (onto ? (c->*onto).p : (c->*zb).p) : where(k);
 			const int fmt = (k > 1 ? 1 : 0) | (k > 2 ? 2 : 0) | (k < n ? 4 : 0);
 			if (k == 1) {
@@ -796,7 +793,6 @@ Vec poly_chain(RankSet& R, Vec r, Vec za, Vec zb, double* chain_bytes = nullptr,
 				                  k == 2 ? 1.0 / theta : 0.0, 0.0, sc, 0, fmt, k == n && onto ? (c->*onto).p : nullptr,
 				                  k == n && dotv ? (c->*dotv).p : nullptr);
 			}
-			rho = rho_new;
 		}
 		return onto ? onto : zb;
 	}
@@ -808,10 +804,10 @@ Vec poly_chain(RankSet& R, Vec r, Vec za, Vec zb, double* chain_bytes = nullptr,
 	const int  deep_width = 2 * (terms - 1);
 	const bool deep = pro && c0->nranks > 1 && c0->halo >= deep_width && c0->min_slab >= deep_width && !test_switch("FI_NO_DEEP_HALO");
 	Vec zin = za, zout = zb;
-	double rho = 1.0 / sigma;
+	ChebRecurrence rec(iv);
 	for (int k = 1; k < terms; ++k) {
-		const double rho_new = 1.0 / (2.0 * sigma - rho);
-		const double c1 = rho_new * rho, c2 = 2.0 * rho_new / delta;
+		rec.next();
+		const double c1 = rec.c1, c2 = rec.c2;
 		const bool   first_on_load = pro && k == 1;
 		const int    ext = deep ? 2 * (terms - 1 - k) : 0;  // ghost planes this step computes for the next one
 		if (deep) {
@@ -832,7 +828,6 @@ Vec poly_chain(RankSet& R, Vec r, Vec za, Vec zb, double* chain_bytes = nullptr,
 			}
 		}
 		std::swap(zin, zout);
-		rho = rho_new;
 	}
 	return onto ? onto : zin;
 }
@@ -864,31 +859,29 @@ struct TailProgram {
 	{
 		fi_ctx* c = chain[l];
 		const int    terms = mg_poly_terms(c);
-		const double lam = c->poly_lambda > 1.0 ? c->poly_lambda : 1.0;
-		const double hi = 1.1 * lam, lo = hi / mg_poly_ratio(c);
-		const double theta = 0.5 * (hi + lo), delta = 0.5 * (hi - lo), sigma = theta / delta;
+		const ChebInterval iv(c->poly_lambda > 1.0 ? c->poly_lambda : 1.0, mg_poly_ratio(c));
+		const double theta = iv.theta;
 		const unsigned short* sc = c->dinv16s.as<unsigned short>();
 		const int W[2] = {vec(l, W0), vec(l, W1)};
 		if (terms < 2 || !c->dinv16s_valid) { ok = false; return; }
 		op(kTailScale, l, vec(l, r), -1, -1, W[0], -1, sc, 1.0 / theta);
 		int cur = 0;
-		double rho = 1.0 / sigma;
+		ChebRecurrence rec(iv);
 		for (int k = 1; k < terms; ++k) {
-			const double rho_new = 1.0 / (2.0 * sigma - rho);
-			const double c1 = rho_new * rho, c2 = 2.0 * rho_new / delta;
+			rec.next();
+			const double c1 = rec.c1, c2 = rec.c2;
 			const bool   last = k == terms - 1;
 			op(kTailPolyStep, l, W[cur], k == 1 ? -1 : W[1 - cur], vec(l, r), last ? (out >= 0 ? vec(l, out) : -1) : W[1 - cur],
 			   last && acc >= 0 ? vec(l, acc) : -1, sc, 1.0 + c1, k == 1 ? 0.0 : c1, c2);
 			cur = 1 - cur;
-			rho = rho_new;
 		}
 	}
 	// degree-k Chebyshev smoothing in the full operator (cheb_smooth_fused): X starts at zero / at its present value
 	void cheb_ops(int l, int degree, double ratio, bool from_zero)
 	{
 		fi_ctx* c = chain[l];
-		const double hi = 1.1 * c->lambda_max, lo = hi / ratio;
-		const double theta = 0.5 * (hi + lo), delta = 0.5 * (hi - lo), sigma = theta / delta;
+		const ChebInterval iv(c->lambda_max, ratio);
+		const double theta = iv.theta;
 		const unsigned short* sc = c->dinv16.as<unsigned short>();
 		const int b = vec(l, B), x = vec(l, X);
 		const int W[3] = {vec(l, W0), vec(l, W1), vec(l, Rr)};   // (the residual vector is free while a smoother runs)
@@ -904,10 +897,10 @@ struct TailProgram {
 			zk = W[0];
 			zp = x;
 		}
-		double rho = 1.0 / sigma;
+		ChebRecurrence rec(iv);
 		for (int k = 1; k <= steps; ++k) {
-			const double rho_new = 1.0 / (2.0 * sigma - rho);
-			const double c1 = rho_new * rho, c2 = 2.0 * rho_new / delta;
+			rec.next();
+			const double c1 = rec.c1, c2 = rec.c2;
 			const bool   last = k == steps;
 			// a stage reads its input's NEIGHBOURS: the output is a vector that is neither x_k nor (read at the point only, but
 			// by other threads' stages not at all) x_{k-1}'s: three work vectors rotate, the last step lands in X
@@ -920,7 +913,6 @@ struct TailProgram {
 			op(kTailChebStep, l, zk, zp, b, out, -1, sc, 1.0 + c1, zp >= 0 ? c1 : 0.0, c2);
 			zp = zk;
 			zk = out;
-			rho = rho_new;
 		}
 		if (zk != x) { ok = false; }  // (cannot happen: the last step writes X unless X is its own input, and it never is)
 	}
@@ -1573,24 +1565,18 @@ void cg_run_mg(RankSet& R, int max_iterations, float tol)
 	} else {
 		mg_prepare<T>(R, false);
 	}
-	if (max_iterations <= 0) {
-		const int64_t dflt = 2 * static_cast<int64_t>(c0->g.gn[0]) * c0->g.gn[1] * c0->g.gn[2];
-		max_iterations = dflt > std::numeric_limits<int>::max() ? std::numeric_limits<int>::max() : static_cast<int>(dflt);
-	}
+	SolveFrame frame(R, max_iterations, tol);
 	// FI_OPT_FIELD_TOLERANCE (an undivided lattice): the solve stops by the field (k_mg_logic, kMgResid); the residual rule
 	// stays as the floor of what the precision's recurrence can still tell apart
 	// Over slabs (a loop-back group's members or one slab per process, at most kFieldRanks of them) every slab's maxima
 	// travel with the r.r sum (CgScalars::rank_max): no collective of their own, and every rank decides on the same numbers.
 	const int  field_slabs = R.size() > 1 ? static_cast<int>(R.size()) : (c0->nranks > 1 ? c0->nranks : 0);
 	const bool by_field = c0->field_tol > 0 && field_slabs <= kFieldRanks && !replicated_copies(R);
-	const double tolerance = by_field ? (sizeof(T) == 8 ? 1e-13 : 2e-7)
-	                                  : (tol > 0 ? static_cast<double>(tol) : static_cast<double>(std::numeric_limits<float>::epsilon()));
-	EventPair timer;  // (destroyed on every way out: a coarse level's breakdown, a timeout)
-	const hipEvent_t e0 = timer.e0, e1 = timer.e1;
-	FI_HIP_TRY(hipEventRecord(e0, st));
+	const double tolerance = by_field ? (sizeof(T) == 8 ? 1e-13 : 2e-7) : frame.tolerance;
+	frame.begin();
 	CgScalars init{};
 	init.tol2      = tolerance * tolerance;
-	init.max_iter  = max_iterations;
+	init.max_iter  = frame.max_iterations;
 	init.field_tol = by_field ? c0->field_tol : 0.0;
 	init.field_est = -1.0;
 	init.field_ranks = by_field ? field_slabs : 0;
@@ -1602,11 +1588,7 @@ void cg_run_mg(RankSet& R, int max_iterations, float tol)
 	// (the step kernels' workgroup maxima: behind the r.r partials -- the array holds 4 x max_blocks doubles)
 	auto field_part = [&](fi_ctx* c) -> double* { return by_field ? c->partial.as<double>() + static_cast<size_t>(c->max_blocks) : nullptr; };
 	const Vec X = &fi_ctx::x, Rv = &fi_ctx::r, P = &fi_ctx::p, Z = &fi_ctx::mg_x, B = &fi_ctx::atb;
-	while (static_cast<int>(c0->ev.size()) < 2 * kMaxSamples) {
-		hipEvent_t e;
-		FI_HIP_TRY(hipEventCreate(&e));
-		c0->ev.push_back(e);
-	}
+	top_up_events(c0->ev, 2 * kMaxSamples);
 	int samples = 0;
 	const bool mixed = !Tw.empty();
 	// FI_OPT_MG_KCYCLE: where a level of the hierarchy IS a K-level the cycle depends on its argument and CG takes the flexible beta.
@@ -1623,11 +1605,7 @@ void cg_run_mg(RankSet& R, int max_iterations, float tol)
 	const Vec Q = flexible && !mixed && !start_level ? &fi_ctx::mg_b : &fi_ctx::q;
 	fi_ctx* const prec_ctx = mixed ? Tw[0] : c0;  // the context whose finest-level smoother chains are timed (vcycle)
 	if (prec_ctx->level == 0 && !(mixed ? replicated_copies(Tw) : replicated_copies(R))) {
-		while (static_cast<int>(prec_ctx->ev_prec.size()) < 2 * kPolySamples) {
-			hipEvent_t e;
-			FI_HIP_TRY(hipEventCreate(&e));
-			prec_ctx->ev_prec.push_back(e);
-		}
+		top_up_events(prec_ctx->ev_prec, 2 * kPolySamples);
 		prec_ctx->prec_budget = 1;  // (one chain per solve: every record is a marker the stream stops at, ~6 us each side)
 		prec_ctx->prec_taken  = 0;
 	}
@@ -1683,11 +1661,7 @@ void cg_run_mg(RankSet& R, int max_iterations, float tol)
 		}
 	};
 
-	auto read_flag = [&]() {
-		FI_HIP_TRY(hipMemcpyAsync(c0->scal_host, sc0, sizeof(CgScalars), hipMemcpyDeviceToHost, st));
-		FI_HIP_TRY(hipStreamSynchronize(st));
-		return c0->scal_host->done;
-	};
+	auto read_flag = [&]() { return frame.look(sc0).done; };
 	// r = b - A x, rr (b.b on the first call) and the stop test on it; unless that ends the solve: z = V(r), p = z, rz.
 	// Returns the stop flag.  (The flag is read BEFORE the V-cycle is spent: a verification that confirms the recurrence's
 	// residual -- the usual outcome -- costs one operator application, not a cycle.)
@@ -1756,10 +1730,6 @@ void cg_run_mg(RankSet& R, int max_iterations, float tol)
 	};
 	int done = restart();
 
-	double limit_s = 600.0;
-	if (const char* env = getenv("FI_SOLVE_TIMEOUT_S")) { limit_s = atof(env); }
-	const auto wall0 = std::chrono::steady_clock::now();
-	bool timed_out = false;
 	int restarts_left = (c0->verify_residual && !by_field) ? 3 : 0;  // (by the field: the recurrence of an fp64 CG is the residual)
 	int widenings_left = 2;
 	// One look at the stop flag per iteration, right behind the residual update: the V-cycle of an iteration that has just
@@ -1794,11 +1764,7 @@ void cg_run_mg(RankSet& R, int max_iterations, float tol)
 		}
 		// (over slabs the guard is an all-reduce and a host round trip: every eighth iteration -- the same ones on every rank --
 		// is often enough for a limit of minutes)
-		if ((c0->nranks == 1 || (steps & 7) == 7) &&
-		    timed_out_anywhere(R, std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() > limit_s)) {
-			timed_out = true;
-			break;
-		}
+		if ((c0->nranks == 1 || (steps & 7) == 7) && frame.guard(R)) { break; }
 		// the apply of the first two iterations is timed (fi_stats::spmv_ms_avg): an event record is a marker the stream stops
 		// at -- ~6 us on either side of the launch, 11 us per timed iteration: timing all five of config 4's cost the solve 1 %
 		const bool sample = samples < 2;
@@ -1910,19 +1876,14 @@ void cg_run_mg(RankSet& R, int max_iterations, float tol)
 		direction(0);
 		FI_HIP_TRY(hipGetLastError());
 	}
-	FI_HIP_TRY(hipEventRecord(e1, st));
-	FI_HIP_TRY(hipEventSynchronize(e1));
-	float ms = 0;
-	FI_HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-	if (tuning_switch("FI_MG_LOOP_DBG")) { std::fprintf(stderr, "cg_run_mg: %d host steps, predicted %d, device iterations %d\n", steps, predicted, c0->scal_host->iter); }
-	const CgScalars h = *c0->scal_host;
-	int used = samples < h.iter ? samples : h.iter;
-	double sum_ms = 0;
-	for (int k = 0; k < used; ++k) {
-		float t = 0;
-		FI_HIP_TRY(hipEventElapsedTime(&t, c0->ev[2 * k], c0->ev[2 * k + 1]));
-		sum_ms += t;
-	}
+	const CgScalars h = frame.end();
+	const bool timed_out = frame.timed_out;
+	if (tuning_switch("FI_MG_LOOP_DBG")) { std::fprintf(stderr, "cg_run_mg: %d host steps, predicted %d, device iterations %d\n", steps, predicted, h.iter); }
+	// by the field: met when the estimate says so -- or, in fp64, when the recurrence has reached the precision's floor (the
+	// field is then as converged as the arithmetic allows).  An fp32 solve that ends at ITS floor (2e-7) with the estimate
+	// above the tolerance has not delivered what was asked for: converged = 0, fi_stats::field_estimate says how far off.
+	const bool field_ok = by_field && h.done == 1 && ((h.field_est >= 0.0 && h.field_est <= h.field_tol) || sizeof(T) == 8);
+	frame.stats<T>(R, h, samples < h.iter ? samples : h.iter, by_field ? field_ok : !c0->verify_residual);
 	// the timed smoother chains of cycles that ran (cycle k belongs to iteration k: the first one to the start)
 	int pused = 0, plaunch = 0;
 	double psum = 0;
@@ -1938,42 +1899,26 @@ void cg_run_mg(RankSet& R, int max_iterations, float tol)
 		plaunch = prec_ctx->prec_chain_launches;
 	}
 	for (fi_ctx* c : R) {
-		c->stats.spmv_samples = used;
-		c->stats.spmv_ms_avg  = used ? sum_ms / used : 0.0;
-		c->stats.spmv_bytes   = apply_algorithmic_bytes(c);
 		// per LAUNCH, like the polynomial PCG's figures: a sample holds the launches of one chain
 		c->stats.prec_samples = pused * plaunch;
 		c->stats.prec_ms_avg  = pused && plaunch ? psum / (pused * plaunch) : 0.0;
 		c->stats.prec_bytes   = pused && plaunch ? prec_ctx->prec_chain_bytes / plaunch : 0.0;
-		c->stats.operator_applies = h.iter + 1 + h.restarts;
 		{
 			int ex = c0->n_halo_exchanges;
 			for (fi_ctx* l = (mixed ? Tw[0] : c0->coarse); l; l = l->coarse) { ex += l->n_halo_exchanges; }
 			c->stats.halo_exchanges = ex;
 		}
-		c->stats.solve_ms     = ms;
-		c->stats.iterations   = h.iter;
 		c->stats.reductions   = static_cast<int>((reduces_now() - reduces0) / (same_comm ? 2 : 1));
 		c->last_mg_iterations = timed_out || h.done == 2 ? 0 : h.iter;  // (the same on every rank: the scalars are sums over all)
 		c->last_mg_tol        = tolerance;
 		if (R.size() == 1 && c0->predictable_start && !timed_out && h.done != 2) { remember_iterations(c, 1, tolerance, h.iter); }
-		// by the field: met when the estimate says so -- or, in fp64, when the recurrence has reached the precision's floor (the
-		// field is then as converged as the arithmetic allows).  An fp32 solve that ends at ITS floor (2e-7) with the estimate
-		// above the tolerance has not delivered what was asked for: converged = 0, fi_stats::field_estimate says how far off.
-		const bool field_ok = by_field && h.done == 1 && ((h.field_est >= 0.0 && h.field_est <= h.field_tol) || sizeof(T) == 8);
-		c->stats.converged    = (!timed_out && (h.done == 4 || h.done == 5 || (h.done == 1 && (by_field ? field_ok : !c0->verify_residual)))) ? 1 : 0;
-		c->stats.rel_residual = h.bb > 0 ? std::sqrt(h.rr / h.bb) : 0.0;
-		c->stats.restarts     = h.restarts;
-		c->stats.verified_residual = (h.restarts > 0 && h.bb > 0) ? std::sqrt(h.true_rr / h.bb) : -1.0;
-		c->stats.field_estimate     = by_field ? h.field_est : -1.0;
-		c->stats.field_per_residual = by_field ? h.field_kappa : 0.0;
-		c->stats.stop_residual      = c->stats.rel_residual;
-		c->stats.field_rounds       = (by_field && !timed_out && h.done == 1 && h.field_stopped) ? 1 : 0;  // (not the floor, not max_iter)
-		if (h.done == 4) { FI_HIP_TRY(hipMemsetAsync(c->x.p, 0, sizeof(T) * c->g.nloc, c->stream)); }
+		if (by_field) {  // (frame.stats has written what a solve by the residual reports)
+			c->stats.field_estimate     = h.field_est;
+			c->stats.field_per_residual = h.field_kappa;
+			c->stats.field_rounds       = (!timed_out && h.done == 1 && h.field_stopped) ? 1 : 0;  // (not the floor, not max_iter)
+		}
 	}
-	FI_REQUIRE(h.done != 2, FI_ERR_BREAKDOWN, "CG breakdown: non-finite or non-positive curvature (p.AtA p = %g)", h.pq);
-	FI_REQUIRE(!timed_out, FI_ERR_TIMEOUT, "solve stopped by the wall-clock guard (FI_SOLVE_TIMEOUT_S = %g s) after %d iterations, "
-	           "relative residual %g", limit_s, h.iter, h.bb > 0 ? std::sqrt(h.rr / h.bb) : 0.0);
+	frame.require_ok(h);
 }
 
 

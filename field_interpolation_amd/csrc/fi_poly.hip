@@ -2,6 +2,7 @@
 // over slabs, and the power-method bound of the model operator.  Replaces the diagonal preconditioner of
 // Eigen::BiCGSTAB (sparse_linear.cpp:199-206) where FI_OPT_POLY_TERMS asks for it.
 #include "fi_solver_internal.h"
+#include "fi_cheb.h"
 
 namespace fi {
 
@@ -381,17 +382,12 @@ void cg_run_poly(RankSet& R, int max_iterations, float tol)
 	fi_ctx* c0 = R[0];
 	hipStream_t st = c0->stream;
 	const int terms = c0->poly_terms;
-	if (max_iterations <= 0) {
-		const int64_t dflt = 2 * static_cast<int64_t>(c0->g.gn[0]) * c0->g.gn[1] * c0->g.gn[2];
-		max_iterations = dflt > std::numeric_limits<int>::max() ? std::numeric_limits<int>::max() : static_cast<int>(dflt);
-	}
-	const double tolerance = tol > 0 ? static_cast<double>(tol) : static_cast<double>(std::numeric_limits<float>::epsilon());
+	SolveFrame frame(R, max_iterations, tol);
+	max_iterations = frame.max_iterations;
+	const double tolerance = frame.tolerance;
 	for (fi_ctx* c : R) { ensure_poly_vectors<T>(c); }
 	if (!(c0->poly_lambda > 0)) { estimate_poly_lambda<T>(R); }
-
-	EventPair timer;  // (destroyed on every way out: a coarse level's breakdown, a timeout)
-	const hipEvent_t e0 = timer.e0, e1 = timer.e1;
-	FI_HIP_TRY(hipEventRecord(e0, st));
+	frame.begin();
 
 	// Chebyshev interval and recurrence constants (the same polynomial as cheb_smooth).  The preconditioner is positive
 	// definite while the spectrum of Dinv A~ stays below hi + lo; poly_lambda is a power-method estimate -- a LOWER bound of
@@ -401,22 +397,18 @@ void cg_run_poly(RankSet& R, int max_iterations, float tol)
 	// scales the estimate, to drive that path.
 	double lam_scale = 1.0;
 	if (const char* env = test_switch("FI_POLY_LAMBDA_SCALE")) { lam_scale = atof(env) > 0 ? atof(env) : 1.0; }
-	double theta = 1.0, delta = 1.0;
+	double theta = 1.0;
 	std::vector<double> c1s, c2s;
 	auto set_interval = [&]() {
-		const double lam = (c0->poly_lambda > 1.0 ? c0->poly_lambda : 1.0) * lam_scale;
-		const double hi = 1.1 * lam, lo = hi / (c0->poly_ratio > 1.0 ? c0->poly_ratio : 10.0);
-		theta = 0.5 * (hi + lo);
-		delta = 0.5 * (hi - lo);
-		const double sigma = theta / delta;
+		const ChebInterval iv((c0->poly_lambda > 1.0 ? c0->poly_lambda : 1.0) * lam_scale, c0->poly_ratio > 1.0 ? c0->poly_ratio : 10.0);
+		theta = iv.theta;
 		c1s.clear();
 		c2s.clear();
-		double rho = 1.0 / sigma;
+		ChebRecurrence rec(iv);
 		for (int k = 1; k < terms; ++k) {
-			const double rho_new = 1.0 / (2.0 * sigma - rho);
-			c1s.push_back(rho_new * rho);
-			c2s.push_back(2.0 * rho_new / delta);
-			rho = rho_new;
+			rec.next();
+			c1s.push_back(rec.c1);
+			c2s.push_back(rec.c2);
 		}
 	};
 	set_interval();
@@ -472,11 +464,7 @@ void cg_run_poly(RankSet& R, int max_iterations, float tol)
 	std::vector<int> ptags;
 	std::vector<double> pbytes;  // algorithmic bytes of the sampled steps
 	std::vector<hipEvent_t>& pev = c0->ev_prec;
-	while (static_cast<int>(pev.size()) < 2 * kMaxSamples) {
-		hipEvent_t e;
-		FI_HIP_TRY(hipEventCreate(&e));
-		pev.push_back(e);
-	}
+	top_up_events(pev, 2 * kMaxSamples);
 	// one pass of the recurrence: phase 1 = a CG step (the apply of p has been launched), 0 / 2 = start / restart (the
 	// apply of x has been launched)
 	auto first_half = [&](int phase) {  // alpha, r, z1 (phase 0 / 2 / 3: r = b - A x)
@@ -604,15 +592,7 @@ void cg_run_poly(RankSet& R, int max_iterations, float tol)
 	start(0);
 
 	int samples = 0;
-	while (static_cast<int>(c0->ev.size()) < 2 * kMaxSamples) {
-		hipEvent_t e;
-		FI_HIP_TRY(hipEventCreate(&e));
-		c0->ev.push_back(e);
-	}
-	double limit_s = 600.0;
-	if (const char* env = getenv("FI_SOLVE_TIMEOUT_S")) { limit_s = atof(env); }
-	const auto wall0 = std::chrono::steady_clock::now();
-	bool timed_out = false;
+	top_up_events(c0->ev, 2 * kMaxSamples);
 	CgScalars* sc0 = c0->scal.as<CgScalars>();
 	int restarts_left = c0->verify_residual ? 3 : 0;
 	int widenings_left = 2, iter_base = 0;
@@ -622,8 +602,7 @@ void cg_run_poly(RankSet& R, int max_iterations, float tol)
 	int next_burst = c0->last_outer_iterations > 0 ? (c0->last_outer_iterations < 64 ? c0->last_outer_iterations : 64) : burst;
 	int issued = 0;
 	for (;;) {
-		FI_HIP_TRY(hipMemcpyAsync(c0->scal_host, sc0, sizeof(CgScalars), hipMemcpyDeviceToHost, st));
-		FI_HIP_TRY(hipStreamSynchronize(st));
+		frame.look(sc0);
 		if (c0->scal_host->done == 2 && widenings_left > 0 && std::isfinite(c0->scal_host->pq) && std::isfinite(c0->scal_host->rr) &&
 		    std::isfinite(c0->scal_host->rz)) {
 			// non-positive curvature with finite numbers: the polynomial's interval is too narrow for this lattice (see
@@ -658,16 +637,11 @@ void cg_run_poly(RankSet& R, int max_iterations, float tol)
 				hipLaunchKernelGGL(k_pcg_verify, dim3(1), dim3(kThreads), 0, c->stream, sc + 1, sc, folded ? region(c, 1) : slot2(c),
 				                   folded ? nbf_of(c) : 1);
 			}
-			FI_HIP_TRY(hipMemcpyAsync(c0->scal_host, sc0, sizeof(CgScalars), hipMemcpyDeviceToHost, st));
-			FI_HIP_TRY(hipStreamSynchronize(st));
-			if (c0->scal_host->done) { break; }   // verified (5), out of iterations (3) or not finite (2)
+			if (frame.look(sc0).done) { break; }   // verified (5), out of iterations (3) or not finite (2)
 			second_half(3);  // the true residual misses the tolerance: CG goes on from it (z = M r, p = z)
 			continue;
 		}
-		if (timed_out_anywhere(R, std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() > limit_s)) {
-			timed_out = true;
-			break;
-		}
+		if (frame.guard(R)) { break; }
 		const int nb = next_burst;
 		next_burst = burst > 2 ? 2 : burst;  // after the first look the solve is close to its end
 		for (int k = 0; k < nb; ++k) {
@@ -685,20 +659,10 @@ void cg_run_poly(RankSet& R, int max_iterations, float tol)
 		}
 		FI_HIP_TRY(hipGetLastError());
 	}
-	FI_HIP_TRY(hipEventRecord(e1, st));
-	FI_HIP_TRY(hipEventSynchronize(e1));
-	float ms = 0;
-	FI_HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-
-	const CgScalars h = *c0->scal_host;
+	const CgScalars h = frame.end();
 	int used = samples;
 	if ((h.iter + 3) / 4 < used) { used = (h.iter + 3) / 4; }  // sample k belongs to outer iteration 4k + 1
-	double sum_ms = 0;
-	for (int k = 0; k < used; ++k) {
-		float t = 0;
-		FI_HIP_TRY(hipEventElapsedTime(&t, c0->ev[2 * k], c0->ev[2 * k + 1]));
-		sum_ms += t;
-	}
+	frame.stats<T>(R, h, used, !c0->verify_residual);
 	// the timed steps of passes that ran (pass t is outer iteration t - 1; passes past the stop exited at once)
 	int pused = 0;
 	double psum = 0, pbsum = 0;
@@ -711,9 +675,6 @@ void cg_run_poly(RankSet& R, int max_iterations, float tol)
 		++pused;
 	}
 	for (fi_ctx* c : R) {
-		c->stats.spmv_samples = used;
-		c->stats.spmv_ms_avg  = used ? sum_ms / used : 0.0;
-		c->stats.spmv_bytes   = apply_algorithmic_bytes(c);
 		// per LAUNCH: a sample holds the terms - 1 steps of one polynomial; bytes / time is their byte-weighted rate
 		c->stats.prec_samples = pused * (terms - 1);
 		c->stats.prec_ms_avg  = pused ? psum / (pused * (terms - 1)) : 0.0;
@@ -723,18 +684,9 @@ void cg_run_poly(RankSet& R, int max_iterations, float tol)
 		c->stats.halo_exchanges = c0->nranks > 1 ? n_exchanges + issued + 1 + h.restarts : 0;
 		c->stats.reductions     = n_reductions;
 		c->last_outer_iterations = h.iter;
-		c->stats.solve_ms     = ms;
-		c->stats.iterations   = iter_base + h.iter;
-		c->stats.converged    = (!timed_out && (h.done == 4 || h.done == 5 || (h.done == 1 && !c0->verify_residual))) ? 1 : 0;
-		c->stats.rel_residual = h.bb > 0 ? std::sqrt(h.rr / h.bb) : 0.0;
-		c->stats.restarts     = h.restarts;
-		c->stats.verified_residual = (h.restarts > 0 && h.bb > 0) ? std::sqrt(h.true_rr / h.bb) : -1.0;
-		residual_rule_stats(c->stats);
-		if (h.done == 4) { FI_HIP_TRY(hipMemsetAsync(c->x.p, 0, sizeof(T) * c->g.nloc, c->stream)); }
+		c->stats.iterations   = iter_base + h.iter;  // (with the iterations before a widening of the interval)
 	}
-	FI_REQUIRE(h.done != 2, FI_ERR_BREAKDOWN, "CG breakdown: non-finite or non-positive curvature (p.AtA p = %g)", h.pq);
-	FI_REQUIRE(!timed_out, FI_ERR_TIMEOUT, "solve stopped by the wall-clock guard (FI_SOLVE_TIMEOUT_S = %g s) after %d iterations, "
-	           "relative residual %g", limit_s, h.iter, h.bb > 0 ? std::sqrt(h.rr / h.bb) : 0.0);
+	frame.require_ok(h);
 }
 
 // ---- the same solve over slabs with ONE reduction per outer iteration ---------------------------------------------------
@@ -862,11 +814,7 @@ void cg_run_poly_sr(RankSet& R, int max_iterations, float tol)
 	fi_ctx* c0 = R[0];
 	hipStream_t st = c0->stream;
 	const int terms = c0->poly_terms;
-	if (max_iterations <= 0) {
-		const int64_t dflt = 2 * static_cast<int64_t>(c0->g.gn[0]) * c0->g.gn[1] * c0->g.gn[2];
-		max_iterations = dflt > std::numeric_limits<int>::max() ? std::numeric_limits<int>::max() : static_cast<int>(dflt);
-	}
-	const double tolerance = tol > 0 ? static_cast<double>(tol) : static_cast<double>(std::numeric_limits<float>::epsilon());
+	SolveFrame frame(R, max_iterations, tol);
 	for (fi_ctx* c : R) {
 		ensure_poly_vectors<T>(c);
 		const size_t bytes = sizeof(T) * c->g.nloc;
@@ -876,28 +824,24 @@ void cg_run_poly_sr(RankSet& R, int max_iterations, float tol)
 		}
 	}
 	if (!(c0->poly_lambda > 0)) { estimate_poly_lambda<T>(R); }
-	EventPair timer;  // (destroyed on every way out: a coarse level's breakdown, a timeout)
-	const hipEvent_t e0 = timer.e0, e1 = timer.e1;
-	FI_HIP_TRY(hipEventRecord(e0, st));
+	frame.begin();
 
 	double lam_scale = 1.0;
 	if (const char* env = test_switch("FI_POLY_LAMBDA_SCALE")) { lam_scale = atof(env) > 0 ? atof(env) : 1.0; }
-	const double lam = (c0->poly_lambda > 1.0 ? c0->poly_lambda : 1.0) * lam_scale;
-	const double hi = 1.1 * lam, lo = hi / (c0->poly_ratio > 1.0 ? c0->poly_ratio : 10.0);
-	const double theta = 0.5 * (hi + lo), delta = 0.5 * (hi - lo), sigma = theta / delta;
+	const ChebInterval iv((c0->poly_lambda > 1.0 ? c0->poly_lambda : 1.0) * lam_scale, c0->poly_ratio > 1.0 ? c0->poly_ratio : 10.0);
+	const double theta = iv.theta;
 	std::vector<double> c1s, c2s;
 	{
-		double rho = 1.0 / sigma;
+		ChebRecurrence rec(iv);
 		for (int k = 1; k < terms; ++k) {
-			const double rho_new = 1.0 / (2.0 * sigma - rho);
-			c1s.push_back(rho_new * rho);
-			c2s.push_back(2.0 * rho_new / delta);
-			rho = rho_new;
+			rec.next();
+			c1s.push_back(rec.c1);
+			c2s.push_back(rec.c2);
 		}
 	}
 	CgScalars init{};
-	init.tol2     = tolerance * tolerance;
-	init.max_iter = max_iterations;
+	init.tol2     = frame.tolerance * frame.tolerance;
+	init.max_iter = frame.max_iterations;
 	init.rz       = 1.0;
 	init.alpha    = 1.0;
 	reset_scalars(R, init);
@@ -1000,21 +944,12 @@ void cg_run_poly_sr(RankSet& R, int max_iterations, float tol)
 			++n_exchanges;
 		}
 	};
-	auto read_state = [&]() -> const CgScalars& {
-		FI_HIP_TRY(hipMemcpyAsync(c0->scal_host, slot(c0, state), sizeof(CgScalars), hipMemcpyDeviceToHost, st));
-		FI_HIP_TRY(hipStreamSynchronize(st));
-		return *c0->scal_host;
-	};
 
 	true_residual(0);
-	double limit_s = 600.0;
-	if (const char* env = getenv("FI_SOLVE_TIMEOUT_S")) { limit_s = atof(env); }
-	const auto wall0 = std::chrono::steady_clock::now();
-	bool timed_out = false;
 	int  restarts_left = c0->verify_residual ? 3 : 0;
 	int  next_burst = c0->last_outer_iterations > 0 ? (c0->last_outer_iterations < 64 ? c0->last_outer_iterations + 1 : 64) : 4;
 	for (;;) {
-		const CgScalars& h = read_state();
+		const CgScalars& h = frame.look(slot(c0, state));
 		if (h.done) {
 			if (h.done != 1 || restarts_left <= 0) { break; }
 			--restarts_left;  // the recurrence's residual met the tolerance: check b - A x, go on from it if it misses
@@ -1028,42 +963,20 @@ void cg_run_poly_sr(RankSet& R, int max_iterations, float tol)
 			first = true;
 			continue;
 		}
-		if (timed_out_anywhere(R, std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() > limit_s)) {
-			timed_out = true;
-			break;
-		}
+		if (frame.guard(R)) { break; }
 		for (int k = 0; k < next_burst; ++k) { iterate(); }
 		next_burst = 2;
 		FI_HIP_TRY(hipGetLastError());
 	}
-	FI_HIP_TRY(hipEventRecord(e1, st));
-	FI_HIP_TRY(hipEventSynchronize(e1));
-	float ms = 0;
-	FI_HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-	const CgScalars h = *c0->scal_host;
+	const CgScalars h = frame.end();
+	frame.stats<T>(R, h, 0, !c0->verify_residual);  // (no apply is timed here)
 	for (fi_ctx* c : R) {
-		c->stats.spmv_samples = 0;
-		c->stats.spmv_ms_avg  = 0.0;
-		c->stats.spmv_bytes   = apply_algorithmic_bytes(c);
-		c->stats.prec_samples = 0;
-		c->stats.prec_ms_avg  = 0.0;
-		c->stats.prec_bytes   = 0.0;
 		c->stats.operator_applies = h.iter * terms + 1 + h.restarts;
 		c->stats.halo_exchanges = n_exchanges;
 		c->stats.reductions     = n_reductions;
 		c->last_outer_iterations = h.iter;
-		c->stats.solve_ms     = ms;
-		c->stats.iterations   = h.iter;
-		c->stats.converged    = (!timed_out && (h.done == 4 || h.done == 5 || (h.done == 1 && !c0->verify_residual))) ? 1 : 0;
-		c->stats.rel_residual = h.bb > 0 ? std::sqrt(h.rr / h.bb) : 0.0;
-		c->stats.restarts     = h.restarts;
-		c->stats.verified_residual = (h.restarts > 0 && h.bb > 0) ? std::sqrt(h.true_rr / h.bb) : -1.0;
-		residual_rule_stats(c->stats);
-		if (h.done == 4) { FI_HIP_TRY(hipMemsetAsync(c->x.p, 0, sizeof(T) * c->g.nloc, c->stream)); }
 	}
-	FI_REQUIRE(h.done != 2, FI_ERR_BREAKDOWN, "CG breakdown in the single-reduction recurrence (r.M r or p.A p not positive)");
-	FI_REQUIRE(!timed_out, FI_ERR_TIMEOUT, "solve stopped by the wall-clock guard (FI_SOLVE_TIMEOUT_S = %g s) after %d iterations, "
-	           "relative residual %g", limit_s, h.iter, h.bb > 0 ? std::sqrt(h.rr / h.bb) : 0.0);
+	frame.require_ok(h, "CG breakdown in the single-reduction recurrence (r.M r or p.A p not positive)");
 }
 
 // polynomial PCG; if its preconditioner stays indefinite after two widenings of the interval: the Jacobi diagonal, from

@@ -725,6 +725,110 @@ void mg_reduce(RankSet& R, CountFn count_of, int phase)
 	}
 }
 
+// ---- the frame of a solve ------------------------------------------------------------------------------------------
+// What the four CG drivers (cg_run, cg_run_poly, cg_run_poly_sr, cg_run_mg) do alike, once: the defaults of the caller's
+// limits, the timed region, the wall-clock guard, the look at the stop flag, the mean of the timed applies, the fi_stats
+// fields that mean the same on every path and the two errors a solve ends in.  What a driver does its own way -- its
+// iteration, when it looks, what it predicts, its own statistics -- stays in the driver.  Nothing here allocates: look(),
+// guard() and the sampling run inside the iteration loops.
+inline void top_up_events(std::vector<hipEvent_t>& ev, int count)
+{
+	while (static_cast<int>(ev.size()) < count) {
+		hipEvent_t e;
+		FI_HIP_TRY(hipEventCreate(&e));
+		ev.push_back(e);
+	}
+}
+
+struct SolveFrame {
+	fi_ctx* const     c0;
+	const hipStream_t st;
+	int               max_iterations;  // the caller's, or Eigen's default: 2 * cols
+	double            tolerance;       // the caller's, or Eigen's default
+	EventPair         timer;           // (destroyed on every way out: a coarse level's breakdown, a timeout)
+	// wall-clock guard: a solve that cannot reach its tolerance (fp32 stagnation with the default 2N iteration cap) must
+	// not hold the GPU for hours.  FI_SOLVE_TIMEOUT_S overrides the 600 s default.
+	double limit_s   = 600.0;
+	bool   timed_out = false;
+	float  ms        = 0;
+	std::chrono::steady_clock::time_point wall0 = std::chrono::steady_clock::now();
+
+	SolveFrame(RankSet& R, int max_it, float tol) : c0(R[0]), st(R[0]->stream), max_iterations(max_it)
+	{
+		if (max_iterations <= 0) {
+			const int64_t dflt = 2 * static_cast<int64_t>(c0->g.gn[0]) * c0->g.gn[1] * c0->g.gn[2];
+			max_iterations = dflt > std::numeric_limits<int>::max() ? std::numeric_limits<int>::max() : static_cast<int>(dflt);
+		}
+		tolerance = tol > 0 ? static_cast<double>(tol) : static_cast<double>(std::numeric_limits<float>::epsilon());
+		if (const char* env = getenv("FI_SOLVE_TIMEOUT_S")) { limit_s = atof(env); }
+	}
+	void begin()
+	{
+		FI_HIP_TRY(hipEventRecord(timer.e0, st));
+		wall0 = std::chrono::steady_clock::now();
+	}
+	// the scalar record `slot` of R[0] as the stream has left it: a copy and a host round trip
+	const CgScalars& look(const CgScalars* slot)
+	{
+		FI_HIP_TRY(hipMemcpyAsync(c0->scal_host, slot, sizeof(CgScalars), hipMemcpyDeviceToHost, st));
+		FI_HIP_TRY(hipStreamSynchronize(st));
+		return *c0->scal_host;
+	}
+	bool guard(RankSet& R)  // true: the limit has passed, on this rank or (one slab per process) on any
+	{
+		timed_out = timed_out_anywhere(R, std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() > limit_s);
+		return timed_out;
+	}
+	// the end of the timed region; returns what the last look saw
+	CgScalars end()
+	{
+		FI_HIP_TRY(hipEventRecord(timer.e1, st));
+		FI_HIP_TRY(hipEventSynchronize(timer.e1));
+		FI_HIP_TRY(hipEventElapsedTime(&ms, timer.e0, timer.e1));
+		return *c0->scal_host;
+	}
+	// The fields every driver reports alike; `used`: the timed applies (pairs of c0->ev) of iterations that ran; `done1_ok`:
+	// whether a solve the recurrence's residual ended (done == 1) counts as converged -- the one term of the rule that
+	// differs.  With the verified stop on, "converged" means b - A x itself met the tolerance (done == 5); a recurrence that
+	// converged while the true residual stagnated above it (fp32 on an ill-conditioned system) is not.
+	template <typename T>
+	void stats(RankSet& R, const CgScalars& h, int used, bool done1_ok)
+	{
+		double sum_ms = 0;
+		for (int k = 0; k < used; ++k) {
+			float t = 0;
+			FI_HIP_TRY(hipEventElapsedTime(&t, c0->ev[2 * k], c0->ev[2 * k + 1]));
+			sum_ms += t;
+		}
+		for (fi_ctx* c : R) {
+			c->stats.spmv_samples = used;
+			c->stats.spmv_ms_avg  = used ? sum_ms / used : 0.0;
+			c->stats.spmv_bytes   = apply_algorithmic_bytes(c);
+			c->stats.prec_samples = 0;  // (the drivers with a timed preconditioner write theirs behind this call)
+			c->stats.prec_ms_avg  = 0.0;
+			c->stats.prec_bytes   = 0.0;
+			c->stats.operator_applies = h.iter + 1 + h.restarts;
+			c->stats.solve_ms     = ms;
+			c->stats.iterations   = h.iter;
+			c->stats.converged    = (!timed_out && (h.done == 4 || h.done == 5 || (h.done == 1 && done1_ok))) ? 1 : 0;
+			c->stats.rel_residual = h.bb > 0 ? std::sqrt(h.rr / h.bb) : 0.0;
+			c->stats.restarts     = h.restarts;
+			c->stats.verified_residual = (h.restarts > 0 && h.bb > 0) ? std::sqrt(h.true_rr / h.bb) : -1.0;
+			residual_rule_stats(c->stats);
+			if (h.done == 4) {  // rhs == 0  ->  x = 0 (Eigen's early return)
+				FI_HIP_TRY(hipMemsetAsync(c->x.p, 0, sizeof(T) * c->g.nloc, c->stream));
+			}
+		}
+	}
+	// the last thing a driver does (`breakdown`: its own sentence where the default does not describe it)
+	void require_ok(const CgScalars& h, const char* breakdown = nullptr) const
+	{
+		if (breakdown) { FI_REQUIRE(h.done != 2, FI_ERR_BREAKDOWN, "%s", breakdown); }
+		FI_REQUIRE(h.done != 2, FI_ERR_BREAKDOWN, "CG breakdown: non-finite or non-positive curvature (p.AtA p = %g)", h.pq);
+		FI_REQUIRE(!timed_out, FI_ERR_TIMEOUT, "solve stopped by the wall-clock guard (FI_SOLVE_TIMEOUT_S = %g s) after %d iterations, "
+		           "relative residual %g", limit_s, h.iter, h.bb > 0 ? std::sqrt(h.rr / h.bb) : 0.0);
+	}
+};
 
 }  // namespace
 
