@@ -24,7 +24,7 @@ SYMBOLS = [
     "fi_group_iso_extract", "fi_iso_extract", "fi_iso_extract_field", "fi_mesh_info", "fi_mesh_copy", "fi_mesh_destroy",
     "fi_dual_contour", "fi_dual_contour_field",
     "fi_mesh_create", "fi_mesh_parts", "fi_mesh_measure", "fi_mesh_select", "fi_mesh_simplify",
-    "fi_mesh_smooth", "fi_mesh_normals", "fi_mesh_sample", "fi_mesh_deviation",
+    "fi_mesh_smooth", "fi_mesh_normals", "fi_mesh_sample", "fi_mesh_deviation", "fi_mesh_register", "fi_points_register",
     "fi_group_sample", "fi_sample", "fi_sample_field",
     "fi_nearest", "fi_distance_field", "fi_points_create", "fi_points_nearest", "fi_points_distance_field", "fi_points_destroy",
     "fi_knn", "fi_points_knn", "fi_estimate_normals", "fi_points_estimate_normals",
@@ -36,6 +36,8 @@ SYMBOLS = [
     "fi_point_count", "fi_point_residuals", "fi_robust_reweight", "fi_reset_point_weights", "fi_solve_robust",
 ]
 FI_LOSS = {"huber": 0, "cauchy": 1, "tukey": 2}
+FI_LOSS_NONE = -1
+FI_REGISTER = {"plane": 0, "point": 1}
 
 
 class FiWeights(C.Structure):
@@ -91,6 +93,18 @@ class FiSmoothOptions(C.Structure):
 class FiDeviation(C.Structure):
     _fields_ = [("queries", C.c_longlong), ("counted", C.c_longlong), ("beyond", C.c_longlong), ("invalid", C.c_longlong),
                 ("at", C.c_longlong), ("max", C.c_double), ("mean", C.c_double), ("rms", C.c_double), ("where", C.c_float * 3)]
+
+
+class FiRegisterOptions(C.Structure):
+    _fields_ = [("mode", C.c_int), ("max_iterations", C.c_int), ("max_distance", C.c_float), ("rotation_tolerance", C.c_double),
+                ("translation_tolerance", C.c_double), ("loss", C.c_int), ("tuning", C.c_float), ("scale", C.c_float)]
+
+
+class FiRegistration(C.Structure):
+    _fields_ = [("transform", C.c_double * 16), ("iterations", C.c_int), ("converged", C.c_int), ("fixed_mask", C.c_int),
+                ("reserved", C.c_int), ("queries", C.c_longlong), ("counted", C.c_longlong), ("beyond", C.c_longlong),
+                ("invalid", C.c_longlong), ("degenerate", C.c_longlong), ("rms", C.c_double), ("weighted_rms", C.c_double),
+                ("last_rotation", C.c_double), ("last_translation", C.c_double)]
 
 
 class FiError(RuntimeError):
@@ -175,6 +189,9 @@ def lib():
     L.fi_mesh_sample.argtypes = [vp, C.c_long, C.c_ulonglong, C.c_int, fp, fp, vp, C.c_int]
     L.fi_mesh_deviation.argtypes = [vp, vp, C.c_long, C.c_ulonglong, C.c_float, C.POINTER(FiDeviation), C.POINTER(FiDeviation), fp,
                                     C.c_int]
+    L.fi_mesh_register.argtypes = [vp, vp, C.c_long, fp, C.POINTER(FiRegisterOptions), dp, C.POINTER(FiRegistration), fp, fp, C.c_int]
+    L.fi_points_register.argtypes = [vp, fp, C.c_long, fp, C.POINTER(FiRegisterOptions), dp, C.POINTER(FiRegistration), fp, fp,
+                                     C.c_int]
     L.fi_group_sample.argtypes = [vp, fp, C.c_long, fp, C.c_int, C.c_float, fp, fp]
     L.fi_sample.argtypes = [vp, fp, C.c_long, fp, C.c_int, C.c_float, fp, fp, C.c_int]
     L.fi_sample_field.argtypes = [fp, C.c_int, ip, C.c_long, fp, C.c_int, C.c_float, fp, fp, C.c_int]

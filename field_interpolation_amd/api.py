@@ -943,6 +943,112 @@ def mesh_deviation(a, b, samples=100_000, seed=0, max_distance=math.inf, symmetr
     return out
 
 
+def _register_options(mode, max_iterations, max_distance, rotation_tolerance, translation_tolerance, loss, scale, tuning):
+    if mode not in _capi.FI_REGISTER:
+        raise ValueError("mode is 'plane' or 'point', not %r" % (mode,))
+    if loss is not None and loss not in _capi.FI_LOSS:
+        raise ValueError("loss is None, 'huber', 'cauchy' or 'tukey', not %r" % (loss,))
+    return _capi.FiRegisterOptions(_capi.FI_REGISTER[mode], int(max_iterations), float(max_distance), float(rotation_tolerance),
+                                   float(translation_tolerance), _capi.FI_LOSS_NONE if loss is None else _capi.FI_LOSS[loss],
+                                   float(tuning), float(scale))
+
+
+def _register(call, ndim, source, opt, initial, transformed, distances, other_memory=()):
+    """Shared body of the registrations: call(n, source, options, initial, result, transformed, distances, memory) -> the dict"""
+    s, smem, skeep = _buf(source)
+    shape = tuple(skeep.shape)
+    if len(shape) != 2 or shape[1] != ndim:
+        raise ValueError("source is (n, %d) for a %d-D target, not %r" % (ndim, ndim, shape))
+    mem = _same_memory(smem, *other_memory)
+    n = int(shape[0])
+    init = None
+    if initial is not None:
+        init = np.ascontiguousarray(initial, np.float64)
+        if init.shape != (ndim + 1, ndim + 1):
+            raise ValueError("initial is a (%d, %d) matrix" % (ndim + 1, ndim + 1))
+    like = skeep if hasattr(skeep, "data_ptr") else None
+    moved, pmoved = _like_array(like, (n, ndim), np.float32) if transformed else (None, None)
+    dist, pdist = _like_array(like, (n,), np.float32) if distances else (None, None)
+    r = _capi.FiRegistration()
+    check(call(n, s if n else None, C.byref(opt), None if init is None else init.ctypes.data_as(C.POINTER(C.c_double)), C.byref(r),
+               pmoved, pdist, mem))
+    out = {"transform": np.array(list(r.transform)[:(ndim + 1) ** 2], np.float64).reshape(ndim + 1, ndim + 1)}
+    for k in ("iterations", "converged", "fixed_mask", "queries", "counted", "beyond", "invalid", "degenerate"):
+        out[k] = int(getattr(r, k))
+    for k in ("rms", "weighted_rms", "last_rotation", "last_translation"):
+        out[k] = float(getattr(r, k))
+    if transformed:
+        out["transformed"] = moved
+    if distances:
+        out["distances"] = dist
+    return out
+
+
+def _register_to_mesh(h, surface, ndim, source, opt, initial, transformed, distances, other_memory=()):
+    def call(n, s, o, init, r, moved, dist, mem):
+        return _capi.lib().fi_mesh_register(h, surface, n, s, o, init, r, moved, dist, mem)
+    return _register(call, ndim, source, opt, initial, transformed, distances, other_memory)
+
+
+def register_points(source, target, target_normals=None, mode="plane", max_iterations=30, max_distance=math.inf,
+                    rotation_tolerance=1e-6, translation_tolerance=1e-6, loss=None, scale=0.0, tuning=0.0, initial=None,
+                    transformed=False, distances=False):
+    """The rigid transform that lays the points `source` (n, ndim) over `target` by iterated closest points on the device,
+    2-D or 3-D.  target: an IsoMesh (its exact closest points), a PointIndex or an (m, ndim) array of points (their nearest
+    point) -- numpy arrays, or torch CUDA tensors in the same memory as `source`; a bare SurfaceIndex holds no vertices to
+    take normals from and is accepted with mode="point" only (ValueError otherwise).  mode="plane" minimises the distances
+    along the target's normals (a mesh's face normals; a point set needs target_normals (m, ndim)) and converges in a few
+    steps; mode="point" minimises the distances themselves.  Pairs further apart than max_distance are left out; loss
+    ("huber", "cauchy", "tukey" with a residual `scale` > 0 and an optional `tuning` constant) weighs outliers down.  The loop
+    stops when a step turns by at most rotation_tolerance (radians) and shifts by at most translation_tolerance, or after
+    max_iterations steps; initial: a (ndim + 1, ndim + 1) matrix to start from (coarse alignment is the caller's).
+    -> a dict: transform (ndim + 1, ndim + 1) float64 mapping source to target coordinates, iterations, converged, fixed_mask
+    (the unknowns the data could not see, e.g. a plane's slide), queries, counted, beyond, invalid, degenerate, rms,
+    weighted_rms, last_rotation, last_translation, and with transformed / distances the moved points and their last
+    distances where `source` lives (include/fi_hip.h fi_mesh_register)."""
+    opt = _register_options(mode, max_iterations, max_distance, rotation_tolerance, translation_tolerance, loss, scale, tuning)
+    L = _capi.lib()
+    if isinstance(target, SurfaceIndex):
+        if mode != "point":
+            raise ValueError("mode='plane' needs the target as a mesh: a SurfaceIndex holds no vertices to take normals from")
+        return _register_to_mesh(None, target._h, target.ndim, source, opt, initial, transformed, distances)
+    if isinstance(target, IsoMesh):
+        h, ndim, mem, _like = _mesh_handle(target)
+        try:
+            return _register_to_mesh(h, None, ndim, source, opt, initial, transformed, distances, [mem])
+        finally:
+            L.fi_mesh_destroy(h)
+    index, memory = target, []
+    if not isinstance(target, PointIndex):
+        memory = [_buf(target)[1]]
+        index = PointIndex(target)
+    tn, tmem, tkeep = _buf(target_normals)
+    if mode == "plane" and tn is None:
+        raise ValueError("mode='plane' on a point set needs target_normals")
+    if tn is not None and tuple(tkeep.shape) != (index.num_points, index.ndim):
+        raise ValueError("target_normals is (%d, %d), one per target point" % (index.num_points, index.ndim))
+
+    def call(n, s, o, init, r, moved, dist, mem):
+        return L.fi_points_register(index._h, tn, n, s, o, init, r, moved, dist, mem)
+    return _register(call, index.ndim, source, opt, initial, transformed, distances, memory + [tmem])
+
+
+def apply_transform(transform, points, normals=None):
+    """`points` (n, ndim) moved by a register_points transform, R x + t in float64, and with `normals` also R n -- numpy in,
+    numpy out; torch in, torch out.  A convenience: register_points' own `transformed` follows the contract's rounding (one
+    fp32 rounding of a fixed-order sum), this does not."""
+    if hasattr(points, "data_ptr"):
+        import torch
+        T = torch.as_tensor(np.asarray(transform, np.float64), device=points.device)
+        D = T.shape[0] - 1
+        moved = points.to(torch.float64) @ T[:D, :D].T + T[:D, D]
+        return moved if normals is None else (moved, normals.to(torch.float64) @ T[:D, :D].T)
+    T = np.asarray(transform, np.float64)
+    D = T.shape[0] - 1
+    moved = np.asarray(points, np.float64) @ T[:D, :D].T + T[:D, D]
+    return moved if normals is None else (moved, np.asarray(normals, np.float64) @ T[:D, :D].T)
+
+
 def mesh_to_sdf(mesh, sizes, max_distance=math.inf):
     """The signed distance (flat, x fastest, float32) of every point of a lattice of `sizes` to a mesh -- an IsoMesh or
     anything with `vertices` and `indices`, from a field or not: SurfaceIndex.signed_distance_field.  The sign is the parity
@@ -1326,6 +1432,23 @@ class LatticeField:
         def call(d, i, h, mem):
             return _capi.lib().fi_redistance(self._h, s, float(iso), m, float(max_distance), d, i, h, mem)
         return _redistance(call, self.num_unknowns, primitives, device, len(self.sizes))
+
+    def register(self, points, iso=0.0, method="iso", mode="plane", max_iterations=30, max_distance=math.inf,
+                 rotation_tolerance=1e-6, translation_tolerance=1e-6, loss=None, scale=0.0, tuning=0.0, initial=None,
+                 transformed=False, distances=False):
+        """register_points of `points` (n, ndim) to the surface f = iso of the last solve's solution: the mesh of
+        iso_surface (method "iso") or of dual_contour with central differences ("dual") is extracted, searched and
+        registered to on the device and never copied to the host.  Undivided contexts only.  -> register_points' dict"""
+        opt = _register_options(mode, max_iterations, max_distance, rotation_tolerance, translation_tolerance, loss, scale, tuning)
+        h = C.c_void_p()
+        if _surface_method(method) == 0:
+            check(_capi.lib().fi_iso_extract(self._h, None, float(iso), FI_HOST, C.byref(h)))
+        else:
+            check(_capi.lib().fi_dual_contour(self._h, None, None, float(iso), FI_HOST, C.byref(h)))
+        try:
+            return _register_to_mesh(h, None, len(self.sizes), points, opt, initial, transformed, distances)
+        finally:
+            _capi.lib().fi_mesh_destroy(h)
 
     def set_verify_residual(self, on):
         """FI_OPT_VERIFY_RESIDUAL: True (default) checks b - A x at convergence and restarts CG if fp32 drift

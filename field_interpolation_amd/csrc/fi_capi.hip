@@ -15,6 +15,7 @@
 #include "fi_simplify.h"
 #include "fi_smooth.h"
 #include "fi_meshpts.h"
+#include "fi_register.h"
 
 #include <memory>
 
@@ -1323,6 +1324,24 @@ int fi_mesh_deviation(const fi_mesh* a, fi_surface* b, long samples, unsigned lo
 {
 	FI_API_BEGIN
 	fi::mesh_deviation(a, b, samples, seed, max_distance, of_samples, of_vertices, vertex_distances, memory);
+	FI_API_END
+}
+
+// ---- rigid registration of a point cloud (fi_register.hip) ---------------------------------------------
+int fi_mesh_register(const fi_mesh* target, fi_surface* index, long n, const float* source, const fi_register_options* options,
+                     const double* initial, fi_registration* out, float* transformed, float* distances, int memory)
+{
+	FI_API_BEGIN
+	fi::mesh_register(target, index, n, source, options, initial, out, transformed, distances, memory);
+	FI_API_END
+}
+
+int fi_points_register(const fi_points* target, const float* target_normals, long n, const float* source,
+                       const fi_register_options* options, const double* initial, fi_registration* out, float* transformed,
+                       float* distances, int memory)
+{
+	FI_API_BEGIN
+	fi::points_register(target, target_normals, n, source, options, initial, out, transformed, distances, memory);
 	FI_API_END
 }
 

@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 
 #include <fi_hip.h>
@@ -448,6 +449,31 @@ bool GpuLatticeField::iso_surface_points(float iso, bool dual, long n, unsigned 
 	if (!ok) { warn("iso_surface_points"); }
 	fi_mesh_destroy(m);
 	return ok;
+}
+
+static_assert(sizeof(Registration) == sizeof(fi_registration), "Registration mirrors fi_registration");
+
+bool GpuLatticeField::register_points(float iso, bool dual, long n, const float* positions, const RegisterOptions& options,
+                                      std::vector<double>* transform, Registration* stats) const
+{
+	fi_mesh* m = nullptr;
+	if (!transform || n < 0 ||
+	    (dual ? fi_dual_contour(ctx_, nullptr, nullptr, iso, FI_HOST, &m) : fi_iso_extract(ctx_, nullptr, iso, FI_DEVICE, &m)) != FI_OK) {
+		warn("register_points");
+		return false;
+	}
+	const fi_register_options opt{static_cast<int>(options.mode), options.max_iterations,       options.max_distance,
+	                              options.rotation_tolerance,     options.translation_tolerance, static_cast<int>(options.loss),
+	                              options.tuning,                 options.scale};
+	fi_registration r;
+	const bool      ok = fi_mesh_register(m, nullptr, n, positions, &opt, nullptr, &r, nullptr, nullptr, FI_HOST) == FI_OK;
+	if (!ok) { warn("register_points"); }
+	fi_mesh_destroy(m);
+	if (!ok) { return false; }
+	const size_t side = sizes_.size() + 1;
+	transform->assign(r.transform, r.transform + side * side);
+	if (stats) { std::memcpy(stats, &r, sizeof(r)); }
+	return true;
 }
 
 bool GpuLatticeField::sample(const std::vector<float>& positions, std::vector<float>* values, std::vector<float>* gradients,

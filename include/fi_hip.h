@@ -737,6 +737,100 @@ int fi_mesh_sample(const fi_mesh* m, long n, unsigned long long seed, int normal
 int fi_mesh_deviation(const fi_mesh* a, fi_surface* b, long samples, unsigned long long seed, float max_distance,
                       fi_deviation* of_samples, fi_deviation* of_vertices, float* vertex_distances, int memory);
 
+/* ---- rigid registration of a point cloud to a mesh or to a point set (ICP) -----------------------
+ * Finds the rotation R and translation t that lay n source points over a target -- a device mesh (its exact closest points,
+ * fi_surface_distance) or a point set (fi_points_nearest) -- by iterated closest points, without the points leaving the
+ * device.  ndim D = 2 or 3.  The contract (tests/register_reference.py is its definition in numpy) -- all
+ * arithmetic fp64 on the fp32 inputs converted exactly, one rounding per operation, only + - * / sqrt (no sin, cos or atan:
+ * device and host libm do not agree to the last bit), except where another contract is quoted.  The unknowns of a step are
+ * delta = (omega, tau): 3-D (omega_0, omega_1, omega_2, tau_0, tau_1, tau_2), U = 6; 2-D (theta, tau_0, tau_1), U = 3:
+ *   1. state.  R (D x D, row-major) and t (D) in double, from `initial` -- a (D + 1) x (D + 1) row-major double matrix on the
+ *      HOST whose last row is ignored, taken as given and not checked for orthogonality -- or the identity.  The pivot
+ *      g0_a = 0.5 ((double)lo_a + (double)hi_a) + 0.0 of the box of the finite source points (every coordinate finite; lo, hi
+ *      the fp32 extremes, order-free; the + 0.0 makes a zero pivot +0).  No finite source point: zero iterations, g0 = 0,
+ *      every point comes out `invalid`, FI_OK;
+ *   2. transformed point.  p_i[a] = (float)(((R[a][0] x_0 + R[a][1] x_1) + R[a][2] x_2) + t[a]) (2-D: no third term); the
+ *      current pivot g is the same expression of g0, kept in double;
+ *   3. pair.  Mesh target: (d, prim, c) are exactly what fi_surface_distance(p, max_distance) returns.  Point-set target:
+ *      (d, j) are exactly fi_points_nearest's and c is target point j.  A finite d is counted, +inf goes to `beyond`, NaN to
+ *      `invalid`;
+ *   4. normal (FI_REGISTER_PLANE only).  Mesh target: fi_mesh_normals' n_p of primitive prim (3-D (b - a) x (c - a), 2-D
+ *      (e_y, -e_x)) divided per component by w_p = sqrt((n_0 n_0 + n_1 n_1) + n_2 n_2) (2-D: sqrt(e_x e_x + e_y e_y)).
+ *      Point-set target: target_normals[j] as doubles divided by their length, the squares summed in axis order.  A length
+ *      that is 0 or not finite: the pair goes to `degenerate`, uncounted;
+ *   5. rows.  u = (double)p - g, e = (double)p - (double)c.
+ *      PLANE, one row: r = (n_0 e_0 + n_1 e_1) + n_2 e_2; 3-D J = (u_1 n_2 - u_2 n_1, u_2 n_0 - u_0 n_2, u_0 n_1 - u_1 n_0, n_0,
+ *      n_1, n_2); 2-D J = (u_0 n_1 - u_1 n_0, n_0, n_1); rho = |r|.
+ *      POINT, D rows with r_a = e_a: 3-D J_0 = (0, u_2, -u_1, 1, 0, 0), J_1 = (-u_2, 0, u_0, 0, 1, 0), J_2 = (u_1, -u_0, 0, 0, 0,
+ *      1); 2-D J_0 = (-u_1, 1, 0), J_1 = (u_0, 0, 1); rho = sqrt((e_0 e_0 + e_1 e_1) + e_2 e_2).
+ *      The weight w is 1.0 with FI_LOSS_NONE; else fi_robust_reweight's three formulas in double with u = rho / sc,
+ *      sc = (double)scale (double)c, c = tuning if > 0 else the fp32 constants 1.345f, 2.385f, 4.685f.
+ *      A counted pair adds w (sum_a J_a[j] J_a[k]) to M[j][k] (j <= k), w (sum_a J_a[j] r_a) to b[j], w (sum_a r_a r_a) to S_w
+ *      and sum_a r_a r_a to S; each inner sum runs over ascending a from its first term, zeros and ones included.  A pair
+ *      that is not counted adds 0.0;
+ *   6. sums over pairs.  Each of the U (U + 1) / 2 + U + 2 sums in fi_mesh_deviation's order: blocks of 256 consecutive
+ *      source indices by the tree s[t] += s[t + w], w = 128 .. 1 (the tail padded with 0.0), the block sums then added
+ *      ascending from 0.0.  The counts are integers;
+ *   7. solve M delta = -b by Cholesky in the order of the unknowns, plain scalar operations.  top = the largest M[j][j] (top =
+ *      M[0][0]; top = M[j][j] > top ? M[j][j] : top), lim = 1e-12 top.  For j ascending: d = M[j][j] - sum L[j][k] L[j][k] over
+ *      the free k < j, subtracted one after the other in ascending k.  If not d > lim, unknown j is FIXED: delta_j = 0, it is
+ *      skipped in every later sum and bit j of fixed_mask is set (bit 0 is omega_0 / theta).  Else L[j][j] = sqrt(d) and, for
+ *      i > j, L[i][j] = (M[j][i] - sum L[i][k] L[j][k]) / L[j][j], the same way.  Forward: y_j = (-b[j] - sum L[j][k] y_k) /
+ *      L[j][j], free k < j ascending, j ascending.  Back: delta_j = (y_j - sum L[k][j] delta_k) / L[j][j], free k > j
+ *      DESCENDING from U - 1, j descending.  A plane may slide and a lone cylinder spin without a blow-up.  counted == 0:
+ *      the loop stops and the step does not move the transform;
+ *   8. update by the Cayley map: an exact rotation for any step, I + [omega]x to first order.  3-D: v = 0.5 omega,
+ *      q = (v_0 v_0 + v_1 v_1) + v_2 v_2, den = 1 + q, c0 = 1 - q; R_d[a][a] = (c0 + 2 (v_a v_a)) / den;
+ *      R_d[0][1] = (2 (v_0 v_1) - 2 v_2) / den, R_d[1][0] = (2 (v_0 v_1) + 2 v_2) / den, R_d[0][2] = (2 (v_0 v_2) + 2 v_1) / den,
+ *      R_d[2][0] = (2 (v_0 v_2) - 2 v_1) / den, R_d[1][2] = (2 (v_1 v_2) - 2 v_0) / den, R_d[2][1] = (2 (v_1 v_2) + 2 v_0) / den.
+ *      2-D: a = 0.5 theta, a2 = a a, den = 1 + a2, c = (1 - a2) / den, s = (2 a) / den, R_d = [[c, -s], [s, c]].  Then, from the
+ *      old R, t and g: t'[a] = (((R_d[a][0] h_0 + R_d[a][1] h_1) + R_d[a][2] h_2) + g[a]) + tau[a] with h = t - g, and
+ *      R'[a][b] = (R_d[a][0] R[0][b] + R_d[a][1] R[1][b]) + R_d[a][2] R[2][b];
+ *   9. stop.  last_rotation = the largest |omega_j|, last_translation = the largest |tau_a| of the step just taken; the loop
+ *      has converged when last_rotation <= rotation_tolerance and last_translation <= translation_tolerance, else it stops
+ *      at max_iterations steps.  fixed_mask is the last step's.  A last evaluation then runs items 2 to 6 with no solve: it
+ *      gives counted, beyond, invalid, degenerate, rms = sqrt(S / rows) and weighted_rms = sqrt(S_w / rows), rows = counted
+ *      (PLANE) or D counted (POINT); both 0 when nothing is counted; `transformed` and `distances` are its p and d.
+ *      max_iterations = 0 is this evaluation alone.  The fp32 rounding of p leaves a floor of about 1e-8 under the steps at
+ *      coordinates near 10: tolerances under that floor are never met;
+ *   10. result.  transform: the (D + 1) x (D + 1) matrix [R t; 0 1], row-major in the first (D + 1)^2 entries, the rest 0.
+ * fi_mesh_register: `index` is a fi_surface of the target mesh, or NULL: built for the call.  `target` may be NULL with an
+ * index and FI_REGISTER_POINT (a surface alone holds no vertices to take normals from).  fi_points_register:
+ * target_normals float[m][ndim] in `memory` (m the set's points), NULL with FI_REGISTER_POINT.  source float[n][ndim],
+ * transformed float[n][ndim] or NULL, distances float[n] or NULL, all in `memory`; options, initial and out are HOST.
+ * n = 0: FI_OK, the identity or `initial` and zeros.  FI_ERR_INVALID: NULL target (and index), options or out; NULL source
+ * with n > 0; n < 0; a mesh and an index of different dimension, device or primitive count; a 1-D point set;
+ * max_iterations < 0; a NaN or negative max_distance or tolerance; a bad mode, loss or memory kind; a loss with scale <= 0 (a
+ * median scale is not offered) or a NaN or negative tuning; a non-finite entry in the first D rows of `initial`;
+ * FI_REGISTER_PLANE on a point set without normals or on a surface without its mesh.  n >= 2^31: FI_ERR_UNSUPPORTED.
+ * Fewer than about 6 well-spread points leave the problem under-determined: the answer is then the caller's affair.
+ * No atomics of any kind: a repeated call returns the same bytes.  Not offered: scale or affine fits, a median scale,
+ * normal-compatibility rejection, source-side normals and symmetric ICP, global or coarse alignment (the caller supplies
+ * `initial`), Levenberg damping, slab groups, 1-D, more than one target per call. */
+#define FI_REGISTER_PLANE 0
+#define FI_REGISTER_POINT 1
+#define FI_LOSS_NONE (-1)
+typedef struct fi_register_options {
+	int    mode;             /* FI_REGISTER_* */
+	int    max_iterations;   /* >= 0 */
+	float  max_distance;     /* >= 0, may be +inf: pairs further apart are `beyond` */
+	double rotation_tolerance, translation_tolerance;   /* >= 0 */
+	int    loss;             /* FI_LOSS_NONE or FI_LOSS_HUBER / _CAUCHY / _TUKEY */
+	float  tuning;           /* 0: the loss's default constant */
+	float  scale;            /* > 0 with a loss */
+} fi_register_options;
+typedef struct fi_registration {
+	double    transform[16];
+	int       iterations, converged, fixed_mask, reserved;   /* reserved: 0 */
+	long long queries, counted, beyond, invalid, degenerate;
+	double    rms, weighted_rms, last_rotation, last_translation;
+} fi_registration;
+int fi_mesh_register(const fi_mesh* target, fi_surface* index, long n, const float* source, const fi_register_options* options,
+                     const double* initial, fi_registration* out, float* transformed, float* distances, int memory);
+int fi_points_register(const fi_points* target, const float* target_normals, long n, const float* source,
+                       const fi_register_options* options, const double* initial, fi_registration* out, float* transformed,
+                       float* distances, int memory);
+
 /* ---- point queries: values and gradients at arbitrary positions --------------------------------
  * The contract ("Point queries") is this project's own:
  *   - positions: n points of ndim fp32 values, interleaved, in global lattice coordinates (x fastest, as fi_add_points);

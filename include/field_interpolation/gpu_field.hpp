@@ -36,6 +36,29 @@ struct MeshPart
 	long long euler() const { return vertices - edges + primitives; } // of a 3-D part
 };
 
+// Rigid registration (include/fi_hip.h fi_mesh_register): the options and the result, field for field.
+struct RegisterOptions
+{
+	enum class Mode { kPlane = 0, kPoint = 1 };
+	enum class Loss { kNone = -1, kHuber = 0, kCauchy = 1, kTukey = 2 };
+	Mode   mode                  = Mode::kPlane;
+	int    max_iterations        = 30;
+	float  max_distance          = std::numeric_limits<float>::infinity(); // pairs further apart are left out
+	double rotation_tolerance    = 1e-6; // the loop ends when a step turns and shifts by no more than these
+	double translation_tolerance = 1e-6;
+	Loss   loss                  = Loss::kNone;
+	float  tuning                = 0; // the loss's constant c; 0: its default
+	float  scale                 = 0; // the residual scale s: > 0 with a loss
+};
+
+struct Registration
+{
+	double    transform[16]; // (ndim + 1) x (ndim + 1), row-major, in the first entries
+	int       iterations, converged, fixed_mask, reserved;
+	long long queries, counted, beyond, invalid, degenerate;
+	double    rms, weighted_rms, last_rotation, last_translation;
+};
+
 class GpuLatticeField
 {
 public:
@@ -125,6 +148,14 @@ public:
 	// with nothing to sample, or the library refused the call.
 	bool iso_surface_points(float iso, bool dual, long n, unsigned long long seed, std::vector<float>* positions,
 	                        std::vector<float>* normals = nullptr) const;
+
+	// The rigid transform that lays `n` points (`positions`, ndim floats per point, lattice units) over iso_surface (dual =
+	// false) or dual_contour (dual = true) of the last solution by iterated closest points: the mesh is extracted, searched and
+	// registered to on the device and never copied to the host.  `transform` receives the (ndim + 1) x (ndim + 1) row-major
+	// matrix [R t; 0 1] that maps the points to the surface; `stats`, if asked, the whole result.  The contract is
+	// include/fi_hip.h fi_mesh_register.  false: no solution yet, or the library refused the call.
+	bool register_points(float iso, bool dual, long n, const float* positions, const RegisterOptions& options,
+	                     std::vector<double>* transform, Registration* stats = nullptr) const;
 
 	// Values (and, if asked, gradients: ndim floats per point) of the last solution at `positions` (ndim floats per point,
 	// global lattice coordinates, x fastest), sampled where the solution lives on the device: multilinear, or Catmull-Rom
