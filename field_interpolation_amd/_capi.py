@@ -29,6 +29,8 @@ SYMBOLS = [
     "fi_nearest", "fi_distance_field", "fi_points_create", "fi_points_nearest", "fi_points_distance_field", "fi_points_destroy",
     "fi_knn", "fi_points_knn", "fi_estimate_normals", "fi_points_estimate_normals",
     "fi_orient_normals", "fi_points_orient_normals",
+    "fi_radius_count", "fi_points_radius_count", "fi_neighbour_distances", "fi_points_neighbour_distances",
+    "fi_outliers_statistical", "fi_points_outliers_statistical", "fi_outliers_radius", "fi_points_outliers_radius", "fi_cloud_thin",
     "fi_surface_create", "fi_surface_from_mesh", "fi_surface_distance", "fi_surface_distance_field", "fi_surface_destroy",
     "fi_surface_raycast", "fi_surface_count_hits", "fi_surface_contains", "fi_surface_signed_distance",
     "fi_surface_signed_distance_field",
@@ -38,6 +40,7 @@ SYMBOLS = [
 FI_LOSS = {"huber": 0, "cauchy": 1, "tukey": 2}
 FI_LOSS_NONE = -1
 FI_REGISTER = {"plane": 0, "point": 1}
+FI_THIN = {"mean": 0, "first": 1}
 
 
 class FiWeights(C.Structure):
@@ -105,6 +108,10 @@ class FiRegistration(C.Structure):
                 ("reserved", C.c_int), ("queries", C.c_longlong), ("counted", C.c_longlong), ("beyond", C.c_longlong),
                 ("invalid", C.c_longlong), ("degenerate", C.c_longlong), ("rms", C.c_double), ("weighted_rms", C.c_double),
                 ("last_rotation", C.c_double), ("last_translation", C.c_double)]
+
+
+class FiOutlierStats(C.Structure):
+    _fields_ = [("counted", C.c_long), ("kept", C.c_long), ("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double)]
 
 
 class FiError(RuntimeError):
@@ -207,6 +214,16 @@ def lib():
     L.fi_points_estimate_normals.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, C.c_long, fp, fp, C.c_int]
     L.fi_orient_normals.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, C.c_long, fp, vp, C.c_int]
     L.fi_points_orient_normals.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, C.c_long, fp, vp, C.c_int]
+    L.fi_radius_count.argtypes = [vp, C.c_long, fp, C.c_float, C.c_int, vp, C.c_int]
+    L.fi_points_radius_count.argtypes = [vp, C.c_long, fp, C.c_float, C.c_int, vp, C.c_int]
+    L.fi_neighbour_distances.argtypes = [vp, C.c_int, C.c_float, fp, fp, vp, C.c_int]
+    L.fi_points_neighbour_distances.argtypes = [vp, C.c_int, C.c_float, fp, fp, vp, C.c_int]
+    L.fi_outliers_statistical.argtypes = [vp, C.c_int, C.c_float, C.c_float, vp, C.POINTER(FiOutlierStats), C.c_int]
+    L.fi_points_outliers_statistical.argtypes = [vp, C.c_int, C.c_float, C.c_float, vp, C.POINTER(FiOutlierStats), C.c_int]
+    L.fi_outliers_radius.argtypes = [vp, C.c_float, C.c_int, vp, C.POINTER(C.c_long), C.c_int]
+    L.fi_points_outliers_radius.argtypes = [vp, C.c_float, C.c_int, vp, C.POINTER(C.c_long), C.c_int]
+    L.fi_cloud_thin.argtypes = [C.c_int, C.c_long, fp, fp, fp, C.c_float, C.POINTER(C.c_float), C.c_int, fp, fp, fp, vp, vp, vp,
+                                C.POINTER(C.c_long), C.c_int]
     L.fi_surface_create.argtypes = [C.POINTER(vp), C.c_int, C.c_long, fp, C.c_long, vp, C.c_int]
     L.fi_surface_from_mesh.argtypes = [C.POINTER(vp), vp]
     L.fi_surface_distance.argtypes = [vp, C.c_long, fp, C.c_float, fp, vp, fp, C.c_int]

@@ -458,6 +458,72 @@ def _knn(call, ndim, queries, k, max_distance, indices):
     return (dist, idx) if indices else dist
 
 
+def _cloud_out(device, shape, dtype):
+    """an uninitialised output of `shape`: a torch tensor on `device` (a torch device or its name), or with None a numpy array
+    -> (array, pointer or None for an empty one)"""
+    if device is not None:
+        import torch
+        t = torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=device)
+        return t, (C.c_void_p(t.data_ptr()) if t.numel() else None)
+    a = np.empty(shape, dtype)
+    return a, (C.c_void_p(a.ctypes.data) if a.size else None)
+
+
+def _as_mask(keep):
+    """the uint8 flags of a C call as booleans"""
+    return keep.bool() if hasattr(keep, "data_ptr") else keep.view(np.bool_)
+
+
+def _radius_count(call, ndim, queries, radius, limit):
+    """Shared body of the radius counts: call(n, queries, radius, limit, counts, memory) is the C entry point.  The counts
+    live where `queries` lives."""
+    q, qmem, qkeep = _buf(queries)
+    count = qkeep.numel() if hasattr(qkeep, "numel") else qkeep.size
+    if count % ndim:
+        raise ValueError("queries: %d values, not a multiple of ndim = %d (x fastest)" % (count, ndim))
+    n = count // ndim
+    counts, p = _cloud_out(qkeep.device if qmem == FI_DEVICE else None, (n,), np.int32)
+    if n:
+        check(call(n, q, float(radius), int(limit), p, qmem))
+    return counts
+
+
+def _check_k(k):
+    if not 1 <= int(k) <= 32:
+        raise ValueError("k must be 1..32 (got %d)" % k)
+    return int(k)
+
+
+def _neighbour_distances(call, n, k, max_distance, device):
+    """Shared body: call(k, max_distance, mean, kth, counts, memory) is the C entry point -> (mean, kth, counts)"""
+    k = _check_k(k)
+    dev = "cuda" if device else None
+    mean, pm = _cloud_out(dev, (n,), np.float32)
+    kth, pk = _cloud_out(dev, (n,), np.float32)
+    counts, pc = _cloud_out(dev, (n,), np.int32)
+    if n:
+        check(call(k, float(max_distance), pm, pk, pc, FI_DEVICE if device else FI_HOST))
+    return mean, kth, counts
+
+
+def _statistical_outliers(call, n, k, std_ratio, max_distance, device):
+    """Shared body: call(k, max_distance, std_ratio, keep, stats, memory) is the C entry point -> (keep, stats dict)"""
+    k = _check_k(k)
+    keep, pk = _cloud_out("cuda" if device else None, (n,), np.uint8)
+    s = _capi.FiOutlierStats()
+    check(call(k, float(max_distance), float(std_ratio), pk, C.byref(s), FI_DEVICE if device else FI_HOST))
+    return _as_mask(keep), {"counted": int(s.counted), "kept": int(s.kept), "mean": float(s.mean), "stddev": float(s.stddev),
+                            "threshold": float(s.threshold)}
+
+
+def _radius_outliers(call, n, radius, min_neighbours, device):
+    """Shared body: call(radius, min_neighbours, keep, num_kept, memory) is the C entry point -> (keep, how many are kept)"""
+    keep, pk = _cloud_out("cuda" if device else None, (n,), np.uint8)
+    kept = C.c_long(0)
+    check(call(float(radius), int(min_neighbours), pk, C.byref(kept), FI_DEVICE if device else FI_HOST))
+    return _as_mask(keep), int(kept.value)
+
+
 def _estimate_normals(call, ndim, n, k, max_distance, viewpoints, directions, variation, device):
     """Shared body of the normal estimation: call(k, max_distance, orient, guides, num_guides, normals, variation, memory)
     is the C entry point.  Outputs are numpy arrays, or torch tensors on the GPU when the guides are device tensors or with
@@ -627,6 +693,42 @@ class PointIndex:
             return _capi.lib().fi_points_orient_normals(self._h, kk, md, anchor, g, ng, nrm, comp, mem)
         return _orient_normals(call, self.ndim, self.num_points, normals, k, max_distance, viewpoints, directions, components,
                                device)
+
+    def radius_count(self, queries, radius, limit=2 ** 31 - 1):
+        """How many finite points of the set lie within `radius` of each of `queries` (n x ndim), a point exactly on the
+        radius included: (n,) int32 where `queries` lives, -1 for a non-finite query.  The search of a query stops at `limit`
+        points and reports `limit`: pass the number you need to know about (include/fi_hip.h fi_radius_count)."""
+        def call(n, q, r, lim, c, mem):
+            return _capi.lib().fi_points_radius_count(self._h, n, q, r, lim, c, mem)
+        return _radius_count(call, self.ndim, queries, radius, limit)
+
+    def neighbour_distances(self, k=8, max_distance=math.inf, device=False):
+        """(mean, kth, counts), each (num_points,): the mean distance of every point of the set to its k nearest OTHER points
+        within max_distance (the point itself is left out by its index; a duplicate of it is a neighbour at distance 0), the
+        distance to the last of them, and how many they are.  No neighbour: +inf, +inf, 0; a non-finite point: NaN, NaN, 0.
+        1 <= k <= 32.  This is also the density weight: mean ** ndim or kth ** ndim is what a caller passes on as
+        `point_weights` so that an over-sampled patch does not outweigh the rest of the fit.  numpy arrays, or torch tensors
+        on the GPU with device=True (include/fi_hip.h fi_neighbour_distances)."""
+        def call(kk, md, m, kt, c, mem):
+            return _capi.lib().fi_points_neighbour_distances(self._h, kk, md, m, kt, c, mem)
+        return _neighbour_distances(call, self.num_points, k, max_distance, device)
+
+    def statistical_outliers(self, k=8, std_ratio=2.0, max_distance=math.inf, device=False):
+        """The statistical outlier rule of PCL and Open3D: a point is kept when its mean distance to its k nearest other
+        points (neighbour_distances) is at most mean + std_ratio * standard deviation of that figure over the cloud, the two
+        summed in a fixed order.  -> (keep (num_points,) bool, stats: counted, kept, mean, stddev, threshold); points that are
+        non-finite or have no neighbour within max_distance are neither counted nor kept (include/fi_hip.h
+        fi_outliers_statistical)."""
+        def call(kk, md, sr, kp, s, mem):
+            return _capi.lib().fi_points_outliers_statistical(self._h, kk, md, sr, kp, s, mem)
+        return _statistical_outliers(call, self.num_points, k, std_ratio, max_distance, device)
+
+    def radius_outliers(self, radius, min_neighbours=2, device=False):
+        """-> (keep (num_points,) bool, how many are kept): a point is kept when it is finite and at least min_neighbours
+        other finite points lie within `radius` of it (include/fi_hip.h fi_outliers_radius)."""
+        def call(r, mn, kp, nk, mem):
+            return _capi.lib().fi_points_outliers_radius(self._h, r, mn, kp, nk, mem)
+        return _radius_outliers(call, self.num_points, radius, min_neighbours, device)
 
     def distance_field(self, sizes, max_distance=math.inf, indices=False, device=False):
         """PointIndex.nearest of every point of a lattice of `sizes` (x fastest), flat."""
@@ -1049,6 +1151,92 @@ def apply_transform(transform, points, normals=None):
     return moved if normals is None else (moved, np.asarray(normals, np.float64) @ T[:D, :D].T)
 
 
+def _rows(a):
+    return int(a.shape[0])
+
+
+def thin_points(positions, cell, normals=None, values=None, origin=None, mode="mean", counts=False, indices=False, cell_map=False):
+    """A point cloud thinned on a uniform grid of spacing `cell` on the device: one output point per occupied cell, in
+    ascending cell order.  positions (n, ndim) -- or (n,) in 1-D -- with optional normals (n, ndim) and values (n,), numpy
+    arrays or torch CUDA tensors (all in the same memory).  mode="mean": the members' mean position and value and their
+    summed, normalised normal; mode="first": the member with the lowest index, bit for bit.  origin: where cell (0, ..) starts
+    (default zeros).  Non-finite points are left out.  counts / indices / cell_map=True add each cell's number of members
+    (int32), its lowest member's index (int64) and, per input point, the output it went to (int32, -1 for a point left out).
+    -> positions, or a tuple (positions, normals, values, counts, indices, cell_map) of what was given and asked for, where
+    `positions` lives (include/fi_hip.h fi_cloud_thin)."""
+    if mode not in _capi.FI_THIN:
+        raise ValueError("mode is 'mean' or 'first', not %r" % (mode,))
+    p, pmem, pkeep = _buf(positions)
+    shape = tuple(pkeep.shape)
+    if len(shape) not in (1, 2):
+        raise ValueError("positions is (n, ndim), or (n,) in 1-D, not %r" % (shape,))
+    n, ndim = shape[0], (shape[1] if len(shape) == 2 else 1)
+    nr, nmem, nkeep = _buf(normals)
+    if normals is not None and tuple(nkeep.shape) != shape:
+        raise ValueError("normals is %r, one per point" % (shape,))
+    vl, vmem, vkeep = _buf(values)
+    if values is not None and tuple(vkeep.shape) != (n,):
+        raise ValueError("values is (%d,), one per point" % n)
+    mem = _same_memory(pmem, nmem, vmem)
+    o = None
+    if origin is not None:
+        o = np.ascontiguousarray(origin, np.float32).reshape(-1)
+        if o.size != ndim:
+            raise ValueError("origin has %d coordinates" % ndim)
+    dev = pkeep.device if mem == FI_DEVICE else None
+    out = [_cloud_out(dev, shape, np.float32),
+           _cloud_out(dev, shape, np.float32) if normals is not None else None,
+           _cloud_out(dev, (n,), np.float32) if values is not None else None,
+           _cloud_out(dev, (n,), np.int32) if counts else None,
+           _cloud_out(dev, (n,), np.int64) if indices else None,
+           _cloud_out(dev, (n,), np.int32) if cell_map else None]
+    ptr = [None if a is None else a[1] for a in out]
+    num = C.c_long(0)
+    check(_capi.lib().fi_cloud_thin(ndim, n, p if n else None, nr, vl, float(cell),
+                                    None if o is None else o.ctypes.data_as(C.POINTER(C.c_float)), _capi.FI_THIN[mode], *ptr,
+                                    C.byref(num), mem))
+    m = num.value
+    trim = lambda a: a[:m].clone() if hasattr(a, "data_ptr") else a[:m].copy()  # noqa: E731
+    got = tuple(a[0] if i == 5 else trim(a[0]) for i, a in enumerate(out) if a is not None)
+    return got if len(got) > 1 else got[0]
+
+
+def clean_points(positions, normals=None, values=None, cell=None, k=None, std_ratio=2.0, radius=None, min_neighbours=2,
+                 max_distance=math.inf):
+    """A scan made fit for estimate_normals / sdf_from_points on the device, in this order and each step only if asked for:
+    thin_points(cell) (mean mode), PointIndex.radius_outliers(radius, min_neighbours), PointIndex.statistical_outliers(k,
+    std_ratio, max_distance).  Each filter builds its PointIndex over what the step before left.  numpy arrays, or torch
+    CUDA tensors that stay on the device.  -> (positions, normals, values, report): the surviving arrays (None where none was
+    given) and a dict with `input`, `output`, what each stage removed (`thinned`, `radius`, `statistical`) and the
+    statistical stage's `stats`."""
+    as_array = lambda a: a if a is None or hasattr(a, "data_ptr") else np.ascontiguousarray(a, np.float32)  # noqa: E731
+    pos, nrm, val = as_array(positions), as_array(normals), as_array(values)
+    on_device = bool(getattr(pos, "is_cuda", False))
+    report = {"input": _rows(pos)}
+
+    def select(keep):
+        return tuple(a if a is None else a[keep] for a in (pos, nrm, val))
+    if cell is not None:
+        got = thin_points(pos, cell, nrm, val)
+        got = iter(got if isinstance(got, tuple) else (got,))
+        before = _rows(pos)
+        pos = next(got)
+        nrm = next(got) if nrm is not None else None
+        val = next(got) if val is not None else None
+        report["thinned"] = before - _rows(pos)
+    if radius is not None:
+        keep, kept = PointIndex(pos).radius_outliers(radius, min_neighbours, device=on_device)
+        report["radius"] = _rows(pos) - kept
+        pos, nrm, val = select(keep)
+    if k is not None:
+        keep, stats = PointIndex(pos).statistical_outliers(k, std_ratio, max_distance, device=on_device)
+        report["statistical"] = _rows(pos) - stats["kept"]
+        report["stats"] = stats
+        pos, nrm, val = select(keep)
+    report["output"] = _rows(pos)
+    return pos, nrm, val, report
+
+
 def mesh_to_sdf(mesh, sizes, max_distance=math.inf):
     """The signed distance (flat, x fastest, float32) of every point of a lattice of `sizes` to a mesh -- an IsoMesh or
     anything with `vertices` and `indices`, from a field or not: SurfaceIndex.signed_distance_field.  The sign is the parity
@@ -1412,6 +1600,39 @@ class LatticeField:
             return _capi.lib().fi_orient_normals(self._h, kk, md, anchor, g, ng, nrm, comp, mem)
         return _orient_normals(call, len(self.sizes), n.value, normals, k, max_distance, viewpoints, directions, components,
                                device)
+
+    def _point_count(self):
+        n = C.c_long(0)
+        check(_capi.lib().fi_point_count(self._h, C.byref(n)))
+        return n.value
+
+    def radius_count(self, queries, radius, limit=2 ** 31 - 1):
+        """PointIndex.radius_count over the data points of this context (include/fi_hip.h fi_radius_count): the set and the
+        search structure are nearest()'s."""
+        def call(n, q, r, lim, c, mem):
+            return _capi.lib().fi_radius_count(self._h, n, q, r, lim, c, mem)
+        return _radius_count(call, len(self.sizes), queries, radius, limit)
+
+    def neighbour_distances(self, k=8, max_distance=math.inf, device=False):
+        """PointIndex.neighbour_distances of the data points of this context, in the order they were added
+        (include/fi_hip.h fi_neighbour_distances)."""
+        def call(kk, md, m, kt, c, mem):
+            return _capi.lib().fi_neighbour_distances(self._h, kk, md, m, kt, c, mem)
+        return _neighbour_distances(call, self._point_count(), k, max_distance, device)
+
+    def statistical_outliers(self, k=8, std_ratio=2.0, max_distance=math.inf, device=False):
+        """PointIndex.statistical_outliers of the data points of this context, in the order they were added
+        (include/fi_hip.h fi_outliers_statistical)."""
+        def call(kk, md, sr, kp, s, mem):
+            return _capi.lib().fi_outliers_statistical(self._h, kk, md, sr, kp, s, mem)
+        return _statistical_outliers(call, self._point_count(), k, std_ratio, max_distance, device)
+
+    def radius_outliers(self, radius, min_neighbours=2, device=False):
+        """PointIndex.radius_outliers of the data points of this context, in the order they were added
+        (include/fi_hip.h fi_outliers_radius)."""
+        def call(r, mn, kp, nk, mem):
+            return _capi.lib().fi_outliers_radius(self._h, r, mn, kp, nk, mem)
+        return _radius_outliers(call, self._point_count(), radius, min_neighbours, device)
 
     def distance_field(self, max_distance=math.inf, indices=False, device=False):
         """LatticeField.nearest of every lattice point (x fastest), flat: numpy arrays, or torch tensors with device=True."""

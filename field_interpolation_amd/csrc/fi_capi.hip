@@ -16,6 +16,7 @@
 #include "fi_smooth.h"
 #include "fi_meshpts.h"
 #include "fi_register.h"
+#include "fi_cloud.h"
 
 #include <memory>
 
@@ -1539,6 +1540,144 @@ int fi_points_estimate_normals(fi_points* h, int k, float max_distance, int orie
 	check_points(h);
 	check_normals(&h->t, h->t.D, k, max_distance, orient, guides, num_guides, normals, memory);
 	fi::estimate_normals(h->t, k, max_distance, orient, guides, num_guides, normals, variation, memory, nullptr);
+	FI_API_END
+}
+
+
+// ---- a point cloud made clean: thinning and outlier removal (fi_cloud.hip) -----------------------
+namespace {
+void check_radius(float radius, int least, const char* what, int memory)
+{
+	FI_REQUIRE(radius >= 0.0f, FI_ERR_INVALID, "radius must be >= 0 (got %g)", static_cast<double>(radius));  // (NaN fails)
+	FI_REQUIRE(least >= 1, FI_ERR_INVALID, "%s must be >= 1 (got %d)", what, least);
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+}
+
+void check_radius_count(long n, const float* queries, float radius, int limit, const int* counts, int memory)
+{
+	FI_REQUIRE(n >= 0, FI_ERR_INVALID, "n = %ld", n);
+	FI_REQUIRE(queries != nullptr && counts != nullptr, FI_ERR_INVALID, "null queries or counts");
+	check_radius(radius, limit, "limit", memory);
+	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld queries in one call", n);  // (one thread per query, 32-bit counts)
+}
+
+void check_neighbours(int k, float max_distance, bool any_output, int memory)
+{
+	check_k(k);
+	FI_REQUIRE(max_distance >= 0.0f, FI_ERR_INVALID, "max_distance must be >= 0 (got %g)", static_cast<double>(max_distance));
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	FI_REQUIRE(any_output, FI_ERR_INVALID, "every output is null");
+}
+
+void check_statistical(int k, float max_distance, float std_ratio, bool any_output, int memory)
+{
+	check_neighbours(k, max_distance, any_output, memory);
+	FI_REQUIRE(std_ratio >= 0.0f, FI_ERR_INVALID, "std_ratio must be >= 0 (got %g)", static_cast<double>(std_ratio));
+}
+}  // namespace
+
+int fi_radius_count(fi_ctx* c, long n, const float* queries, float radius, int limit, int* counts, int memory)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	check_radius_count(n, queries, radius, limit, counts, memory);
+	check_undivided(c);
+	if (n == 0) { return FI_OK; }
+	fi::cloud_radius_count(fi::nearest_of(c), n, queries, radius, limit, counts, memory, c->stream);
+	FI_API_END
+}
+
+int fi_points_radius_count(fi_points* h, long n, const float* queries, float radius, int limit, int* counts, int memory)
+{
+	FI_API_BEGIN
+	check_points(h);
+	check_radius_count(n, queries, radius, limit, counts, memory);
+	fi::cloud_radius_count(h->t, n, queries, radius, limit, counts, memory, nullptr);
+	FI_API_END
+}
+
+int fi_neighbour_distances(fi_ctx* c, int k, float max_distance, float* mean, float* kth, int* counts, int memory)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	check_neighbours(k, max_distance, mean || kth || counts, memory);
+	check_undivided(c);
+	fi::cloud_neighbour_distances(fi::nearest_of(c), k, max_distance, mean, kth, counts, memory, c->stream);
+	FI_API_END
+}
+
+int fi_points_neighbour_distances(fi_points* h, int k, float max_distance, float* mean, float* kth, int* counts, int memory)
+{
+	FI_API_BEGIN
+	check_points(h);
+	check_neighbours(k, max_distance, mean || kth || counts, memory);
+	fi::cloud_neighbour_distances(h->t, k, max_distance, mean, kth, counts, memory, nullptr);
+	FI_API_END
+}
+
+int fi_outliers_statistical(fi_ctx* c, int k, float max_distance, float std_ratio, unsigned char* keep, fi_outlier_stats* stats, int memory)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	check_statistical(k, max_distance, std_ratio, keep || stats, memory);
+	check_undivided(c);
+	fi::cloud_outliers_statistical(fi::nearest_of(c), k, max_distance, std_ratio, keep, stats, memory, c->stream);
+	FI_API_END
+}
+
+int fi_points_outliers_statistical(fi_points* h, int k, float max_distance, float std_ratio, unsigned char* keep, fi_outlier_stats* stats,
+                                   int memory)
+{
+	FI_API_BEGIN
+	check_points(h);
+	check_statistical(k, max_distance, std_ratio, keep || stats, memory);
+	fi::cloud_outliers_statistical(h->t, k, max_distance, std_ratio, keep, stats, memory, nullptr);
+	FI_API_END
+}
+
+int fi_outliers_radius(fi_ctx* c, float radius, int min_neighbours, unsigned char* keep, long* num_kept, int memory)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	check_radius(radius, min_neighbours, "min_neighbours", memory);
+	FI_REQUIRE(keep || num_kept, FI_ERR_INVALID, "every output is null");
+	check_undivided(c);
+	fi::cloud_outliers_radius(fi::nearest_of(c), radius, min_neighbours, keep, num_kept, memory, c->stream);
+	FI_API_END
+}
+
+int fi_points_outliers_radius(fi_points* h, float radius, int min_neighbours, unsigned char* keep, long* num_kept, int memory)
+{
+	FI_API_BEGIN
+	check_points(h);
+	check_radius(radius, min_neighbours, "min_neighbours", memory);
+	FI_REQUIRE(keep || num_kept, FI_ERR_INVALID, "every output is null");
+	fi::cloud_outliers_radius(h->t, radius, min_neighbours, keep, num_kept, memory, nullptr);
+	FI_API_END
+}
+
+int fi_cloud_thin(int ndim, long n, const float* positions, const float* normals, const float* values, float cell, const float* origin,
+                  int mode, float* out_positions, float* out_normals, float* out_values, int* out_counts, long long* out_indices,
+                  int* cell_map, long* num_out, int memory)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(num_out != nullptr, FI_ERR_INVALID, "num_out is null");
+	*num_out = 0;
+	FI_REQUIRE(1 <= ndim && ndim <= FI_MAX_DIM, FI_ERR_INVALID, "ndim must be 1..%d (got %d)", FI_MAX_DIM, ndim);
+	FI_REQUIRE(n >= 0, FI_ERR_INVALID, "n = %ld", n);
+	FI_REQUIRE(n == 0 || (positions != nullptr && out_positions != nullptr), FI_ERR_INVALID, "null positions or out_positions");
+	FI_REQUIRE(normals != nullptr || out_normals == nullptr, FI_ERR_INVALID, "out_normals without normals");
+	FI_REQUIRE(values != nullptr || out_values == nullptr, FI_ERR_INVALID, "out_values without values");
+	FI_REQUIRE(cell > 0.0f, FI_ERR_INVALID, "cell must be > 0 (got %g)", static_cast<double>(cell));  // (false for a NaN)
+	FI_REQUIRE(mode == FI_THIN_MEAN || mode == FI_THIN_FIRST, FI_ERR_INVALID, "bad mode %d", mode);
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld points in one call", n);
+	fi::cloud_thin(ndim, n, positions, normals, values, cell, origin, mode, out_positions, out_normals, out_values, out_counts, out_indices,
+	               cell_map, num_out, memory);
 	FI_API_END
 }
 

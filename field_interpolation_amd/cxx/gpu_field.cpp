@@ -582,6 +582,117 @@ bool GpuLatticeField::orient_normals(std::vector<float>* normals, int k, const s
 	return true;
 }
 
+bool GpuLatticeField::radius_count(const std::vector<float>& queries, float radius, std::vector<int>* counts, int limit) const
+{
+	const size_t D = sizes_.size();
+	if (!counts || queries.size() % D != 0) {
+		warn("radius_count");
+		return false;
+	}
+	const size_t n = queries.size() / D;
+	counts->resize(n);
+	if (n == 0) { return true; }
+	if (fi_radius_count(ctx_, static_cast<long>(n), queries.data(), radius, limit, counts->data(), FI_HOST) != FI_OK) {
+		warn("radius_count");
+		return false;
+	}
+	return true;
+}
+
+bool GpuLatticeField::neighbour_distances(int k, std::vector<float>* mean, std::vector<float>* kth, std::vector<int>* counts,
+                                          float max_distance) const
+{
+	long n = 0;
+	if ((!mean && !kth && !counts) || fi_point_count(ctx_, &n) != FI_OK) {
+		warn("neighbour_distances");
+		return false;
+	}
+	if (mean) { mean->resize(n); }
+	if (kth) { kth->resize(n); }
+	if (counts) { counts->resize(n); }
+	if (n == 0) { return true; }  // (data() of an empty vector may be null: the library would take every output for missing)
+	if (fi_neighbour_distances(ctx_, k, max_distance, mean ? mean->data() : nullptr, kth ? kth->data() : nullptr,
+	                           counts ? counts->data() : nullptr, FI_HOST) != FI_OK) {
+		warn("neighbour_distances");
+		return false;
+	}
+	return true;
+}
+
+static_assert(sizeof(OutlierStats) == sizeof(fi_outlier_stats), "OutlierStats mirrors fi_outlier_stats");
+
+bool GpuLatticeField::statistical_outliers(int k, float std_ratio, std::vector<unsigned char>* keep, OutlierStats* stats,
+                                           float max_distance) const
+{
+	long n = 0;
+	if (!keep || fi_point_count(ctx_, &n) != FI_OK) {
+		warn("statistical_outliers");
+		return false;
+	}
+	keep->resize(n);
+	fi_outlier_stats s;
+	if (fi_outliers_statistical(ctx_, k, max_distance, std_ratio, n ? keep->data() : nullptr, &s, FI_HOST) != FI_OK) {
+		warn("statistical_outliers");
+		return false;
+	}
+	if (stats) { std::memcpy(stats, &s, sizeof(s)); }
+	return true;
+}
+
+bool GpuLatticeField::radius_outliers(float radius, int min_neighbours, std::vector<unsigned char>* keep, long* num_kept) const
+{
+	long n = 0, kept = 0;
+	if (!keep || fi_point_count(ctx_, &n) != FI_OK) {
+		warn("radius_outliers");
+		return false;
+	}
+	keep->resize(n);
+	if (fi_outliers_radius(ctx_, radius, min_neighbours, n ? keep->data() : nullptr, &kept, FI_HOST) != FI_OK) {
+		warn("radius_outliers");
+		return false;
+	}
+	if (num_kept) { *num_kept = kept; }
+	return true;
+}
+
+bool thin_points(int ndim, const std::vector<float>& positions, float cell, std::vector<float>* out_positions,
+                 const std::vector<float>& normals, std::vector<float>* out_normals, const std::vector<float>& values,
+                 std::vector<float>* out_values, const std::vector<float>& origin, bool first, std::vector<int>* out_counts,
+                 std::vector<long long>* out_indices, std::vector<int>* cell_map)
+{
+	const auto refuse = [] {
+		std::fprintf(stderr, "field_interpolation: thin_points: %s\n", fi_last_error());
+		return false;
+	};
+	if (ndim < 1 || ndim > 3 || !out_positions || positions.size() % ndim != 0) { return refuse(); }
+	const size_t n = positions.size() / ndim;
+	if ((!normals.empty() && normals.size() != positions.size()) || (!values.empty() && values.size() != n) ||
+	    (!origin.empty() && origin.size() != static_cast<size_t>(ndim)) || (out_normals && normals.empty() && n) ||
+	    (out_values && values.empty() && n)) {
+		return refuse();
+	}
+	out_positions->resize(positions.size());
+	if (out_normals) { out_normals->resize(positions.size()); }
+	if (out_values) { out_values->resize(n); }
+	if (out_counts) { out_counts->resize(n); }
+	if (out_indices) { out_indices->resize(n); }
+	if (cell_map) { cell_map->resize(n); }
+	long m = 0;
+	if (fi_cloud_thin(ndim, static_cast<long>(n), positions.data(), normals.empty() ? nullptr : normals.data(),
+	                  values.empty() ? nullptr : values.data(), cell, origin.empty() ? nullptr : origin.data(),
+	                  first ? FI_THIN_FIRST : FI_THIN_MEAN, out_positions->data(), out_normals && n ? out_normals->data() : nullptr,
+	                  out_values && n ? out_values->data() : nullptr, out_counts ? out_counts->data() : nullptr,
+	                  out_indices ? out_indices->data() : nullptr, cell_map ? cell_map->data() : nullptr, &m, FI_HOST) != FI_OK) {
+		return refuse();
+	}
+	out_positions->resize(static_cast<size_t>(m) * ndim);
+	if (out_normals) { out_normals->resize(static_cast<size_t>(m) * ndim); }
+	if (out_values) { out_values->resize(m); }
+	if (out_counts) { out_counts->resize(m); }
+	if (out_indices) { out_indices->resize(m); }
+	return true;
+}
+
 bool GpuLatticeField::distance_field(std::vector<float>* distances, std::vector<long long>* indices, float max_distance) const
 {
 	if (!distances) {

@@ -970,6 +970,75 @@ int fi_orient_normals(fi_ctx* ctx, int k, float max_distance, int anchor, const 
 int fi_points_orient_normals(fi_points* points, int k, float max_distance, int anchor, const float* guides, long num_guides,
                              float* normals, long long* components, int memory);
 
+/* ---- a point cloud made clean: thinning and outlier removal ---------------------------------------
+ * The contract (tests/cloud_reference.py is its definition in numpy).  The point set, s(p, q), finiteness and
+ * the search structure are fi_nearest's; ndim = 1, 2 or 3.  fp64 arithmetic is one rounding per operation over + - * / sqrt on
+ * fp32 inputs converted exactly.  Every output is defined bit for bit and depends neither on the launch shape nor on timing.
+ *
+ * fi_radius_count: for a finite query, counts[i] = min(limit, the number of finite points j with sqrtf(s(p_j, q)) <= radius):
+ * a point exactly on the radius counts; radius = +inf counts every finite point (one whose s overflows included).  A
+ * non-finite query: -1.  queries float[n * ndim], counts int[n], both in `memory`.  The search stops at `limit` points: pass
+ * the largest int for the exact number.  FI_ERR_INVALID: the errors of fi_nearest; a NaN or negative radius; limit < 1.
+ *
+ * fi_neighbour_distances: for point i of the set (a context's points in the order they were added, or a fi_points) and
+ * 1 <= k <= 32: the pairs (s(p_j, p_i), j) over the finite points j != i in lexicographic order -- the point itself is left
+ * out by its INDEX, a duplicate of it is a neighbour at distance 0; the first k of them with sqrtf(s) <= max_distance are its
+ * neighbours, m of them.  mean[i] = (float)((0.0 + d_0 + ... + d_{m-1}) / m) with d_r = (double)sqrtf(s_r) added in result
+ * order; kth[i] = sqrtf(s_{m-1}); counts[i] = m.  m = 0: mean and kth are +inf.  A non-finite point: NaN, NaN, 0.  mean
+ * float[n], kth float[n], counts int[n] in `memory`; any of them may be NULL, not all three.  mean^ndim or kth^ndim is the
+ * inverse local density: what a caller passes on as point weights.  FI_ERR_INVALID: k outside 1..32, a NaN or negative
+ * max_distance, a bad memory kind, three NULL outputs.
+ *
+ * fi_outliers_statistical (the rule of PCL and Open3D): x_i = (double)mean[i] of fi_neighbour_distances(k, max_distance).
+ * Point i is COUNTED iff x_i is finite; N = their number.  mu = T(x) / N, sigma = sqrt(T((x - mu)(x - mu)) / N), where T is
+ * the fixed-order sum of fi_mesh_deviation over the array in POINT order, an uncounted point adding 0.0: blocks of 256
+ * consecutive indices by the tree s[t] += s[t + w], w = 128 .. 1 (the tail padded with 0.0), the block sums then added
+ * ascending from 0.0.  threshold = mu + (double)std_ratio sigma.  keep[i] = 1 iff i is counted and x_i <= threshold, else 0.
+ * N = 0: nothing is kept, the doubles are 0, FI_OK.  keep unsigned char[n] in `memory` or NULL, stats on the HOST or NULL,
+ * not both NULL.  FI_ERR_INVALID: as fi_neighbour_distances; a NaN or negative std_ratio.
+ *
+ * fi_outliers_radius: keep[i] = 1 iff p_i is finite and at least min_neighbours finite points j != i have
+ * sqrtf(s(p_j, p_i)) <= radius.  keep unsigned char[n] in `memory` or NULL, *num_kept (HOST) or NULL, not both NULL.
+ * FI_ERR_INVALID: a NaN or negative radius, min_neighbours < 1, a bad memory kind.
+ *
+ * The four above on a slab context: FI_ERR_UNSUPPORTED, as for fi_nearest.
+ *
+ * fi_cloud_thin: one output point per occupied cell of a uniform grid; it needs no search structure and runs on the current
+ * device.  The cell of a finite point is fi_mesh_simplify's: c_a = floorf((p_a - o_a) / cell) in fp32, o = origin (HOST,
+ * float[ndim]) or zeros, key = sum_a (c_a + 2^20) << 21 a.  A point with a non-finite coordinate is left out (cell_map -1): a
+ * scan has such points.  Outputs are the occupied cells in ascending key order; a cell's members are taken in ascending
+ * index, m of them.  FI_THIN_MEAN: position[a] = (float)((0.0 + p^0_a + p^1_a + ...) / m) in fp64; values (float[n], or NULL)
+ * are averaged the same way; normals (float[n * ndim], or NULL): the fp64 sum S of the members' normals divided by
+ * sqrt((S_0 S_0 + S_1 S_1) + S_2 S_2), all zeros where that length is not > 0.  FI_THIN_FIRST: position, normal and value of
+ * the member with the lowest index, bit for bit.  Both: out_counts[c] = m (int), out_indices[c] = the lowest member's index
+ * (long long), cell_map[i] = the output number of point i's cell (int).  Every output array has room for n entries and
+ * *num_out (HOST) says how many were written; out_normals / out_values, out_counts, out_indices and cell_map may be NULL.
+ * n = 0 or no finite point: *num_out = 0, FI_OK.  FI_ERR_INVALID: ndim outside 1..3, n < 0, NULL positions, out_positions or
+ * num_out, out_normals without normals or out_values without values, a NaN or non-positive cell, a bad mode or memory kind, a
+ * finite point with |c_a| >= 2^20.  n >= 2^31: FI_ERR_UNSUPPORTED.  A cell that holds the whole cloud is one thread's work:
+ * slow and correct.
+ * Not offered: lists of the neighbours within a radius, k > 32, a median / MAD threshold, moving-least-squares smoothing of
+ * positions, slab contexts, approximate search. */
+#define FI_THIN_MEAN  0
+#define FI_THIN_FIRST 1
+typedef struct fi_outlier_stats {
+	long   counted, kept;
+	double mean, stddev, threshold;
+} fi_outlier_stats;
+int fi_radius_count(fi_ctx* ctx, long n, const float* queries, float radius, int limit, int* counts, int memory);
+int fi_points_radius_count(fi_points* points, long n, const float* queries, float radius, int limit, int* counts, int memory);
+int fi_neighbour_distances(fi_ctx* ctx, int k, float max_distance, float* mean, float* kth, int* counts, int memory);
+int fi_points_neighbour_distances(fi_points* points, int k, float max_distance, float* mean, float* kth, int* counts, int memory);
+int fi_outliers_statistical(fi_ctx* ctx, int k, float max_distance, float std_ratio, unsigned char* keep, fi_outlier_stats* stats,
+                            int memory);
+int fi_points_outliers_statistical(fi_points* points, int k, float max_distance, float std_ratio, unsigned char* keep,
+                                   fi_outlier_stats* stats, int memory);
+int fi_outliers_radius(fi_ctx* ctx, float radius, int min_neighbours, unsigned char* keep, long* num_kept, int memory);
+int fi_points_outliers_radius(fi_points* points, float radius, int min_neighbours, unsigned char* keep, long* num_kept, int memory);
+int fi_cloud_thin(int ndim, long n, const float* positions, const float* normals, const float* values, float cell,
+                  const float* origin, int mode, float* out_positions, float* out_normals, float* out_values, int* out_counts,
+                  long long* out_indices, int* cell_map, long* num_out, int memory);
+
 /* ---- exact distances to a surface; redistancing ------------------------------------------------
  * The contract ("Distances to a surface") is this project's own.  All arithmetic is fp32, one rounding per
  * operation (no FMA contraction):

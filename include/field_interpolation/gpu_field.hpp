@@ -59,6 +59,13 @@ struct Registration
 	double    rms, weighted_rms, last_rotation, last_translation;
 };
 
+// The figures of the statistical outlier rule (include/fi_hip.h fi_outlier_stats), field for field.
+struct OutlierStats
+{
+	long   counted, kept;
+	double mean, stddev, threshold;
+};
+
 class GpuLatticeField
 {
 public:
@@ -190,6 +197,25 @@ public:
 	bool orient_normals(std::vector<float>* normals, int k = 16, const std::vector<float>& viewpoints = std::vector<float>(),
 	                    std::vector<long long>* components = nullptr,
 	                    float max_distance = std::numeric_limits<float>::infinity()) const;
+	// How many data points lie within `radius` of each query (a point exactly on the radius included), at most `limit`: the
+	// search stops there; -1 for a non-finite query.  The contract is include/fi_hip.h fi_radius_count.
+	bool radius_count(const std::vector<float>& queries, float radius, std::vector<int>* counts,
+	                  int limit = std::numeric_limits<int>::max()) const;
+	// Per data point, in the order the points were added: the mean distance to its k nearest OTHER points within
+	// max_distance (1 <= k <= 32; the point itself is left out by its index), the distance to the last of them and their
+	// number; +inf, +inf, 0 without a neighbour, NaN, NaN, 0 for a non-finite point.  Any of the three may be null, not all.
+	// mean or kth to the power ndim is the density weight add_points takes as point_weights.  The contract is
+	// include/fi_hip.h fi_neighbour_distances.
+	bool neighbour_distances(int k, std::vector<float>* mean, std::vector<float>* kth = nullptr, std::vector<int>* counts = nullptr,
+	                         float max_distance = std::numeric_limits<float>::infinity()) const;
+	// The statistical outlier rule: keep[i] = 1 where point i's mean neighbour distance is at most mean + std_ratio * standard
+	// deviation of that figure over the cloud.  stats (optional): counted, kept, mean, stddev, threshold.  The contract is
+	// include/fi_hip.h fi_outliers_statistical.
+	bool statistical_outliers(int k, float std_ratio, std::vector<unsigned char>* keep, OutlierStats* stats = nullptr,
+	                          float max_distance = std::numeric_limits<float>::infinity()) const;
+	// keep[i] = 1 where point i is finite and has at least min_neighbours other points within radius.  The contract is
+	// include/fi_hip.h fi_outliers_radius.
+	bool radius_outliers(float radius, int min_neighbours, std::vector<unsigned char>* keep, long* num_kept = nullptr) const;
 	// nearest() of every lattice point (x fastest): num_unknowns() distances (and indices)
 	bool distance_field(std::vector<float>* distances, std::vector<long long>* indices = nullptr,
 	                    float max_distance = std::numeric_limits<float>::infinity()) const;
@@ -235,6 +261,18 @@ private:
 std::unique_ptr<GpuLatticeField> gpu_sdf_from_points(const std::vector<int>& sizes, const Weights& weights,
                                                      int num_points, const float positions[], const float* normals,
                                                      const float* point_weights);
+
+// A point cloud thinned on a uniform grid of spacing `cell` on the device, no lattice needed: one output point per occupied
+// cell in ascending cell order -- the members' mean position (and value, and their summed, normalised normal), or with
+// first = true the member with the lowest index bit for bit.  positions: ndim floats per point; normals (ndim per point)
+// and values (one per point) may be empty, and so may origin (zeros).  Non-finite points are left out.  out_counts: members
+// per cell; out_indices: a cell's lowest member; cell_map: per input point its output, -1 for a point left out; all
+// optional.  The contract is include/fi_hip.h fi_cloud_thin.  false: the library refused the call.
+bool thin_points(int ndim, const std::vector<float>& positions, float cell, std::vector<float>* out_positions,
+                 const std::vector<float>& normals = std::vector<float>(), std::vector<float>* out_normals = nullptr,
+                 const std::vector<float>& values = std::vector<float>(), std::vector<float>* out_values = nullptr,
+                 const std::vector<float>& origin = std::vector<float>(), bool first = false, std::vector<int>* out_counts = nullptr,
+                 std::vector<long long>* out_indices = nullptr, std::vector<int>* cell_map = nullptr);
 
 // The stateless solver calls of sparse_linear.hpp keep device contexts between calls, keyed by shape and precision (at
 // most six, systems of up to 2^20 unknowns only; larger systems get a context per call): the per-frame caller's latency
