@@ -31,6 +31,7 @@ SYMBOLS = [
     "fi_orient_normals", "fi_points_orient_normals",
     "fi_radius_count", "fi_points_radius_count", "fi_neighbour_distances", "fi_points_neighbour_distances",
     "fi_outliers_statistical", "fi_points_outliers_statistical", "fi_outliers_radius", "fi_points_outliers_radius", "fi_cloud_thin",
+    "fi_cluster", "fi_points_cluster", "fi_cluster_measure",
     "fi_surface_create", "fi_surface_from_mesh", "fi_surface_distance", "fi_surface_distance_field", "fi_surface_destroy",
     "fi_surface_raycast", "fi_surface_count_hits", "fi_surface_contains", "fi_surface_signed_distance",
     "fi_surface_signed_distance_field",
@@ -112,6 +113,14 @@ class FiRegistration(C.Structure):
 
 class FiOutlierStats(C.Structure):
     _fields_ = [("counted", C.c_long), ("kept", C.c_long), ("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double)]
+
+
+class FiClusterStats(C.Structure):
+    _fields_ = [("clusters", C.c_long), ("core", C.c_long), ("border", C.c_long), ("noise", C.c_long), ("non_finite", C.c_long)]
+
+
+class FiClusterRow(C.Structure):
+    _fields_ = [("count", C.c_long), ("core", C.c_long), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("centroid", C.c_double * 3)]
 
 
 class FiError(RuntimeError):
@@ -224,6 +233,9 @@ def lib():
     L.fi_points_outliers_radius.argtypes = [vp, C.c_float, C.c_int, vp, C.POINTER(C.c_long), C.c_int]
     L.fi_cloud_thin.argtypes = [C.c_int, C.c_long, fp, fp, fp, C.c_float, C.POINTER(C.c_float), C.c_int, fp, fp, fp, vp, vp, vp,
                                 C.POINTER(C.c_long), C.c_int]
+    L.fi_cluster.argtypes = [vp, C.c_float, C.c_int, vp, vp, C.POINTER(FiClusterStats), C.c_int]
+    L.fi_points_cluster.argtypes = [vp, C.c_float, C.c_int, vp, vp, C.POINTER(FiClusterStats), C.c_int]
+    L.fi_cluster_measure.argtypes = [C.c_int, C.c_long, fp, vp, vp, C.c_long, C.POINTER(FiClusterRow), C.c_int]
     L.fi_surface_create.argtypes = [C.POINTER(vp), C.c_int, C.c_long, fp, C.c_long, vp, C.c_int]
     L.fi_surface_from_mesh.argtypes = [C.POINTER(vp), vp]
     L.fi_surface_distance.argtypes = [vp, C.c_long, fp, C.c_float, fp, vp, fp, C.c_int]

@@ -524,6 +524,32 @@ def _radius_outliers(call, n, radius, min_neighbours, device):
     return _as_mask(keep), int(kept.value)
 
 
+def _cluster(call, n, eps, min_points, core, stats, device):
+    """Shared body: call(eps, min_points, labels, core, stats, memory) is the C entry point -> labels, or a tuple of labels
+    and what was asked for (core mask, stats dict)"""
+    dev = "cuda" if device else None
+    labels, pl = _cloud_out(dev, (n,), np.int32)
+    flags, pc = _cloud_out(dev, (n,), np.uint8) if core else (None, None)
+    s = _capi.FiClusterStats()
+    check(call(float(eps), int(min_points), pl, pc, C.byref(s), FI_DEVICE if device else FI_HOST))
+    out = (labels,)
+    if core:
+        out += (_as_mask(flags),)
+    if stats:
+        out += ({"clusters": int(s.clusters), "core": int(s.core), "border": int(s.border), "noise": int(s.noise),
+                 "non_finite": int(s.non_finite)},)
+    return out if len(out) > 1 else labels
+
+
+_CLUSTER_DOC = """Labels (num_points,) int32 of the clusters of the set's own points (include/fi_hip.h fi_cluster): a point
+        is CORE when at least min_points points of the set, itself included, lie within eps of it (a point exactly at eps
+        counts); core points within eps of each other share a cluster, and clusters are numbered by their lowest core point; a
+        point that is not core takes the cluster of its nearest core point within eps (ties: the lower index), and -1 (noise)
+        without one; a non-finite point gets -1.  min_points = 1: plain Euclidean clustering, every finite point in a cluster.
+        core=True adds the core mask (bool), stats=True a dict: clusters, core, border, noise, non_finite.  numpy arrays, or
+        torch tensors on the GPU with device=True.  An eps that spans the cloud makes every point visit every other: slow."""
+
+
 def _estimate_normals(call, ndim, n, k, max_distance, viewpoints, directions, variation, device):
     """Shared body of the normal estimation: call(k, max_distance, orient, guides, num_guides, normals, variation, memory)
     is the C entry point.  Outputs are numpy arrays, or torch tensors on the GPU when the guides are device tensors or with
@@ -729,6 +755,12 @@ class PointIndex:
         def call(r, mn, kp, nk, mem):
             return _capi.lib().fi_points_outliers_radius(self._h, r, mn, kp, nk, mem)
         return _radius_outliers(call, self.num_points, radius, min_neighbours, device)
+
+    def cluster(self, eps, min_points=1, core=False, stats=False, device=False):
+        def call(e, mp, lb, cr, st, mem):
+            return _capi.lib().fi_points_cluster(self._h, e, mp, lb, cr, st, mem)
+        return _cluster(call, self.num_points, eps, min_points, core, stats, device)
+    cluster.__doc__ = _CLUSTER_DOC
 
     def distance_field(self, sizes, max_distance=math.inf, indices=False, device=False):
         """PointIndex.nearest of every point of a lattice of `sizes` (x fastest), flat."""
@@ -1202,13 +1234,16 @@ def thin_points(positions, cell, normals=None, values=None, origin=None, mode="m
 
 
 def clean_points(positions, normals=None, values=None, cell=None, k=None, std_ratio=2.0, radius=None, min_neighbours=2,
-                 max_distance=math.inf):
+                 max_distance=math.inf, cluster_eps=None, cluster_min_points=1, largest=None, min_cluster=0):
     """A scan made fit for estimate_normals / sdf_from_points on the device, in this order and each step only if asked for:
     thin_points(cell) (mean mode), PointIndex.radius_outliers(radius, min_neighbours), PointIndex.statistical_outliers(k,
     std_ratio, max_distance).  Each filter builds its PointIndex over what the step before left.  numpy arrays, or torch
     CUDA tensors that stay on the device.  -> (positions, normals, values, report): the surviving arrays (None where none was
     given) and a dict with `input`, `output`, what each stage removed (`thinned`, `radius`, `statistical`) and the
-    statistical stage's `stats`."""
+    statistical stage's `stats`.  With cluster_eps a last step runs after the outlier rules, for the stray CLUMP that both of
+    them keep: PointIndex.cluster(cluster_eps, cluster_min_points) over what is left, and only the points of the clusters
+    that keep_clusters(rows, largest, min_cluster) chooses survive (noise points go); the report gains `cluster`, what the
+    step removed, and `clusters`, its stats."""
     as_array = lambda a: a if a is None or hasattr(a, "data_ptr") else np.ascontiguousarray(a, np.float32)  # noqa: E731
     pos, nrm, val = as_array(positions), as_array(normals), as_array(values)
     on_device = bool(getattr(pos, "is_cuda", False))
@@ -1233,8 +1268,83 @@ def clean_points(positions, normals=None, values=None, cell=None, k=None, std_ra
         report["statistical"] = _rows(pos) - stats["kept"]
         report["stats"] = stats
         pos, nrm, val = select(keep)
+    if cluster_eps is not None:
+        labels, stats = PointIndex(pos).cluster(cluster_eps, cluster_min_points, stats=True, device=on_device)
+        chosen = keep_clusters(cluster_measure(pos, labels, num_clusters=stats["clusters"]), largest, min_cluster)
+        chosen = np.concatenate([chosen, [False]])           # (the label -1 reads the entry at the end)
+        if on_device:
+            import torch
+            keep = torch.from_numpy(chosen).to(labels.device)[labels.long()]
+        else:
+            keep = chosen[labels]
+        report["cluster"] = _rows(pos) - int(keep.sum())
+        report["clusters"] = stats
+        pos, nrm, val = select(keep)
     report["output"] = _rows(pos)
     return pos, nrm, val, report
+
+
+def cluster_points(positions, eps, min_points=1, measure=False):
+    """The clusters of a point cloud on the device: PointIndex(positions).cluster(eps, min_points) -> labels (n,) int32,
+    where `positions` lives (numpy, or a torch CUDA tensor); measure=True: -> (labels, rows), rows being cluster_measure's
+    table of the clusters found."""
+    on_device = bool(getattr(positions, "is_cuda", False))
+    labels, stats = PointIndex(positions).cluster(eps, min_points, stats=True, device=on_device)
+    if not measure:
+        return labels
+    return labels, cluster_measure(positions, labels, num_clusters=stats["clusters"])
+
+
+def cluster_measure(positions, labels, core=None, num_clusters=None):
+    """One row per cluster of a labelling of `positions` (n, ndim) -- or (n,) in 1-D -- by `labels` (n,) int32 with values in
+    [-1, num_clusters) (default: the largest label + 1), found on the device: a list of dicts with `count`, `core` (the
+    members flagged in the mask `core`, 0 without one), `lo` / `hi` (the bounding box, float32 (ndim,)) and `centroid`
+    (float64 (ndim,), summed in a fixed order).  numpy arrays or torch CUDA tensors, all in the same memory (include/fi_hip.h
+    fi_cluster_measure)."""
+    p, pmem, pkeep = _buf(positions)
+    shape = tuple(pkeep.shape)
+    if len(shape) not in (1, 2):
+        raise ValueError("positions is (n, ndim), or (n,) in 1-D, not %r" % (shape,))
+    n, ndim = shape[0], (shape[1] if len(shape) == 2 else 1)
+    lb, lmem, lkeep = _buf(labels, np.int32)
+    if tuple(lkeep.shape) != (n,):
+        raise ValueError("labels is (%d,), one per point" % n)
+    cr, cmem, ckeep = None, None, None
+    if core is not None:
+        if hasattr(core, "data_ptr"):
+            import torch
+            ckeep = core.to(torch.uint8).contiguous()
+            cr, cmem = C.c_void_p(ckeep.data_ptr()), (FI_DEVICE if ckeep.is_cuda else FI_HOST)
+        else:
+            ckeep = np.ascontiguousarray(core, np.uint8)
+            cr, cmem = C.c_void_p(ckeep.ctypes.data), FI_HOST
+        if tuple(ckeep.shape) != (n,):
+            raise ValueError("core is (%d,), one per point" % n)
+    mem = _same_memory(pmem, lmem, cmem)
+    if num_clusters is None:
+        num_clusters = int(lkeep.max()) + 1 if n else 0
+    nc = max(0, int(num_clusters))
+    rows = (_capi.FiClusterRow * max(nc, 1))()
+    check(_capi.lib().fi_cluster_measure(ndim, n, p if n else None, lb if n else None, cr if n else None, int(num_clusters), rows, mem))
+    table = np.frombuffer(rows, np.dtype(_capi.FiClusterRow), nc)          # (columns first: a row at a time costs 2 us a cluster)
+    count, cores = table["count"].tolist(), table["core"].tolist()
+    lo, hi, centroid = (np.ascontiguousarray(table[key][:, :ndim]) for key in ("lo", "hi", "centroid"))
+    return [{"count": count[c], "core": cores[c], "lo": lo[c], "hi": hi[c], "centroid": centroid[c]} for c in range(nc)]
+
+
+def keep_clusters(rows, largest=None, min_points=0):
+    """A boolean mask over the rows of cluster_measure: the clusters with at least min_points members; with largest = k only
+    the k of them with the most members (ties go to the lower cluster number).  Evaluated on the host, like keep_parts."""
+    count = np.array([r["count"] for r in rows], np.int64)
+    mask = count >= int(min_points)
+    if largest is not None:
+        if int(largest) < 0:
+            raise ValueError("largest must be >= 0")
+        order = np.argsort(-count, kind="stable")            # descending count, ties by ascending cluster number
+        order = order[mask[order]][:int(largest)]
+        mask = np.zeros(len(count), bool)
+        mask[order] = True
+    return mask
 
 
 def mesh_to_sdf(mesh, sizes, max_distance=math.inf):
@@ -1633,6 +1743,13 @@ class LatticeField:
         def call(r, mn, kp, nk, mem):
             return _capi.lib().fi_outliers_radius(self._h, r, mn, kp, nk, mem)
         return _radius_outliers(call, self._point_count(), radius, min_neighbours, device)
+
+    def cluster(self, eps, min_points=1, core=False, stats=False, device=False):
+        """PointIndex.cluster of the data points of this context, in the order they were added (include/fi_hip.h
+        fi_cluster)."""
+        def call(e, mp, lb, cr, st, mem):
+            return _capi.lib().fi_cluster(self._h, e, mp, lb, cr, st, mem)
+        return _cluster(call, self._point_count(), eps, min_points, core, stats, device)
 
     def distance_field(self, max_distance=math.inf, indices=False, device=False):
         """LatticeField.nearest of every lattice point (x fastest), flat: numpy arrays, or torch tensors with device=True."""

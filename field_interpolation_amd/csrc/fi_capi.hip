@@ -17,6 +17,7 @@
 #include "fi_meshpts.h"
 #include "fi_register.h"
 #include "fi_cloud.h"
+#include "fi_cluster.h"
 
 #include <memory>
 
@@ -1678,6 +1679,52 @@ int fi_cloud_thin(int ndim, long n, const float* positions, const float* normals
 	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld points in one call", n);
 	fi::cloud_thin(ndim, n, positions, normals, values, cell, origin, mode, out_positions, out_normals, out_values, out_counts, out_indices,
 	               cell_map, num_out, memory);
+	FI_API_END
+}
+
+
+// ---- the clusters of a point cloud (fi_cluster.hip) ----------------------------------------------
+namespace {
+void check_cluster(float eps, int min_points, const int* labels, const fi_cluster_stats* stats, int memory)
+{
+	FI_REQUIRE(eps >= 0.0f && !std::isinf(eps), FI_ERR_INVALID, "eps must be finite and >= 0 (got %g)", static_cast<double>(eps));  // (NaN fails)
+	FI_REQUIRE(min_points >= 1, FI_ERR_INVALID, "min_points must be >= 1 (got %d)", min_points);
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	FI_REQUIRE(labels || stats, FI_ERR_INVALID, "every output is null");
+}
+}  // namespace
+
+int fi_cluster(fi_ctx* c, float eps, int min_points, int* labels, unsigned char* core, fi_cluster_stats* stats, int memory)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	check_cluster(eps, min_points, labels, stats, memory);
+	check_undivided(c);
+	fi::cluster_labels(fi::nearest_of(c), eps, min_points, labels, core, stats, memory, c->stream);
+	FI_API_END
+}
+
+int fi_points_cluster(fi_points* h, float eps, int min_points, int* labels, unsigned char* core, fi_cluster_stats* stats, int memory)
+{
+	FI_API_BEGIN
+	check_points(h);
+	check_cluster(eps, min_points, labels, stats, memory);
+	fi::cluster_labels(h->t, eps, min_points, labels, core, stats, memory, nullptr);
+	FI_API_END
+}
+
+int fi_cluster_measure(int ndim, long n, const float* positions, const int* labels, const unsigned char* core, long num_clusters,
+                       fi_cluster_row* rows, int memory)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(1 <= ndim && ndim <= FI_MAX_DIM, FI_ERR_INVALID, "ndim must be 1..%d (got %d)", FI_MAX_DIM, ndim);
+	FI_REQUIRE(n >= 0 && num_clusters >= 0, FI_ERR_INVALID, "n = %ld, num_clusters = %ld", n, num_clusters);
+	FI_REQUIRE(n == 0 || (positions != nullptr && labels != nullptr), FI_ERR_INVALID, "null positions or labels");
+	FI_REQUIRE(num_clusters == 0 || rows != nullptr, FI_ERR_INVALID, "rows is null");
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	FI_REQUIRE(n < (1L << 31) && num_clusters < (1L << 31), FI_ERR_UNSUPPORTED, "%ld points, %ld clusters in one call", n, num_clusters);
+	fi::cluster_measure(ndim, n, positions, labels, core, num_clusters, rows, memory);
 	FI_API_END
 }
 

@@ -23,6 +23,7 @@
 #include "fi_solver_internal.h"
 #include "fi_parts.h"
 #include "fi_prim.h"
+#include "fi_unionfind.h"
 
 #include <algorithm>
 #include <memory>
@@ -39,10 +40,9 @@ struct MeshParts {
 
 namespace {
 
-constexpr int kChunk = 256;  // primitives a workgroup of the measuring pass sums: one each
+using namespace unionfind;  // word_load, word_store, find_root, unite
 
-__device__ inline uint32_t word_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline void word_store(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+constexpr int kChunk = 256;  // primitives a workgroup of the measuring pass sums: one each
 
 // ---- labels ---------------------------------------------------------------------------------------------------------
 
@@ -52,34 +52,6 @@ __global__ __launch_bounds__(kThreads) void k_parts_start(int64_t nv, uint32_t* 
 	if (i > nv) { return; }
 	used[i] = 0;  // (entry nv: the scans' total)
 	if (i < nv) { parent[i] = static_cast<uint32_t>(i); }
-}
-
-// the root of v's tree as it stands, halving the path on the way (every word written is an ancestor of its vertex)
-__device__ inline uint32_t find_root(uint32_t* parent, uint32_t v)
-{
-	for (;;) {
-		const uint32_t p = word_load(&parent[v]);
-		if (p == v) { return v; }
-		const uint32_t g = word_load(&parent[p]);
-		if (g == p) { return p; }
-		word_store(&parent[v], g);
-		v = g;
-	}
-}
-
-__device__ inline void unite(uint32_t* parent, uint32_t a, uint32_t b)
-{
-	for (;;) {
-		a = find_root(parent, a);
-		b = find_root(parent, b);
-		if (a == b) { return; }
-		const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
-		const uint32_t was = atomicCAS(&parent[hi], hi, lo);
-		if (was == hi) { return; }
-		// hi is no root any more: somebody else's swap succeeded and hung it under `was`; that tree and lo's are still to be joined
-		a = was;
-		b = lo;
-	}
 }
 
 template <int D>

@@ -655,6 +655,27 @@ bool GpuLatticeField::radius_outliers(float radius, int min_neighbours, std::vec
 	return true;
 }
 
+static_assert(sizeof(ClusterStats) == sizeof(fi_cluster_stats), "ClusterStats mirrors fi_cluster_stats");
+
+bool GpuLatticeField::cluster_points(float eps, int min_points, std::vector<int>* labels, std::vector<unsigned char>* core,
+                                     ClusterStats* stats) const
+{
+	long n = 0;
+	if (!labels || fi_point_count(ctx_, &n) != FI_OK) {
+		warn("cluster_points");
+		return false;
+	}
+	labels->resize(n);
+	if (core) { core->resize(n); }
+	fi_cluster_stats s;
+	if (fi_cluster(ctx_, eps, min_points, n ? labels->data() : nullptr, core && n ? core->data() : nullptr, &s, FI_HOST) != FI_OK) {
+		warn("cluster_points");
+		return false;
+	}
+	if (stats) { std::memcpy(stats, &s, sizeof(s)); }
+	return true;
+}
+
 bool thin_points(int ndim, const std::vector<float>& positions, float cell, std::vector<float>* out_positions,
                  const std::vector<float>& normals, std::vector<float>* out_normals, const std::vector<float>& values,
                  std::vector<float>* out_values, const std::vector<float>& origin, bool first, std::vector<int>* out_counts,

@@ -1039,6 +1039,55 @@ int fi_cloud_thin(int ndim, long n, const float* positions, const float* normals
                   const float* origin, int mode, float* out_positions, float* out_normals, float* out_values, int* out_counts,
                   long long* out_indices, int* cell_map, long* num_out, int memory);
 
+/* ---- the clusters of a point cloud: Euclidean clusters and DBSCAN ------------------------------------
+ * The contract (tests/cluster_reference.py is its definition in numpy).  The point set, s(p, q), finiteness
+ * and the search structure are fi_nearest's; "within eps" is fi_radius_count's rule, sqrtf(s(p_j, p_i)) <= eps: a pair exactly
+ * at eps is joined.  ndim = 1, 2 or 3.  Every output is defined bit for bit and depends neither on the launch shape nor on
+ * timing.
+ *
+ * fi_cluster labels the set's own points (a context's points in the order they were added, or a fi_points):
+ *   - CORE: a finite point i is core iff at least min_points finite points j have sqrtf(s(p_j, p_i)) <= eps.  The count
+ *     includes i itself (the count of sklearn and Open3D); a duplicate of i counts as another point.  min_points = 1 makes
+ *     every finite point core: plain Euclidean clustering (PCL's EuclideanClusterExtraction).
+ *   - CLUSTERS: two core points within eps of each other are joined; the clusters are the connected components of that graph
+ *     over the core points, numbered 0, 1, ... in ascending order of each cluster's LOWEST CORE POINT INDEX.
+ *   - BORDER: a finite point that is not core and has a core point within eps takes the cluster of its nearest one: of the
+ *     first pair (s, j) in lexicographic order over the core points j -- fi_nearest's tie rule restricted to core points.
+ *     (Classic DBSCAN's "whichever cluster reaches it first" depends on the order of the visit; this rule does not.)  A
+ *     border point joins nothing else to anything.
+ *   - NOISE: every other finite point gets the label -1; so does a non-finite point.
+ * labels int[n] in `memory`; core unsigned char[n] in `memory` (1 for a core point) or NULL; stats on the HOST or NULL; not
+ * both labels and stats NULL.  stats: clusters, and the numbers of core, border, noise (finite, label -1) and non-finite
+ * points, which add up to n.  n = 0 or no finite point: zero clusters, FI_OK.  FI_ERR_INVALID: a NaN, negative or infinite
+ * eps; min_points < 1; a bad memory kind; labels and stats both NULL.  A slab context: FI_ERR_UNSUPPORTED, as for the four
+ * cleaning calls.  Cost: an eps that reaches across the whole cloud makes every thread visit every point: slow and correct.
+ *
+ * fi_cluster_measure: one row per cluster of a labelling; it needs no search structure and runs on the current device.
+ * positions float[n * ndim], labels int[n] and core unsigned char[n] (or NULL) in `memory`; rows on the HOST, num_clusters of
+ * them.  The members of cluster c are the points with label c.  count and core (the members whose core byte is not 0; 0
+ * with core = NULL) are exact; lo / hi are the fp32 minimum / maximum of the members' coordinates; centroid[a] takes the
+ * members in ascending index, cut into chunks of 256 consecutive members: each chunk is summed in fp64 by fi_mesh_deviation's
+ * fixed tree (s[t] += s[t + w], w = 128 .. 1, the tail padded with 0.0), the chunk sums are added ascending from 0.0 and the
+ * total is divided by count.  Unused axes are 0; a cluster without a member is a row of zeros.  A cluster of a million
+ * points costs one thread 4096 additions.  FI_ERR_INVALID: ndim outside 1..3, n or num_clusters < 0, NULL positions or labels
+ * with n > 0, NULL rows with num_clusters > 0, a bad memory kind, a label outside [-1, num_clusters).  n or num_clusters
+ * >= 2^31: FI_ERR_UNSUPPORTED.
+ * Not offered: lists of the neighbours within a radius, HDBSCAN, OPTICS, region growing by normals, RANSAC plane
+ * segmentation, slab contexts, approximate search. */
+typedef struct fi_cluster_stats {
+	long clusters, core, border, noise, non_finite;
+} fi_cluster_stats;
+typedef struct fi_cluster_row {
+	long   count, core;
+	float  lo[3], hi[3];
+	double centroid[3];
+} fi_cluster_row;
+int fi_cluster(fi_ctx* ctx, float eps, int min_points, int* labels, unsigned char* core, fi_cluster_stats* stats, int memory);
+int fi_points_cluster(fi_points* points, float eps, int min_points, int* labels, unsigned char* core, fi_cluster_stats* stats,
+                      int memory);
+int fi_cluster_measure(int ndim, long n, const float* positions, const int* labels, const unsigned char* core, long num_clusters,
+                       fi_cluster_row* rows, int memory);
+
 /* ---- exact distances to a surface; redistancing ------------------------------------------------
  * The contract ("Distances to a surface") is this project's own.  All arithmetic is fp32, one rounding per
  * operation (no FMA contraction):

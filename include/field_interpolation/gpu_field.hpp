@@ -66,6 +66,12 @@ struct OutlierStats
 	double mean, stddev, threshold;
 };
 
+// The totals of a clustering (include/fi_hip.h fi_cluster_stats), field for field.
+struct ClusterStats
+{
+	long clusters, core, border, noise, non_finite;
+};
+
 class GpuLatticeField
 {
 public:
@@ -216,6 +222,13 @@ public:
 	// keep[i] = 1 where point i is finite and has at least min_neighbours other points within radius.  The contract is
 	// include/fi_hip.h fi_outliers_radius.
 	bool radius_outliers(float radius, int min_neighbours, std::vector<unsigned char>* keep, long* num_kept = nullptr) const;
+	// The clusters of the data points, in the order the points were added: labels[i] is point i's cluster, -1 for noise and
+	// for a non-finite point.  A point is core when min_points points, itself included, lie within eps of it (min_points = 1:
+	// plain Euclidean clustering); core points within eps of each other share a cluster, numbered by their lowest core point;
+	// any other point takes the cluster of its nearest core point within eps.  core (optional): 1 for a core point.  stats
+	// (optional): clusters, core, border, noise, non_finite.  The contract is include/fi_hip.h fi_cluster.
+	bool cluster_points(float eps, int min_points, std::vector<int>* labels, std::vector<unsigned char>* core = nullptr,
+	                    ClusterStats* stats = nullptr) const;
 	// nearest() of every lattice point (x fastest): num_unknowns() distances (and indices)
 	bool distance_field(std::vector<float>* distances, std::vector<long long>* indices = nullptr,
 	                    float max_distance = std::numeric_limits<float>::infinity()) const;
