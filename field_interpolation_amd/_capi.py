@@ -31,7 +31,7 @@ SYMBOLS = [
     "fi_orient_normals", "fi_points_orient_normals",
     "fi_radius_count", "fi_points_radius_count", "fi_neighbour_distances", "fi_points_neighbour_distances",
     "fi_outliers_statistical", "fi_points_outliers_statistical", "fi_outliers_radius", "fi_points_outliers_radius", "fi_cloud_thin",
-    "fi_cluster", "fi_points_cluster", "fi_cluster_measure",
+    "fi_cluster", "fi_points_cluster", "fi_cluster_measure", "fi_plane_fit", "fi_planes_segment",
     "fi_surface_create", "fi_surface_from_mesh", "fi_surface_distance", "fi_surface_distance_field", "fi_surface_destroy",
     "fi_surface_raycast", "fi_surface_count_hits", "fi_surface_contains", "fi_surface_signed_distance",
     "fi_surface_signed_distance_field",
@@ -121,6 +121,16 @@ class FiClusterStats(C.Structure):
 
 class FiClusterRow(C.Structure):
     _fields_ = [("count", C.c_long), ("core", C.c_long), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("centroid", C.c_double * 3)]
+
+
+class FiPlaneOptions(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("max_trials", C.c_long), ("confidence", C.c_double), ("refine", C.c_int),
+                ("seed", C.c_ulonglong), ("axis", C.c_float * 3), ("min_cos", C.c_float)]
+
+
+class FiPlaneModel(C.Structure):
+    _fields_ = [("found", C.c_int), ("refits", C.c_int), ("inliers", C.c_long), ("candidates", C.c_long), ("trials", C.c_long),
+                ("normal", C.c_double * 3), ("offset", C.c_double), ("rms", C.c_double)]
 
 
 class FiError(RuntimeError):
@@ -236,6 +246,9 @@ def lib():
     L.fi_cluster.argtypes = [vp, C.c_float, C.c_int, vp, vp, C.POINTER(FiClusterStats), C.c_int]
     L.fi_points_cluster.argtypes = [vp, C.c_float, C.c_int, vp, vp, C.POINTER(FiClusterStats), C.c_int]
     L.fi_cluster_measure.argtypes = [C.c_int, C.c_long, fp, vp, vp, C.c_long, C.POINTER(FiClusterRow), C.c_int]
+    L.fi_plane_fit.argtypes = [C.c_int, C.c_long, fp, vp, C.POINTER(FiPlaneOptions), C.POINTER(FiPlaneModel), vp, C.c_int]
+    L.fi_planes_segment.argtypes = [C.c_int, C.c_long, fp, vp, C.POINTER(FiPlaneOptions), C.c_int, C.c_long, vp,
+                                    C.POINTER(FiPlaneModel), ip, C.c_int]
     L.fi_surface_create.argtypes = [C.POINTER(vp), C.c_int, C.c_long, fp, C.c_long, vp, C.c_int]
     L.fi_surface_from_mesh.argtypes = [C.POINTER(vp), vp]
     L.fi_surface_distance.argtypes = [vp, C.c_long, fp, C.c_float, fp, vp, fp, C.c_int]

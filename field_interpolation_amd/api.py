@@ -1233,8 +1233,85 @@ def thin_points(positions, cell, normals=None, values=None, origin=None, mode="m
     return got if len(got) > 1 else got[0]
 
 
+def _flags(a):
+    """(pointer, memory kind, keep-alive object) of a mask as uint8 flags: a numpy array, a torch tensor, or None"""
+    if a is None:
+        return None, None, None
+    if hasattr(a, "data_ptr"):
+        import torch
+        t = a.to(torch.uint8).contiguous()
+        return C.c_void_p(t.data_ptr()), (FI_DEVICE if t.is_cuda else FI_HOST), t
+    arr = np.ascontiguousarray(a).astype(np.uint8)
+    return C.c_void_p(arr.ctypes.data), FI_HOST, arr
+
+
+def _plane_options(ndim, threshold, max_trials, confidence, refine, seed, axis, max_angle):
+    opt = _capi.FiPlaneOptions(float(threshold), int(max_trials), float(confidence), int(refine), int(seed) & (2 ** 64 - 1))
+    if (axis is None) != (max_angle is None):
+        raise ValueError("axis and max_angle go together")
+    if axis is not None:
+        ax = np.ascontiguousarray(axis, np.float32).reshape(-1)
+        if ax.size != ndim:
+            raise ValueError("axis has %d coordinates" % ndim)
+        if not 0.0 <= float(max_angle) <= 90.0:
+            raise ValueError("max_angle is in degrees, 0 .. 90")
+        opt.axis[:ndim] = ax.tolist()
+        opt.min_cos = float(np.float32(math.cos(math.radians(float(max_angle)))))   # no trigonometry on the device
+    return opt
+
+
+def _plane_dict(m, ndim):
+    return {"found": bool(m.found), "normal": np.array(m.normal[:ndim], np.float64), "offset": float(m.offset),
+            "inliers": int(m.inliers), "candidates": int(m.candidates), "trials": int(m.trials), "refits": int(m.refits),
+            "rms": float(m.rms)}
+
+
+def _plane_cloud(positions, mask):
+    p, pmem, pkeep = _buf(positions)
+    shape = tuple(pkeep.shape)
+    if len(shape) != 2:
+        raise ValueError("positions is (n, ndim), not %r" % (shape,))
+    mk, mmem, mkeep = _flags(mask)
+    if mask is not None and tuple(mkeep.shape) != (shape[0],):
+        raise ValueError("mask is (%d,), one per point" % shape[0])
+    return p, mk, shape[0], shape[1], _same_memory(pmem, mmem), (pkeep, mkeep)
+
+
+def segment_plane(positions, threshold, max_trials=1024, confidence=0.999, refine=2, seed=0, mask=None, axis=None, max_angle=None):
+    """The dominant plane (3-D) or line (2-D) of a point cloud on the device: RANSAC with an exact inlier count, then
+    `refine` least-squares refits.  positions (n, ndim), a numpy array or a torch CUDA tensor that stays on the device; a point
+    within `threshold` of the plane (inclusive) is an inlier.  At most max_trials hypotheses, fewer once the best one would
+    have been drawn with probability `confidence` (0: never stop early); mask (n,): the points that take part; axis and
+    max_angle (degrees): only planes whose normal lies within that angle of +-axis.  -> (model, inliers): a dict with `found`,
+    `normal` (float64 (ndim,), its largest component positive), `offset` (normal . x + offset = 0), `inliers`, `candidates`,
+    `trials`, `refits` and `rms`, and a boolean mask (n,) where `positions` lives.  Every figure is defined bit for bit
+    (include/fi_hip.h fi_plane_fit)."""
+    p, mk, n, ndim, mem, keep = _plane_cloud(positions, mask)
+    opt = _plane_options(ndim, threshold, max_trials, confidence, refine, seed, axis, max_angle)
+    model = _capi.FiPlaneModel()
+    out, ptr = _cloud_out(keep[0].device if mem == FI_DEVICE else None, (n,), np.uint8)
+    check(_capi.lib().fi_plane_fit(ndim, n, p if n else None, mk if n else None, C.byref(opt), C.byref(model), ptr, mem))
+    return _plane_dict(model, ndim), _as_mask(out)
+
+
+def segment_planes(positions, threshold, max_planes, min_inliers=0, max_trials=1024, confidence=0.999, refine=2, seed=0, mask=None,
+                   axis=None, max_angle=None):
+    """Up to max_planes planes (3-D) or lines (2-D) peeled off a point cloud on the device, one after the other: plane p is
+    segment_plane with seed + p over the points no earlier plane took; the loop ends at the first plane with fewer than
+    min_inliers inliers, which is not recorded.  -> (labels, models): labels (n,) int32 where `positions` lives, the plane that
+    took each point or -1, and the list of segment_plane's model dicts (include/fi_hip.h fi_planes_segment)."""
+    p, mk, n, ndim, mem, keep = _plane_cloud(positions, mask)
+    opt = _plane_options(ndim, threshold, max_trials, confidence, refine, seed, axis, max_angle)
+    rows = (_capi.FiPlaneModel * max(int(max_planes), 1))()
+    found = C.c_int(0)
+    labels, ptr = _cloud_out(keep[0].device if mem == FI_DEVICE else None, (n,), np.int32)
+    check(_capi.lib().fi_planes_segment(ndim, n, p if n else None, mk if n else None, C.byref(opt), int(max_planes), int(min_inliers),
+                                        ptr, rows, C.byref(found), mem))
+    return labels, [_plane_dict(rows[i], ndim) for i in range(found.value)]
+
+
 def clean_points(positions, normals=None, values=None, cell=None, k=None, std_ratio=2.0, radius=None, min_neighbours=2,
-                 max_distance=math.inf, cluster_eps=None, cluster_min_points=1, largest=None, min_cluster=0):
+                 max_distance=math.inf, cluster_eps=None, cluster_min_points=1, largest=None, min_cluster=0, remove_planes=None):
     """A scan made fit for estimate_normals / sdf_from_points on the device, in this order and each step only if asked for:
     thin_points(cell) (mean mode), PointIndex.radius_outliers(radius, min_neighbours), PointIndex.statistical_outliers(k,
     std_ratio, max_distance).  Each filter builds its PointIndex over what the step before left.  numpy arrays, or torch
@@ -1243,7 +1320,10 @@ def clean_points(positions, normals=None, values=None, cell=None, k=None, std_ra
     statistical stage's `stats`.  With cluster_eps a last step runs after the outlier rules, for the stray CLUMP that both of
     them keep: PointIndex.cluster(cluster_eps, cluster_min_points) over what is left, and only the points of the clusters
     that keep_clusters(rows, largest, min_cluster) chooses survive (noise points go); the report gains `cluster`, what the
-    step removed, and `clusters`, its stats."""
+    step removed, and `clusters`, its stats.  remove_planes, a dict of segment_planes' arguments (threshold and max_planes at
+    least), takes the floor or table a scan stands on out after the outlier rules and BEFORE the cluster step -- an object
+    touches what it stands on, so clustering alone cannot part them: the points segment_planes labels go, and the report
+    gains `planes`, what the step removed, and `plane_models`, the models."""
     as_array = lambda a: a if a is None or hasattr(a, "data_ptr") else np.ascontiguousarray(a, np.float32)  # noqa: E731
     pos, nrm, val = as_array(positions), as_array(normals), as_array(values)
     on_device = bool(getattr(pos, "is_cuda", False))
@@ -1267,6 +1347,12 @@ def clean_points(positions, normals=None, values=None, cell=None, k=None, std_ra
         keep, stats = PointIndex(pos).statistical_outliers(k, std_ratio, max_distance, device=on_device)
         report["statistical"] = _rows(pos) - stats["kept"]
         report["stats"] = stats
+        pos, nrm, val = select(keep)
+    if remove_planes is not None:
+        labels, models = segment_planes(pos, **remove_planes)
+        keep = labels < 0
+        report["planes"] = _rows(pos) - int(keep.sum())
+        report["plane_models"] = models
         pos, nrm, val = select(keep)
     if cluster_eps is not None:
         labels, stats = PointIndex(pos).cluster(cluster_eps, cluster_min_points, stats=True, device=on_device)

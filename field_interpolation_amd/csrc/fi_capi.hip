@@ -18,6 +18,7 @@
 #include "fi_register.h"
 #include "fi_cloud.h"
 #include "fi_cluster.h"
+#include "fi_plane.h"
 
 #include <memory>
 
@@ -1725,6 +1726,61 @@ int fi_cluster_measure(int ndim, long n, const float* positions, const int* labe
 	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
 	FI_REQUIRE(n < (1L << 31) && num_clusters < (1L << 31), FI_ERR_UNSUPPORTED, "%ld points, %ld clusters in one call", n, num_clusters);
 	fi::cluster_measure(ndim, n, positions, labels, core, num_clusters, rows, memory);
+	FI_API_END
+}
+
+
+// ---- the dominant hyperplanes of a point cloud (fi_plane.hip) -------------------------------------
+namespace {
+void check_plane(int ndim, long n, const float* positions, const fi_plane_options* opt, int memory)
+{
+	FI_REQUIRE(2 <= ndim && ndim <= FI_MAX_DIM, FI_ERR_INVALID, "ndim must be 2..%d (got %d)", FI_MAX_DIM, ndim);
+	FI_REQUIRE(n >= 0, FI_ERR_INVALID, "n = %ld", n);
+	FI_REQUIRE(n == 0 || positions != nullptr, FI_ERR_INVALID, "positions is null");
+	FI_REQUIRE(opt != nullptr, FI_ERR_INVALID, "opt is null");
+	FI_REQUIRE(opt->threshold >= 0.0f && !std::isinf(opt->threshold), FI_ERR_INVALID, "threshold must be finite and >= 0 (got %g)",
+	           static_cast<double>(opt->threshold));  // (NaN fails)
+	FI_REQUIRE(1 <= opt->max_trials && opt->max_trials <= (1L << 20), FI_ERR_INVALID, "max_trials must be 1..2^20 (got %ld)", opt->max_trials);
+	FI_REQUIRE(opt->confidence >= 0.0 && opt->confidence < 1.0, FI_ERR_INVALID, "confidence must be in [0, 1) (got %g)", opt->confidence);
+	FI_REQUIRE(0 <= opt->refine && opt->refine <= 16, FI_ERR_INVALID, "refine must be 0..16 (got %d)", opt->refine);
+	FI_REQUIRE(opt->min_cos >= 0.0f && opt->min_cos <= 1.0f, FI_ERR_INVALID, "min_cos must be in [0, 1] (got %g)",
+	           static_cast<double>(opt->min_cos));
+	if (opt->min_cos > 0.0f) {
+		bool finite = true, zero = true;
+		for (int d = 0; d < ndim; ++d) {
+			finite = finite && std::isfinite(opt->axis[d]);
+			zero   = zero && opt->axis[d] == 0.0f;
+		}
+		FI_REQUIRE(finite && !zero, FI_ERR_INVALID, "min_cos > 0 needs a finite axis that is not zero");
+	}
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+}
+}  // namespace
+
+int fi_plane_fit(int ndim, long n, const float* positions, const unsigned char* mask, const fi_plane_options* opt, fi_plane_model* model,
+                 unsigned char* inliers, int memory)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(model != nullptr, FI_ERR_INVALID, "model is null");
+	*model = fi_plane_model{};
+	check_plane(ndim, n, positions, opt, memory);
+	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld points in one call", n);
+	fi::plane_fit(ndim, n, positions, mask, *opt, model, inliers, memory);
+	FI_API_END
+}
+
+int fi_planes_segment(int ndim, long n, const float* positions, const unsigned char* mask, const fi_plane_options* opt, int max_planes,
+                      long min_inliers, int* labels, fi_plane_model* rows, int* num_planes, int memory)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(num_planes != nullptr, FI_ERR_INVALID, "num_planes is null");
+	*num_planes = 0;
+	check_plane(ndim, n, positions, opt, memory);
+	FI_REQUIRE(max_planes >= 1, FI_ERR_INVALID, "max_planes must be >= 1 (got %d)", max_planes);
+	FI_REQUIRE(min_inliers >= 0, FI_ERR_INVALID, "min_inliers must be >= 0 (got %ld)", min_inliers);
+	FI_REQUIRE(rows != nullptr && (n == 0 || labels != nullptr), FI_ERR_INVALID, "null labels or rows");
+	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld points in one call", n);
+	fi::planes_segment(ndim, n, positions, mask, *opt, max_planes, min_inliers, labels, rows, num_planes, memory);
 	FI_API_END
 }
 

@@ -23,6 +23,7 @@
 #include "fi_solver_internal.h"
 #include "fi_meshpts.h"
 #include "fi_prim.h"
+#include "fi_uniform.h"
 
 #include <algorithm>
 #include <cmath>
@@ -130,16 +131,7 @@ __global__ __launch_bounds__(kThreads) void k_mpts_q(int64_t np, double scale, c
 
 // ---- samples ----------------------------------------------------------------------------------------------------------
 
-__device__ inline double uniform(uint64_t seed, uint64_t counter)
-{
-	uint64_t z = seed + (counter + 1) * 0x9E3779B97F4A7C15ull;
-	z ^= z >> 30;
-	z *= 0xBF58476D1CE4E5B9ull;
-	z ^= z >> 27;
-	z *= 0x94D049BB133111EBull;
-	z ^= z >> 31;
-	return static_cast<double>(z >> 11) * 0x1.0p-53;
-}
+using counter::uniform;  // fi_uniform.h
 
 struct SampleArgs {
 	int64_t         n, np;

@@ -714,6 +714,71 @@ bool thin_points(int ndim, const std::vector<float>& positions, float cell, std:
 	return true;
 }
 
+namespace {
+static_assert(sizeof(PlaneModel) == sizeof(fi_plane_model), "PlaneModel mirrors fi_plane_model");
+
+bool plane_options(int ndim, size_t floats, float threshold, long max_trials, double confidence, int refine, unsigned long long seed,
+                   const std::vector<unsigned char>& mask, const std::vector<float>& axis, float min_cos, fi_plane_options* opt)
+{
+	if (ndim < 2 || ndim > 3 || floats % ndim != 0) { return false; }
+	if ((!mask.empty() && mask.size() != floats / ndim) || (!axis.empty() && axis.size() != static_cast<size_t>(ndim))) { return false; }
+	*opt            = fi_plane_options{};
+	opt->threshold  = threshold;
+	opt->max_trials = max_trials;
+	opt->confidence = confidence;
+	opt->refine     = refine;
+	opt->seed       = seed;
+	for (size_t d = 0; d < axis.size(); ++d) { opt->axis[d] = axis[d]; }
+	opt->min_cos = min_cos;
+	return true;
+}
+}  // namespace
+
+bool segment_plane(int ndim, const std::vector<float>& positions, float threshold, PlaneModel* model, std::vector<unsigned char>* inliers,
+                   long max_trials, double confidence, int refine, unsigned long long seed, const std::vector<unsigned char>& mask,
+                   const std::vector<float>& axis, float min_cos)
+{
+	fi_plane_options opt;
+	fi_plane_model   m;
+	if (!model || !plane_options(ndim, positions.size(), threshold, max_trials, confidence, refine, seed, mask, axis, min_cos, &opt)) {
+		std::fprintf(stderr, "field_interpolation: segment_plane: bad arguments\n");
+		return false;
+	}
+	const size_t n = positions.size() / ndim;
+	if (inliers) { inliers->resize(n); }
+	if (fi_plane_fit(ndim, static_cast<long>(n), positions.data(), mask.empty() ? nullptr : mask.data(), &opt, &m,
+	                 inliers && n ? inliers->data() : nullptr, FI_HOST) != FI_OK) {
+		std::fprintf(stderr, "field_interpolation: segment_plane: %s\n", fi_last_error());
+		return false;
+	}
+	std::memcpy(model, &m, sizeof(m));
+	return true;
+}
+
+bool segment_planes(int ndim, const std::vector<float>& positions, float threshold, int max_planes, std::vector<int>* labels,
+                    std::vector<PlaneModel>* models, long min_inliers, long max_trials, double confidence, int refine,
+                    unsigned long long seed, const std::vector<unsigned char>& mask, const std::vector<float>& axis, float min_cos)
+{
+	fi_plane_options opt;
+	if (!labels || !models || max_planes < 1 ||
+	    !plane_options(ndim, positions.size(), threshold, max_trials, confidence, refine, seed, mask, axis, min_cos, &opt)) {
+		std::fprintf(stderr, "field_interpolation: segment_planes: bad arguments\n");
+		return false;
+	}
+	const size_t n = positions.size() / ndim;
+	labels->resize(n);
+	std::vector<fi_plane_model> rows(static_cast<size_t>(max_planes));
+	int                         found = 0;
+	if (fi_planes_segment(ndim, static_cast<long>(n), positions.data(), mask.empty() ? nullptr : mask.data(), &opt, max_planes, min_inliers,
+	                      n ? labels->data() : nullptr, rows.data(), &found, FI_HOST) != FI_OK) {
+		std::fprintf(stderr, "field_interpolation: segment_planes: %s\n", fi_last_error());
+		return false;
+	}
+	models->resize(static_cast<size_t>(found));
+	if (found > 0) { std::memcpy(models->data(), rows.data(), sizeof(fi_plane_model) * found); }
+	return true;
+}
+
 bool GpuLatticeField::distance_field(std::vector<float>* distances, std::vector<long long>* indices, float max_distance) const
 {
 	if (!distances) {

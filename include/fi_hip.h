@@ -1072,8 +1072,8 @@ int fi_cloud_thin(int ndim, long n, const float* positions, const float* normals
  * points costs one thread 4096 additions.  FI_ERR_INVALID: ndim outside 1..3, n or num_clusters < 0, NULL positions or labels
  * with n > 0, NULL rows with num_clusters > 0, a bad memory kind, a label outside [-1, num_clusters).  n or num_clusters
  * >= 2^31: FI_ERR_UNSUPPORTED.
- * Not offered: lists of the neighbours within a radius, HDBSCAN, OPTICS, region growing by normals, RANSAC plane
- * segmentation, slab contexts, approximate search. */
+ * Not offered: lists of the neighbours within a radius, HDBSCAN, OPTICS, region growing by normals, slab contexts,
+ * approximate search. */
 typedef struct fi_cluster_stats {
 	long clusters, core, border, noise, non_finite;
 } fi_cluster_stats;
@@ -1087,6 +1087,72 @@ int fi_points_cluster(fi_points* points, float eps, int min_points, int* labels,
                       int memory);
 int fi_cluster_measure(int ndim, long n, const float* positions, const int* labels, const unsigned char* core, long num_clusters,
                        fi_cluster_row* rows, int memory);
+
+/* ---- the dominant hyperplanes of a point cloud: RANSAC with refits ------------------------------
+ * The contract (tests/plane_reference.py is its definition in numpy) is this project's own.  fi_plane_fit
+ * fits one hyperplane n . x + d = 0 (a plane in 3-D, a line in 2-D; ndim = 1: FI_ERR_INVALID) to positions float[n * ndim];
+ * fi_planes_segment peels several off, one after the other.  No search structure: positions, mask, inliers and labels lie
+ * in `memory`, the models on the HOST; the calls run on the current device.  Everything is fp64 computed from the fp32
+ * coordinates, one rounding per operation (no FMA contraction), over + - * / sqrt; there are no float atomics, and every
+ * output is defined bit for bit, whatever the launch shape and the timing.
+ *   - candidates: point i is one iff all its coordinates are finite and mask is NULL or mask[i] != 0; in ascending index
+ *     they form the list cand[0 .. m).  m < ndim: found = 0, trials = 0;
+ *   - hypothesis h = 0 .. max_trials - 1 draws D = ndim list positions j_k = min(floor(u(seed, h D + k) m), m - 1), u being
+ *     fi_mesh_sample's counter hash (splitmix64's finaliser of seed + (counter + 1) 0x9E3779B97F4A7C15, its top 53 bits times
+ *     2^-53).  With a, b, c the drawn points: 3-D n = (b - a) x (c - a), each component the difference of two products
+ *     (u_1 w_2 - u_2 w_1, u_2 w_0 - u_0 w_2, u_0 w_1 - u_1 w_0); 2-D t = b - a, n = (-t_1, t_0).  len = sqrt of the squares
+ *     summed over ascending axes; n = n / len; d = -(n_0 a_0 + n_1 a_1 (+ n_2 a_2)), summed over ascending axes.  The
+ *     hypothesis is invalid when two of its j_k are equal or when len is not finite and > 0; with an axis constraint
+ *     (min_cos > 0), t = the sum over ascending axes of n_a axis_a, also when t t >= (min_cos min_cos) (axis . axis) is false.
+ *     An invalid hypothesis scores -1;
+ *   - score: e_i = ((n_0 x_0 + n_1 x_1) + n_2 x_2) + d (2-D: (n_0 x_0 + n_1 x_1) + d); candidate i is an inlier iff
+ *     fabs(e_i) <= (double)threshold -- a point exactly at the threshold is in.  The score is the exact count of inliers among
+ *     the candidates; the best hypothesis has the highest score, ties go to the lowest h; no valid hypothesis: found = 0;
+ *   - batches and the stop: hypotheses are scored in batches of FI_PLANE_BATCH, the last may be partial.  After every batch,
+ *     with T the hypotheses scored so far and b > 0 the best score: w = b / m, p = w w (times w again in 3-D), q = 1 - p, and
+ *     r = q^T by binary exponentiation from the low bit (r = 1; base = q; while (e) { if (e & 1) r = r base; base = base base;
+ *     e >>= 1; }), all in fp64: stop when r <= 1 - confidence.  No logarithm: add, multiply and compare only.  confidence = 0
+ *     never stops early.  trials reports T;
+ *   - refits, `refine` times: the members are the current inliers in ascending index; c_a = tree_sum(x_a) / count;
+ *     A_ab = tree_sum((x_a - c_a)(x_b - c_b)) for a <= b, mirrored; tree_sum is fi_cluster_measure's (chunks of 256
+ *     consecutive members, s[t] += s[t + w], w = 128 .. 1, the tail padded with 0.0; the chunk sums added ascending from 0.0);
+ *     fi_estimate_normals' cyclic Jacobi iteration (6 sweeps); the new normal is the column with the smallest diagonal entry,
+ *     the lowest column on a tie, NOT renormalised; d = -(n_0 c_0 + ...).  The inliers are then counted again over all
+ *     candidates.  A refit is skipped, and the refits end, when count < D or the new normal is not finite.  A refit is not
+ *     conditional on the count going up.  refits reports how many ran;
+ *   - result: the final normal takes fi_estimate_normals' canonical sign (the component of largest magnitude, the first such
+ *     axis, is positive), offset is negated with it; rms = sqrt(tree_sum(e^2) / inliers) over the final inliers, 0 with none;
+ *     inliers (unsigned char[n] or NULL) is one byte per input point from the final model.  Unused axes of normal are 0;
+ *     found = 0 leaves every figure but candidates and trials 0.
+ * fi_planes_segment: plane p is fi_plane_fit with seed + p (wrapping) over the candidates no earlier plane took; the loop
+ * ends at max_planes, at found = 0, or at the first plane with fewer than min_inliers inliers, which is not recorded.
+ * labels[i] (int[n]) is the plane that took point i, or -1; rows (host, max_planes) receive the recorded models and
+ * *num_planes their number.  n = 0: found = 0, no planes, FI_OK.
+ * FI_ERR_INVALID: ndim outside 2..3; n < 0; a negative, NaN or infinite threshold; max_trials outside 1 .. 2^20; confidence
+ * outside [0, 1); refine outside 0 .. 16; min_cos outside [0, 1]; min_cos > 0 with a zero or non-finite axis; a bad memory
+ * kind; NULL required pointers (opt, model / labels, rows, num_planes; positions with n > 0); max_planes < 1;
+ * min_inliers < 0.  n >= 2^31: FI_ERR_UNSUPPORTED.
+ * Not offered: spheres, cylinders and other models; MSAC / MLESAC scores; per-point normals in the inlier test; region
+ * growing by normals; slab contexts. */
+#define FI_PLANE_BATCH 1024
+typedef struct fi_plane_options {
+	float              threshold;
+	long               max_trials;
+	double             confidence;
+	int                refine;
+	unsigned long long seed;
+	float              axis[3];
+	float              min_cos;
+} fi_plane_options;
+typedef struct fi_plane_model {
+	int    found, refits;
+	long   inliers, candidates, trials;
+	double normal[3], offset, rms;
+} fi_plane_model;
+int fi_plane_fit(int ndim, long n, const float* positions, const unsigned char* mask, const fi_plane_options* opt,
+                 fi_plane_model* model, unsigned char* inliers, int memory);
+int fi_planes_segment(int ndim, long n, const float* positions, const unsigned char* mask, const fi_plane_options* opt,
+                      int max_planes, long min_inliers, int* labels, fi_plane_model* rows, int* num_planes, int memory);
 
 /* ---- exact distances to a surface; redistancing ------------------------------------------------
  * The contract ("Distances to a surface") is this project's own.  All arithmetic is fp32, one rounding per

@@ -72,6 +72,14 @@ struct ClusterStats
 	long clusters, core, border, noise, non_finite;
 };
 
+// A hyperplane found by segment_plane / segment_planes (include/fi_hip.h fi_plane_model), field for field.
+struct PlaneModel
+{
+	int    found, refits;
+	long   inliers, candidates, trials;
+	double normal[3], offset, rms;
+};
+
 class GpuLatticeField
 {
 public:
@@ -286,6 +294,25 @@ bool thin_points(int ndim, const std::vector<float>& positions, float cell, std:
                  const std::vector<float>& values = std::vector<float>(), std::vector<float>* out_values = nullptr,
                  const std::vector<float>& origin = std::vector<float>(), bool first = false, std::vector<int>* out_counts = nullptr,
                  std::vector<long long>* out_indices = nullptr, std::vector<int>* cell_map = nullptr);
+
+// The dominant plane (ndim = 3) or line (ndim = 2) of a point cloud on the device, no lattice needed: RANSAC with an exact
+// inlier count (a point within `threshold` of the plane, inclusive, is an inlier), then `refine` least-squares refits.
+// positions: ndim floats per point.  At most max_trials hypotheses, fewer once the best would have been drawn with probability
+// `confidence` (0: never stop early).  mask (one byte per point, may be empty): the points that take part.  axis (ndim
+// floats, may be empty) and min_cos: only planes with |normal . axis| >= min_cos |axis|.  inliers (optional): one byte per
+// point.  Every figure is defined bit for bit: the contract is include/fi_hip.h fi_plane_fit.  false: the library refused
+// the call.
+bool segment_plane(int ndim, const std::vector<float>& positions, float threshold, PlaneModel* model,
+                   std::vector<unsigned char>* inliers = nullptr, long max_trials = 1024, double confidence = 0.999, int refine = 2,
+                   unsigned long long seed = 0, const std::vector<unsigned char>& mask = std::vector<unsigned char>(),
+                   const std::vector<float>& axis = std::vector<float>(), float min_cos = 0.0f);
+// Up to max_planes planes peeled off one after the other: plane p is segment_plane with seed + p over the points no earlier
+// plane took; the first plane with fewer than min_inliers inliers ends the loop and is not recorded.  labels[i]: the plane
+// that took point i, or -1.  The contract is include/fi_hip.h fi_planes_segment.
+bool segment_planes(int ndim, const std::vector<float>& positions, float threshold, int max_planes, std::vector<int>* labels,
+                    std::vector<PlaneModel>* models, long min_inliers = 0, long max_trials = 1024, double confidence = 0.999,
+                    int refine = 2, unsigned long long seed = 0, const std::vector<unsigned char>& mask = std::vector<unsigned char>(),
+                    const std::vector<float>& axis = std::vector<float>(), float min_cos = 0.0f);
 
 // The stateless solver calls of sparse_linear.hpp keep device contexts between calls, keyed by shape and precision (at
 // most six, systems of up to 2^20 unknowns only; larger systems get a context per call): the per-frame caller's latency
