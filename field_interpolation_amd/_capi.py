@@ -32,6 +32,7 @@ SYMBOLS = [
     "fi_radius_count", "fi_points_radius_count", "fi_neighbour_distances", "fi_points_neighbour_distances",
     "fi_outliers_statistical", "fi_points_outliers_statistical", "fi_outliers_radius", "fi_points_outliers_radius", "fi_cloud_thin",
     "fi_cluster", "fi_points_cluster", "fi_cluster_measure", "fi_plane_fit", "fi_planes_segment",
+    "fi_points_describe", "fi_feature_match", "fi_align_correspondences",
     "fi_surface_create", "fi_surface_from_mesh", "fi_surface_distance", "fi_surface_distance_field", "fi_surface_destroy",
     "fi_surface_raycast", "fi_surface_count_hits", "fi_surface_contains", "fi_surface_signed_distance",
     "fi_surface_signed_distance_field",
@@ -131,6 +132,16 @@ class FiPlaneOptions(C.Structure):
 class FiPlaneModel(C.Structure):
     _fields_ = [("found", C.c_int), ("refits", C.c_int), ("inliers", C.c_long), ("candidates", C.c_long), ("trials", C.c_long),
                 ("normal", C.c_double * 3), ("offset", C.c_double), ("rms", C.c_double)]
+
+
+class FiAlignOptions(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("similarity", C.c_float), ("max_trials", C.c_long), ("confidence", C.c_double),
+                ("seed", C.c_ulonglong)]
+
+
+class FiAlignment(C.Structure):
+    _fields_ = [("found", C.c_int), ("pairs", C.c_long), ("live", C.c_long), ("trials", C.c_long), ("valid", C.c_long),
+                ("inliers", C.c_long), ("transform", C.c_double * 16), ("rms", C.c_double)]
 
 
 class FiError(RuntimeError):
@@ -249,6 +260,10 @@ def lib():
     L.fi_plane_fit.argtypes = [C.c_int, C.c_long, fp, vp, C.POINTER(FiPlaneOptions), C.POINTER(FiPlaneModel), vp, C.c_int]
     L.fi_planes_segment.argtypes = [C.c_int, C.c_long, fp, vp, C.POINTER(FiPlaneOptions), C.c_int, C.c_long, vp,
                                     C.POINTER(FiPlaneModel), ip, C.c_int]
+    L.fi_points_describe.argtypes = [vp, fp, C.c_int, C.c_float, fp, vp, C.c_int]
+    L.fi_feature_match.argtypes = [C.c_int, C.c_long, fp, vp, C.c_long, fp, vp, vp, fp, C.c_int]
+    L.fi_align_correspondences.argtypes = [C.c_long, fp, C.c_long, fp, C.c_long, vp, vp, C.POINTER(FiAlignOptions),
+                                           C.POINTER(FiAlignment), vp, C.c_int]
     L.fi_surface_create.argtypes = [C.POINTER(vp), C.c_int, C.c_long, fp, C.c_long, vp, C.c_int]
     L.fi_surface_from_mesh.argtypes = [C.POINTER(vp), vp]
     L.fi_surface_distance.argtypes = [vp, C.c_long, fp, C.c_float, fp, vp, fp, C.c_int]

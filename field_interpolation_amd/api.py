@@ -739,6 +739,31 @@ class PointIndex:
             return _capi.lib().fi_points_neighbour_distances(self._h, kk, md, m, kt, c, mem)
         return _neighbour_distances(call, self.num_points, k, max_distance, device)
 
+    def describe(self, normals, k=32, max_distance=math.inf, device=False):
+        """(features (num_points, 33) float32, valid (num_points,) bool): what every point's neighbourhood looks like as a
+        fast point feature histogram (Rusu) over its k nearest points within max_distance and the normals (num_points, 3)
+        -- three blocks of 11 bins that each sum to 100 and do not change when the cloud is turned or shifted, which is what
+        match_features compares.  A point that is non-finite, has a zero or non-finite normal or no usable neighbour gets
+        zeros and valid = False.  3-D sets only; 1 <= k <= 32.  numpy arrays, or torch tensors on the GPU when `normals` is a
+        device tensor or with device=True (include/fi_hip.h fi_points_describe)."""
+        k = _check_k(k)
+        n = self.num_points
+        nrm, nmem, nkeep = _buf(normals)
+        count = nkeep.numel() if hasattr(nkeep, "numel") else nkeep.size
+        if count != n * 3:
+            raise ValueError("normals: %d values for %d points of 3 dimensions" % (count, n))
+        on_device = bool(device) or nmem == FI_DEVICE
+        if on_device and nmem != FI_DEVICE:
+            import torch
+            nkeep = torch.as_tensor(nkeep).to("cuda")
+            nrm = C.c_void_p(nkeep.data_ptr())
+        dev = (nkeep.device if on_device else None)
+        feat, pf = _cloud_out(dev, (n, 33), np.float32)
+        valid, pv = _cloud_out(dev, (n,), np.uint8)
+        if n:
+            check(_capi.lib().fi_points_describe(self._h, nrm, k, float(max_distance), pf, pv, FI_DEVICE if on_device else FI_HOST))
+        return feat, _as_mask(valid)
+
     def statistical_outliers(self, k=8, std_ratio=2.0, max_distance=math.inf, device=False):
         """The statistical outlier rule of PCL and Open3D: a point is kept when its mean distance to its k nearest other
         points (neighbour_distances) is at most mean + std_ratio * standard deviation of that figure over the cloud, the two
@@ -1308,6 +1333,115 @@ def segment_planes(positions, threshold, max_planes, min_inliers=0, max_trials=1
     check(_capi.lib().fi_planes_segment(ndim, n, p if n else None, mk if n else None, C.byref(opt), int(max_planes), int(min_inliers),
                                         ptr, rows, C.byref(found), mem))
     return labels, [_plane_dict(rows[i], ndim) for i in range(found.value)]
+
+
+def _match(a, b, valid_a, valid_b, distances):
+    pa, amem, akeep = _buf(a)
+    pb, bmem, bkeep = _buf(b)
+    if len(akeep.shape) != 2 or len(bkeep.shape) != 2 or akeep.shape[1] != bkeep.shape[1]:
+        raise ValueError("a is (n_a, dim) and b is (n_b, dim), not %r and %r" % (tuple(akeep.shape), tuple(bkeep.shape)))
+    na, nb, dim = int(akeep.shape[0]), int(bkeep.shape[0]), int(akeep.shape[1])
+    va, vamem, vakeep = _flags(valid_a)
+    vb, vbmem, vbkeep = _flags(valid_b)
+    for mask, n in ((vakeep, na), (vbkeep, nb)):
+        if mask is not None and tuple(mask.shape) != (n,):
+            raise ValueError("a mask is (%d,), one per row" % n)
+    mem = _same_memory(amem, bmem, vamem, vbmem)
+    dev = akeep.device if mem == FI_DEVICE else None
+    idx, pi = _cloud_out(dev, (na,), np.int64)
+    dist, pd = _cloud_out(dev, (na,), np.float32) if distances else (None, None)
+    check(_capi.lib().fi_feature_match(dim, na, pa if na else None, va if na else None, nb, pb if nb else None, vb if nb else None,
+                                       pi, pd, mem))
+    return idx, dist
+
+
+def match_features(a, b, valid_a=None, valid_b=None, mutual=False, distances=False):
+    """For every row of `a` (n_a, dim) the nearest row of `b` (n_b, dim) on the device, 1 <= dim <= 64: the squared distance is
+    summed in fp32 over ascending columns, equal distances go to the smallest index, and only rows that are finite and not
+    masked out (valid_a, valid_b: one flag a row) take part.  -> indices (n_a,) int64, -1 for a row without a match, and with
+    distances=True also the distances (n_a,) float32, +inf there.  mutual=True runs the match both ways and keeps i -> j only
+    where j's own match is i.  numpy arrays, or torch CUDA tensors that stay on the device, all in the same memory
+    (include/fi_hip.h fi_feature_match)."""
+    idx, dist = _match(a, b, valid_a, valid_b, distances)
+    if mutual:
+        back, _ = _match(b, a, valid_b, valid_a, False)
+        if hasattr(idx, "data_ptr"):
+            import torch
+            here = torch.arange(idx.shape[0], device=idx.device)
+            lost = (idx >= 0) & ((back[idx.clamp(min=0)] != here) if back.shape[0] else torch.zeros_like(idx, dtype=torch.bool))
+        else:
+            lost = (idx >= 0) & ((back[np.maximum(idx, 0)] != np.arange(len(idx))) if len(back) else np.zeros(len(idx), bool))
+        idx[lost] = -1
+        if dist is not None:
+            dist[lost] = math.inf
+    return (idx, dist) if distances else idx
+
+
+def _alignment_dict(r):
+    return {"found": bool(r.found), "transform": np.array(r.transform[:], np.float64).reshape(4, 4), "inliers": int(r.inliers),
+            "pairs": int(r.pairs), "live": int(r.live), "trials": int(r.trials), "valid": int(r.valid), "rms": float(r.rms)}
+
+
+def align_correspondences(source, target, src_index, tgt_index, threshold, similarity=0.9, max_trials=100_000, confidence=0.999,
+                          seed=0):
+    """The rotation and shift that carries the most of the matched pairs (source[src_index[c]], target[tgt_index[c]]) to within
+    `threshold` of each other, by RANSAC on the device: the coarse alignment from any pose.  source (n_s, 3), target (n_t, 3),
+    the indices (m,) int64 -- numpy arrays, or torch CUDA tensors that stay on the device, all in the same memory.  A
+    hypothesis is three pairs; it is refused where an edge of its source triangle and the same edge of its target triangle
+    differ by more than the factor `similarity` (0: no such test), which spares scoring most wrong ones.  At most max_trials
+    hypotheses, fewer once the best would have been drawn with probability `confidence` (0: never stop early).  A pair with
+    an index out of range (-1, say, for no match) or a non-finite point takes no part.  -> (result, inliers): a dict with
+    `found`, `transform` (4, 4) float64 mapping source to target coordinates -- register_points' `initial` --, `inliers`,
+    `pairs`, `live`, `trials`, `valid` (the hypotheses that were scored) and `rms`, and a boolean mask (m,) where the inputs
+    live.  Every figure is defined bit for bit (include/fi_hip.h fi_align_correspondences)."""
+    ps, smem, skeep = _buf(source)
+    pt, tmem, tkeep = _buf(target)
+    for what, keep in (("source", skeep), ("target", tkeep)):
+        if len(keep.shape) != 2 or keep.shape[1] != 3:
+            raise ValueError("%s is (n, 3), not %r" % (what, tuple(keep.shape)))
+    pi, imem, ikeep = _buf(src_index, np.int64)
+    pj, jmem, jkeep = _buf(tgt_index, np.int64)
+    if len(ikeep.shape) != 1 or tuple(ikeep.shape) != tuple(jkeep.shape):
+        raise ValueError("src_index and tgt_index are (m,) each, not %r and %r" % (tuple(ikeep.shape), tuple(jkeep.shape)))
+    ns, nt, m = int(skeep.shape[0]), int(tkeep.shape[0]), int(ikeep.shape[0])
+    mem = _same_memory(smem, tmem, imem, jmem)
+    opt = _capi.FiAlignOptions(float(threshold), float(similarity), int(max_trials), float(confidence), int(seed) & (2 ** 64 - 1))
+    res = _capi.FiAlignment()
+    out, ptr = _cloud_out(skeep.device if mem == FI_DEVICE else None, (m,), np.uint8)
+    check(_capi.lib().fi_align_correspondences(ns, ps if ns else None, nt, pt if nt else None, m, pi if m else None,
+                                               pj if m else None, C.byref(opt), C.byref(res), ptr, mem))
+    return _alignment_dict(res), _as_mask(out)
+
+
+_ALIGN_KEYWORDS = ("similarity", "max_trials", "confidence", "seed")
+
+
+def register_global(source, source_normals, target, target_normals, threshold, k=32, mutual=False, refine=True, **keywords):
+    """`source` (n, 3) laid over `target` (m, 3) from any pose, on the device: both clouds described (PointIndex.describe over k
+    neighbours and the normals), every source descriptor matched to its nearest target descriptor (match_features; mutual as
+    there), the motion most matches agree on to within `threshold` (align_correspondences), and with refine=True that motion
+    handed as `initial` to register_points(source, target, target_normals=..., max_distance=3 * threshold).  keywords:
+    align_correspondences' similarity, max_trials, confidence and seed; any other goes to register_points.  numpy arrays, or
+    torch CUDA tensors that stay on the device.  -> (alignment, registration): align_correspondences' dict with `matches`
+    (n,), the target point of every source point or -1, and `mask` (n,), the matches the motion keeps; and register_points'
+    dict, or None without refine."""
+    align_kw = {key: keywords.pop(key) for key in _ALIGN_KEYWORDS if key in keywords}
+    on_device = bool(getattr(source, "is_cuda", False))
+    fs, vs = PointIndex(source).describe(source_normals, k, device=on_device)
+    target_index = PointIndex(target)
+    ft, vt = target_index.describe(target_normals, k, device=on_device)
+    matches = match_features(fs, ft, vs, vt, mutual=mutual)
+    if on_device:
+        import torch
+        here = torch.arange(matches.shape[0], device=matches.device)
+    else:
+        here = np.arange(len(matches), dtype=np.int64)
+    alignment, mask = align_correspondences(source, target, here, matches, threshold, **align_kw)
+    alignment["matches"], alignment["mask"] = matches, mask
+    if not refine:
+        return alignment, None
+    keywords.setdefault("max_distance", 3.0 * float(threshold))
+    return alignment, register_points(source, target_index, target_normals=target_normals, initial=alignment["transform"], **keywords)
 
 
 def clean_points(positions, normals=None, values=None, cell=None, k=None, std_ratio=2.0, radius=None, min_neighbours=2,

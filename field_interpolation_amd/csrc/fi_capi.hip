@@ -19,6 +19,8 @@
 #include "fi_cloud.h"
 #include "fi_cluster.h"
 #include "fi_plane.h"
+#include "fi_align.h"
+#include "fi_feature.h"
 
 #include <memory>
 
@@ -1781,6 +1783,61 @@ int fi_planes_segment(int ndim, long n, const float* positions, const unsigned c
 	FI_REQUIRE(rows != nullptr && (n == 0 || labels != nullptr), FI_ERR_INVALID, "null labels or rows");
 	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld points in one call", n);
 	fi::planes_segment(ndim, n, positions, mask, *opt, max_planes, min_inliers, labels, rows, num_planes, memory);
+	FI_API_END
+}
+
+
+// ---- the rigid motion most matched pairs agree on (fi_align.hip) ----------------------------------
+int fi_align_correspondences(long n_s, const float* source, long n_t, const float* target, long m, const long long* src_index,
+                             const long long* tgt_index, const fi_align_options* opt, fi_alignment* out, unsigned char* inliers, int memory)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(out != nullptr, FI_ERR_INVALID, "out is null");
+	*out = fi_alignment{};
+	for (int d = 0; d < 4; ++d) { out->transform[5 * d] = 1.0; }
+	FI_REQUIRE(n_s >= 0 && n_t >= 0 && m >= 0, FI_ERR_INVALID, "n_s = %ld, n_t = %ld, m = %ld", n_s, n_t, m);
+	FI_REQUIRE(opt != nullptr, FI_ERR_INVALID, "opt is null");
+	FI_REQUIRE(opt->threshold >= 0.0f, FI_ERR_INVALID, "threshold must be >= 0 (got %g)", static_cast<double>(opt->threshold));  // (NaN fails)
+	FI_REQUIRE(opt->similarity >= 0.0f && opt->similarity <= 1.0f, FI_ERR_INVALID, "similarity must be in [0, 1] (got %g)",
+	           static_cast<double>(opt->similarity));
+	FI_REQUIRE(opt->confidence >= 0.0 && opt->confidence < 1.0, FI_ERR_INVALID, "confidence must be in [0, 1) (got %g)", opt->confidence);
+	FI_REQUIRE(1 <= opt->max_trials && opt->max_trials <= 0x7FFFFFFFL, FI_ERR_INVALID, "max_trials must be 1..2^31 - 1 (got %ld)",
+	           opt->max_trials);
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	FI_REQUIRE(m == 0 || (src_index != nullptr && tgt_index != nullptr), FI_ERR_INVALID, "null indices");
+	FI_REQUIRE(m == 0 || ((n_s == 0 || source != nullptr) && (n_t == 0 || target != nullptr)), FI_ERR_INVALID, "null points");
+	FI_REQUIRE(m < (1L << 31) && n_s < (1L << 31) && n_t < (1L << 31), FI_ERR_UNSUPPORTED, "%ld pairs over %ld and %ld points in one call", m,
+	           n_s, n_t);
+	fi::align_correspondences(n_s, source, n_t, target, m, src_index, tgt_index, *opt, out, inliers, memory);
+	FI_API_END
+}
+
+
+// ---- descriptors of a point's neighbourhood and their matching (fi_feature.hip) --------------------
+int fi_points_describe(fi_points* h, const float* normals, int k, float max_distance, float* features, unsigned char* valid, int memory)
+{
+	FI_API_BEGIN
+	check_points(h);
+	check_k(k);
+	FI_REQUIRE(normals != nullptr && features != nullptr, FI_ERR_INVALID, "null normals or features");
+	FI_REQUIRE(max_distance >= 0.0f, FI_ERR_INVALID, "max_distance must be >= 0 (got %g)", static_cast<double>(max_distance));  // (NaN fails)
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	FI_REQUIRE(h->t.D == 3, FI_ERR_UNSUPPORTED, "descriptors need 3 dimensions (the set has %d)", h->t.D);
+	fi::points_describe(h->t, normals, k, max_distance, features, valid, memory, nullptr);
+	FI_API_END
+}
+
+int fi_feature_match(int dim, long n_a, const float* a, const unsigned char* valid_a, long n_b, const float* b, const unsigned char* valid_b,
+                     long long* indices, float* distances, int memory)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(1 <= dim && dim <= FI_FEATURE_MAX_DIM, FI_ERR_INVALID, "dim must be 1..%d (got %d)", FI_FEATURE_MAX_DIM, dim);
+	FI_REQUIRE(n_a >= 0 && n_b >= 0, FI_ERR_INVALID, "n_a = %ld, n_b = %ld", n_a, n_b);
+	FI_REQUIRE(n_a == 0 || (a != nullptr && indices != nullptr), FI_ERR_INVALID, "null a or indices");
+	FI_REQUIRE(n_a == 0 || n_b == 0 || b != nullptr, FI_ERR_INVALID, "b is null");
+	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	FI_REQUIRE(n_a < (1L << 31) && n_b < (1L << 31), FI_ERR_UNSUPPORTED, "%ld rows against %ld in one call", n_a, n_b);
+	fi::feature_match(dim, n_a, a, valid_a, n_b, b, valid_b, indices, distances, memory);
 	FI_API_END
 }
 

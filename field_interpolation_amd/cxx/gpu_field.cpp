@@ -779,6 +779,79 @@ bool segment_planes(int ndim, const std::vector<float>& positions, float thresho
 	return true;
 }
 
+static_assert(sizeof(Alignment) == sizeof(fi_alignment), "Alignment mirrors fi_alignment");
+
+bool describe_points(const std::vector<float>& positions, const std::vector<float>& normals, std::vector<float>* features,
+                     std::vector<unsigned char>* valid, int k, float max_distance)
+{
+	if (!features || positions.size() % 3 != 0 || normals.size() != positions.size()) {
+		std::fprintf(stderr, "field_interpolation: describe_points: bad arguments\n");
+		return false;
+	}
+	const size_t n = positions.size() / 3;
+	features->assign(n * FI_FEATURE_WIDTH, 0.0f);
+	if (valid) { valid->assign(n, 0); }
+	fi_points* set = nullptr;
+	if (fi_points_create(&set, 3, static_cast<long>(n), n ? positions.data() : nullptr, FI_HOST) != FI_OK) {
+		std::fprintf(stderr, "field_interpolation: describe_points: %s\n", fi_last_error());
+		return false;
+	}
+	// (an empty set has nothing to describe, and no buffers to hand over)
+	const int code =
+	    n == 0 ? FI_OK : fi_points_describe(set, normals.data(), k, max_distance, features->data(), valid ? valid->data() : nullptr, FI_HOST);
+	if (code != FI_OK) { std::fprintf(stderr, "field_interpolation: describe_points: %s\n", fi_last_error()); }
+	fi_points_destroy(set);
+	return code == FI_OK;
+}
+
+bool match_features(int dim, const std::vector<float>& a, const std::vector<float>& b, std::vector<long long>* indices,
+                    std::vector<float>* distances, const std::vector<unsigned char>& valid_a, const std::vector<unsigned char>& valid_b)
+{
+	if (!indices || dim < 1 || a.size() % dim != 0 || b.size() % dim != 0 || (!valid_a.empty() && valid_a.size() != a.size() / dim) ||
+	    (!valid_b.empty() && valid_b.size() != b.size() / dim)) {
+		std::fprintf(stderr, "field_interpolation: match_features: bad arguments\n");
+		return false;
+	}
+	const size_t na = a.size() / dim, nb = b.size() / dim;
+	indices->resize(na);
+	if (distances) { distances->resize(na); }
+	if (fi_feature_match(dim, static_cast<long>(na), na ? a.data() : nullptr, valid_a.empty() ? nullptr : valid_a.data(), static_cast<long>(nb),
+	                     nb ? b.data() : nullptr, valid_b.empty() ? nullptr : valid_b.data(), na ? indices->data() : nullptr,
+	                     distances && na ? distances->data() : nullptr, FI_HOST) != FI_OK) {
+		std::fprintf(stderr, "field_interpolation: match_features: %s\n", fi_last_error());
+		return false;
+	}
+	return true;
+}
+
+bool align_correspondences(const std::vector<float>& source, const std::vector<float>& target, const std::vector<long long>& src_index,
+                           const std::vector<long long>& tgt_index, float threshold, Alignment* out, std::vector<unsigned char>* inliers,
+                           float similarity, long max_trials, double confidence, unsigned long long seed)
+{
+	if (!out || source.size() % 3 != 0 || target.size() % 3 != 0 || src_index.size() != tgt_index.size()) {
+		std::fprintf(stderr, "field_interpolation: align_correspondences: bad arguments\n");
+		return false;
+	}
+	fi_align_options opt{};
+	opt.threshold  = threshold;
+	opt.similarity = similarity;
+	opt.max_trials = max_trials;
+	opt.confidence = confidence;
+	opt.seed       = seed;
+	fi_alignment r{};
+	const size_t m = src_index.size();
+	if (inliers) { inliers->resize(m); }
+	if (fi_align_correspondences(static_cast<long>(source.size() / 3), source.empty() ? nullptr : source.data(),
+	                             static_cast<long>(target.size() / 3), target.empty() ? nullptr : target.data(), static_cast<long>(m),
+	                             m ? src_index.data() : nullptr, m ? tgt_index.data() : nullptr, &opt, &r,
+	                             inliers && m ? inliers->data() : nullptr, FI_HOST) != FI_OK) {
+		std::fprintf(stderr, "field_interpolation: align_correspondences: %s\n", fi_last_error());
+		return false;
+	}
+	std::memcpy(out, &r, sizeof(r));
+	return true;
+}
+
 bool GpuLatticeField::distance_field(std::vector<float>* distances, std::vector<long long>* indices, float max_distance) const
 {
 	if (!distances) {

@@ -1154,6 +1154,105 @@ int fi_plane_fit(int ndim, long n, const float* positions, const unsigned char* 
 int fi_planes_segment(int ndim, long n, const float* positions, const unsigned char* mask, const fi_plane_options* opt,
                       int max_planes, long min_inliers, int* labels, fi_plane_model* rows, int* num_planes, int memory);
 
+/* ---- descriptors of a point's neighbourhood that survive a rigid motion, and their matching -----
+ * The contract (tests/feature_reference.py is its definition in numpy) is this project's own: Rusu's fast
+ * point feature histograms with a pseudo-angle in place of the third feature's angle, so that no trigonometry is needed.
+ * fi_points_describe gives every point of a 3-D set (any other ndim: FI_ERR_UNSUPPORTED) FI_FEATURE_WIDTH = 33 floats from
+ * its k nearest points and the normals float[n * 3]; features float[n * 33] and valid unsigned char[n] (or NULL) lie in
+ * `memory` like the normals.  Everything is fp64 computed from the fp32 positions and normals, one rounding per operation (no
+ * FMA contraction), over + - * / sqrt, fabs and compares; counts are integers; every output is defined bit for bit.
+ *   - live: point i is live iff its position is finite and its normal is finite with a length -- the square root of the
+ *     squares summed over ascending axes in double, (x_0^2 + x_1^2) + x_2^2 -- that is finite and > 0.  Its unit normal is
+ *     n = (double)normal / length per component.  A point that is not live gets 33 zeros and valid = 0;
+ *   - neighbours: the neighbours of a live point i are its own fi_points_knn result (k, max_distance) over the whole set, in
+ *     result order, without the entries j = -1, j = i, j not live and j with w = 0 (below);
+ *   - pair (i, j): dp = p_j - p_i; w = (dp_0^2 + dp_1^2) + dp_2^2, L = sqrt(w), e = dp / L; a_i = n_i . e and a_j = n_j . e,
+ *     every dot product (u_0 v_0 + u_1 v_1) + u_2 v_2.  If fabs(a_i) < fabs(a_j): (n_s, n_t, e, f_2) = (n_j, n_i, -e, -a_j),
+ *     else (n_i, n_j, e, a_i) -- PCL's choice of the source as the point whose normal lies closer to the line, without acos.
+ *     v = e x n_s, each component the difference of two products (e_1 n_2 - e_2 n_1, e_2 n_0 - e_0 n_2, e_0 n_1 - e_1 n_0);
+ *     l = sqrt of its squares summed as above; the pair is skipped unless l is finite and > 0; v = v / l; u = n_s x v;
+ *     f_1 = v . n_t, x = n_s . n_t, y = u . n_t; s = fabs(x) + fabs(y), r = s > 0 ? y / s : 0; the pseudo-angle
+ *     f_3 = x >= 0 ? r : (y >= 0 ? 2 - r : -2 - r), in [-2, 2], monotone in atan2(y, x).  A pair with a non-finite f is skipped;
+ *   - bins, 11 per feature: t_1 = (f_1 + 1) 5.5, t_2 = (f_2 + 1) 5.5, t_3 = (f_3 + 2) 2.75; b = t < 0 ? 0 : t >= 11 ? 10 :
+ *     (int)t; c_i[b_1], c_i[11 + b_2], c_i[22 + b_3] and the pair count m_i each gain 1;
+ *   - SPFH: S_i[b] = (100.0 c_i[b]) / m_i for a live i with m_i > 0; any other point has no descriptor: zeros, valid = 0;
+ *   - FPFH: over the same neighbours in the same order, only those with m_j > 0 (q_i of them): A[b] = the sum from 0.0 of
+ *     S_j[b] / w_ij; F[b] = S_i[b] + (q_i > 0 ? A[b] / q_i : 0); per block of 11: z = the sum from 0.0 over its ascending bins,
+ *     F[b] = (100.0 F[b]) / z where z > 0; features[i 33 + b] = (float)F[b], valid[i] = 1.
+ * FI_ERR_INVALID: a NULL set, normals or features; k outside 1..32; a negative or NaN max_distance; a bad memory kind.  An
+ * empty set succeeds.
+ * fi_feature_match: for every row i of a (float[n_a * dim], 1 <= dim <= FI_FEATURE_MAX_DIM), over the rows j of b
+ * (float[n_b * dim]) that are valid (valid_b NULL or valid_b[j] != 0) and finite: s(i, j) = the fp32 sum from 0.0f of
+ * (a_ic - b_jc)^2 over ascending c, one rounding per operation.  indices[i] (long long[n_a]) is the smallest j with the
+ * minimal s, distances[i] (float[n_a] or NULL) = sqrtf(s); an invalid or non-finite row i, or no admissible j: -1 and +inf.
+ * All buffers in `memory`, on the current device.  FI_ERR_INVALID: dim outside 1..64; a negative count; NULL a or indices
+ * with n_a > 0, NULL b with n_a > 0 and n_b > 0; a bad memory kind.  n_a or n_b >= 2^31: FI_ERR_UNSUPPORTED.
+ * Not offered: 2-D; fi_ctx entries; neighbourhoods by radius, k > 32; approximate descriptor search; matrix-core matching
+ * (the contract fixes the order of the sum); slab contexts. */
+#define FI_FEATURE_WIDTH 33
+#define FI_FEATURE_MAX_DIM 64
+int fi_points_describe(fi_points* points, const float* normals, int k, float max_distance, float* features, unsigned char* valid,
+                       int memory);
+int fi_feature_match(int dim, long n_a, const float* a, const unsigned char* valid_a, long n_b, const float* b,
+                     const unsigned char* valid_b, long long* indices, float* distances, int memory);
+
+/* ---- the rigid motion that most matched pairs agree on: RANSAC over correspondences --------------
+ * The contract (tests/align_reference.py is its definition in numpy) is this project's own.
+ * fi_align_correspondences finds the rotation and shift x -> R x + t that carries the most source points of the matched pairs
+ * (source[src_index[c]], target[tgt_index[c]]), c = 0 .. m - 1, to within `threshold` of their target points: the coarse
+ * alignment from any pose whose result fi_points_register takes as `initial`.  3-D only: source is float[n_s * 3], target
+ * float[n_t * 3].  No search structure: the points, the indices (long long[m]) and inliers (unsigned char[m] or NULL) lie in
+ * `memory`, out on the HOST; the call runs on the current device.  Everything is fp64 computed from the fp32 coordinates, one
+ * rounding per operation (no FMA contraction), over + - * / sqrt; there are no float atomics, and every output is defined bit
+ * for bit, whatever the launch shape and the timing.
+ *   - live pairs: pair c is live iff 0 <= src_index[c] < n_s, 0 <= tgt_index[c] < n_t and all six coordinates are finite; in
+ *     ascending c the live pairs form the list pair[0 .. live).  live < 3: found = 0, trials = 0;
+ *   - hypothesis h = 0 .. max_trials - 1 draws three list positions j_k = min(floor(u(seed, 3 h + k) live), live - 1), u being
+ *     fi_mesh_sample's counter hash; a_k is the source point and b_k the target point of pair[j_k], as doubles.  It is invalid
+ *     when two of its j_k are equal; when the edge test fails: for (p, q) = (0, 1), (0, 2), (1, 2), with ls the squares of
+ *     a_q - a_p and lt those of b_q - b_p summed over ascending axes ((x_0^2 + x_1^2) + x_2^2), min(ls, lt) >= (sim sim)
+ *     max(ls, lt) must hold, sim = (double)similarity (no square root; similarity = 0: the test is not made); or when a frame
+ *     does not form: u = a_1 - a_0, l_1 = sqrt of its squares summed over ascending axes, e_1 = u / l_1; w = a_2 - a_0,
+ *     g = e_1 x w, each component the difference of two products (e_1 w_2 - e_2 w_1, e_2 w_0 - e_0 w_2, e_0 w_1 - e_1 w_0),
+ *     l = its length likewise, e_3 = g / l; e_2 = e_3 x e_1; l_1 and l must each be finite and > 0.  The same from b gives
+ *     f_1, f_2, f_3.  An invalid hypothesis scores -1;
+ *   - transform: R[r][c] = (f_1[r] e_1[c] + f_2[r] e_2[c]) + f_3[r] e_3[c]; c_s = ((a_0 + a_1) + a_2) / 3.0 per component, c_t
+ *     likewise from b; t[r] = c_t[r] - ((R[r][0] c_s[0] + R[r][1] c_s[1]) + R[r][2] c_s[2]);
+ *   - score: for a live pair (x, y): p_r = ((R[r][0] x_0 + R[r][1] x_1) + R[r][2] x_2) + t[r], d = p - y; the pair is an
+ *     inlier iff (d_0^2 + d_1^2) + d_2^2 <= (double)threshold (double)threshold -- a pair exactly at the threshold is in.  The
+ *     score is the exact count of inliers among the live pairs; the best hypothesis has the highest score, ties go to the
+ *     lowest h; `valid` counts the valid hypotheses scored; no valid hypothesis: found = 0 and the identity;
+ *   - batches and the stop: hypotheses are scored in batches of FI_ALIGN_BATCH, the last may be partial.  After every batch,
+ *     with T the hypotheses drawn so far (valid or not) and b > 0 the best score: w = b / live, p = (w w) w, q = 1 - p, and
+ *     r = q^T by fi_plane_fit's binary exponentiation: stop when r <= 1 - confidence.  confidence = 0 never stops early.
+ *     trials reports T;
+ *   - result: transform is 4 x 4 row-major, (R t) over (0 0 0 1); inliers[c] is one byte per INPUT pair from the best
+ *     hypothesis (0 for a pair that is not live); rms = sqrt(tree_sum((d_0^2 + d_1^2) + d_2^2) / inliers) over the inlier pairs
+ *     in ascending c, tree_sum being fi_cluster_measure's; 0 with none.  pairs reports m.  found = 0 leaves the identity,
+ *     rms 0 and no inliers.
+ * m = 0: found = 0, FI_OK.  FI_ERR_INVALID: NULL opt or out; NULL source, target or indices with a count > 0 that reads
+ * them; a negative count; a NaN or negative threshold; similarity outside [0, 1]; confidence outside [0, 1);
+ * max_trials outside 1 .. 2^31 - 1; a bad memory kind.  m, n_s or n_t >= 2^31: FI_ERR_UNSUPPORTED.
+ * Not offered: 2-D; a least-squares (Kabsch) refit inside the call (fi_points_register is the refit); scale; normal
+ * compatibility or distance checks beyond the edge test; fast global registration, 4PCS; slab contexts. */
+#define FI_ALIGN_BATCH 16384
+typedef struct fi_align_options {
+	float              threshold;
+	float              similarity;
+	long               max_trials;
+	double             confidence;
+	unsigned long long seed;
+} fi_align_options;
+typedef struct fi_alignment {
+	int    found;
+	long   pairs, live, trials, valid, inliers;
+	double transform[16];
+	double rms;
+} fi_alignment;
+int fi_align_correspondences(long n_s, const float* source, long n_t, const float* target, long m, const long long* src_index,
+                             const long long* tgt_index, const fi_align_options* opt, fi_alignment* out, unsigned char* inliers,
+                             int memory);
+
 /* ---- exact distances to a surface; redistancing ------------------------------------------------
  * The contract ("Distances to a surface") is this project's own.  All arithmetic is fp32, one rounding per
  * operation (no FMA contraction):

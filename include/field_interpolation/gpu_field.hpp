@@ -314,6 +314,35 @@ bool segment_planes(int ndim, const std::vector<float>& positions, float thresho
                     int refine = 2, unsigned long long seed = 0, const std::vector<unsigned char>& mask = std::vector<unsigned char>(),
                     const std::vector<float>& axis = std::vector<float>(), float min_cos = 0.0f);
 
+// What every point's neighbourhood looks like, as 33 floats that survive a turn and a shift of the cloud (fast point feature
+// histograms over the k nearest points and the normals; 3 floats per point each), on the device.  valid (optional): one byte
+// per point, 0 where a point has no descriptor (its 33 floats are zeros).  The contract is include/fi_hip.h
+// fi_points_describe.  false: the library refused the call.
+bool describe_points(const std::vector<float>& positions, const std::vector<float>& normals, std::vector<float>* features,
+                     std::vector<unsigned char>* valid = nullptr, int k = 32,
+                     float max_distance = std::numeric_limits<float>::infinity());
+// For every row of a (dim floats each) the nearest row of b, equal distances to the smallest index; -1 and +inf for a row that
+// is masked out (valid_a / valid_b: one byte per row, may be empty), non-finite or without a partner.  The contract is
+// include/fi_hip.h fi_feature_match.
+bool match_features(int dim, const std::vector<float>& a, const std::vector<float>& b, std::vector<long long>* indices,
+                    std::vector<float>* distances = nullptr, const std::vector<unsigned char>& valid_a = std::vector<unsigned char>(),
+                    const std::vector<unsigned char>& valid_b = std::vector<unsigned char>());
+// The result of align_correspondences (include/fi_hip.h fi_alignment), field for field.
+struct Alignment
+{
+	int    found;
+	long   pairs, live, trials, valid, inliers;
+	double transform[16], rms;
+};
+// The rotation and shift that carries the most matched pairs (source[src_index[c]], target[tgt_index[c]]) to within
+// `threshold` of each other, by RANSAC on the device: 3 floats per point; transform is 4 x 4 row-major, source to target.
+// inliers (optional): one byte per pair.  Every figure is defined bit for bit: the contract is include/fi_hip.h
+// fi_align_correspondences.
+bool align_correspondences(const std::vector<float>& source, const std::vector<float>& target, const std::vector<long long>& src_index,
+                           const std::vector<long long>& tgt_index, float threshold, Alignment* out,
+                           std::vector<unsigned char>* inliers = nullptr, float similarity = 0.9f, long max_trials = 100000,
+                           double confidence = 0.999, unsigned long long seed = 0);
+
 // The stateless solver calls of sparse_linear.hpp keep device contexts between calls, keyed by shape and precision (at
 // most six, systems of up to 2^20 unknowns only; larger systems get a context per call): the per-frame caller's latency
 // (src/bipolar_2d.cpp:730).  This frees the calling thread's cached contexts (they are freed at thread exit otherwise)
