@@ -18,16 +18,17 @@
 //              wave read one address per instruction (a broadcast, no bank conflict), so the count needs no cross-lane
 //              operation and no atomic in the loop.  The grid is (pair tiles, capped and strided) x (groups of 256 listed
 //              slots; the groups past the list leave at once); a workgroup adds its counts with integer atomics.
-//   best       k_align_keys: count << 32 | (0xFFFFFFFF - h) per valid hypothesis, one 64-bit maximum kept across batches on
-//              the device; the host reads it (with the live and valid counts) once a batch and runs the stop rule.
+//   best       k_align_keys and the batch loop: fi_consensus.h, as the draw at the head of a hypothesis; the head's spare word
+//              is the batch's valid count.
 //   result     k_align_pick recomputes the winner with the same device function; k_align_flags (one thread per input pair),
-//              select_indices (the inlier pairs, ascending), k_align_chunks (one workgroup per 256 of them: the contract's tree
-//              in LDS) and k_align_finish (one wave adds the chunk sums in ascending order; the rms, the result).
+//              select_indices (the inlier pairs, ascending), k_align_chunks and k_align_finish (fi_treesum.h's fixed-order
+//              sum; then the rms, the result).
 // One device allocation (fi_arena.h) a call; one read-back a batch and one for the result.
 #include "fi_solver_internal.h"
 #include "fi_align.h"
+#include "fi_consensus.h"
 #include "fi_prim.h"
-#include "fi_uniform.h"
+#include "fi_treesum.h"
 
 #include <algorithm>
 #include <cmath>
@@ -37,19 +38,17 @@ namespace {
 
 constexpr int kBatch   = 16384;  // FI_ALIGN_BATCH: the hypotheses drawn before the stop rule is asked
 constexpr int kTile    = 256;    // the live pairs a workgroup stages at a time
-constexpr int kChunk   = 256;    // the contract's chunk of the fixed-order sum
+constexpr int kChunk   = treesum::kChunk;  // the inlier pairs a workgroup sums
 constexpr int kMaxTile = 512;    // the cap of the score grid's x
 static_assert(kBatch == FI_ALIGN_BATCH, "the batch is part of the contract");
 static_assert(kBatch % kThreads == 0 && kTile == kThreads && kChunk == kThreads, "one lane per hypothesis, per staged pair, per member");
 
-// what stays on the device between the kernels of a call; the host reads the first 16 bytes once a batch
+// what stays on the device between the kernels of a call
 struct AlignState {
-	unsigned long long best;    // the largest key so far (0: no valid hypothesis yet)
-	uint32_t           live;    // the live pairs (select_indices writes it)
-	uint32_t           nvalid;  // the valid hypotheses of the batch (select_indices writes it)
-	uint32_t           count;   // the inlier pairs of the winner (select_indices writes it)
-	double             M[12];   // the winner: row r is R[r][0], R[r][1], R[r][2], t[r]
-	fi_alignment       out;
+	consensus::Head head;    // head.live: the live pairs; head.spare: the valid hypotheses of the batch (select_indices writes it)
+	uint32_t        count;   // the inlier pairs of the winner (select_indices writes it)
+	double          M[12];   // the winner: row r is R[r][0], R[r][1], R[r][2], t[r]
+	fi_alignment    out;
 };
 
 struct AlignArgs {
@@ -113,14 +112,8 @@ __device__ inline bool hypothesis(const AlignArgs& a, uint64_t h, uint32_t live,
 {
 	if (live < 3u) { return false; }
 	uint32_t j[3];
-#pragma unroll
-	for (int k = 0; k < 3; ++k) {
-		const double   u  = counter::uniform(a.seed, h * 3 + k);
-		const uint64_t at = static_cast<uint64_t>(floor(u * static_cast<double>(live)));
-		j[k]              = at < live - 1 ? static_cast<uint32_t>(at) : live - 1;
-	}
-	bool   ok = j[0] != j[1] && j[0] != j[2] && j[1] != j[2];
-	double p[3][3], q[3][3];
+	bool     ok = consensus::draw<3>(a.seed, h, live, j);
+	double   p[3][3], q[3][3];
 #pragma unroll
 	for (int k = 0; k < 3; ++k) {
 		const uint32_t c = a.pair[j[k]];
@@ -192,7 +185,7 @@ __global__ __launch_bounds__(kThreads) void k_align_models(AlignArgs a, int64_t 
 {
 	const int  t = blockIdx.x * kThreads + threadIdx.x;
 	double     M[12];
-	const bool ok = t < count && hypothesis(a, static_cast<uint64_t>(first + t), a.state->live, M);
+	const bool ok = t < count && hypothesis(a, static_cast<uint64_t>(first + t), a.state->head.live, M);
 #pragma unroll
 	for (int x = 0; x < 12; ++x) { a.hyp[x * kBatch + t] = ok ? M[x] : NAN; }
 	a.vflag[t] = ok ? 1 : 0;
@@ -204,10 +197,10 @@ __global__ __launch_bounds__(kThreads) void k_align_score(AlignArgs a)
 {
 	__shared__ double s[kTile][6];
 	const int         t      = threadIdx.x;
-	const uint32_t    nvalid = a.state->nvalid;
+	const uint32_t    nvalid = a.state->head.spare;
 	const uint32_t    at     = blockIdx.y * kThreads + t;
 	if (blockIdx.y * kThreads >= nvalid) { return; }  // (the same for every thread of the workgroup)
-	const int64_t  live = a.state->live;
+	const int64_t  live = a.state->head.live;
 	const uint32_t slot = at < nvalid ? a.slot[at] : 0u;
 	double         M[12];
 #pragma unroll
@@ -243,18 +236,9 @@ __global__ __launch_bounds__(kThreads) void k_align_score(AlignArgs a)
 	if (count != 0) { atomicAdd(&a.counts[slot], count); }
 }
 
-// the key of every valid slot, the maximum of a wave by shuffles, one 64-bit integer atomic a wave; the counts are left zero
 __global__ __launch_bounds__(kThreads) void k_align_keys(AlignArgs a, int64_t first)
 {
-	const int          t   = blockIdx.x * kThreads + threadIdx.x;
-	const uint32_t     h   = static_cast<uint32_t>(first + t);
-	unsigned long long key = a.vflag[t] ? (static_cast<unsigned long long>(a.counts[t]) << 32) | (0xFFFFFFFFu - h) : 0ull;
-	a.counts[t]            = 0;
-	for (int o = 32; o > 0; o >>= 1) {
-		const unsigned long long other = __shfl_xor(key, o, 64);
-		key                            = other > key ? other : key;
-	}
-	if ((threadIdx.x & 63) == 0 && key != 0) { atomicMax(&a.state->best, key); }
+	consensus::keep_best(blockIdx.x * kThreads + threadIdx.x, first, a.vflag, a.counts, &a.state->head);
 }
 
 // the winner becomes the result's motion: the same function of (seed, h, live pairs), so the same bits
@@ -262,7 +246,7 @@ __global__ __launch_bounds__(64) void k_align_pick(AlignArgs a, uint64_t h)
 {
 	if (threadIdx.x != 0) { return; }
 	double M[12];
-	hypothesis(a, h, a.state->live, M);
+	hypothesis(a, h, a.state->head.live, M);
 #pragma unroll
 	for (int x = 0; x < 12; ++x) { a.state->M[x] = M[x]; }
 }
@@ -291,43 +275,33 @@ __global__ __launch_bounds__(kThreads) void k_align_flags(AlignArgs a)
 	a.flag[c] = in ? 1 : 0;
 }
 
-// one workgroup per chunk of 256 consecutive inlier pairs: s[t] += s[t + w], w = 128 .. 1; the tail adds 0.0
+// one workgroup per chunk of 256 consecutive inlier pairs: the block tree of their squared misses; the tail adds 0.0
 __global__ __launch_bounds__(kChunk) void k_align_chunks(AlignArgs a)
 {
-	__shared__ double s[kChunk];
+	__shared__ double s[1][kChunk];
 	const int64_t     count = a.state->count;
 	const int64_t     first = static_cast<int64_t>(blockIdx.x) * kChunk;
 	if (first >= count) { return; }  // (the same for every thread of the workgroup)
-	const int t = threadIdx.x;
-	double    v = 0.0;
+	const int t    = threadIdx.x;
+	double    v[1] = {0.0};
 	if (first + t < count) {
 		double M[12];
 #pragma unroll
 		for (int x = 0; x < 12; ++x) { M[x] = a.state->M[x]; }
-		v = miss_of_pair(a, M, a.member[first + t]);
+		v[0] = miss_of_pair(a, M, a.member[first + t]);
 	}
-	s[t] = v;
-	__syncthreads();
-	for (int w = kChunk / 2; w > 0; w >>= 1) {
-		if (t < w) { s[t] = s[t] + s[t + w]; }
-		__syncthreads();
-	}
-	if (t == 0) { a.partial[blockIdx.x] = s[0]; }
+	treesum::block_tree<1>(v, s);
+	if (t == 0) { a.partial[blockIdx.x] = s[0][0]; }
 }
 
-// one wave: the chunk sums added in ascending order from 0.0 (64 chunks a load, handed to every lane in turn); the result
+// one wave: the chunk sums in ascending order; the result
 __global__ __launch_bounds__(64) void k_align_finish(AlignArgs a)
 {
 	AlignState&   st    = *a.state;
 	const int     lane  = threadIdx.x;
 	const int64_t count = st.count;
-	const int64_t nb    = (count + kChunk - 1) / kChunk;
-	double        total = 0.0;
-	for (int64_t b0 = 0; b0 < nb; b0 += 64) {
-		const double v = b0 + lane < nb ? a.partial[b0 + lane] : 0.0;
-		const int    e = nb - b0 < 64 ? static_cast<int>(nb - b0) : 64;
-		for (int l = 0; l < e; ++l) { total = total + __shfl(v, l, 64); }
-	}
+	double        total[1];
+	treesum::ordered_sum<1>(a.partial, 1, (count + kChunk - 1) / kChunk, lane, total);
 	if (lane != 0) { return; }
 	fi_alignment o{};
 	o.found   = 1;
@@ -335,51 +309,14 @@ __global__ __launch_bounds__(64) void k_align_finish(AlignArgs a)
 #pragma unroll
 	for (int x = 0; x < 12; ++x) { o.transform[x] = st.M[x]; }
 	o.transform[15] = 1.0;
-	o.rms           = count > 0 ? sqrt(total / static_cast<double>(count)) : 0.0;
+	o.rms           = count > 0 ? sqrt(total[0] / static_cast<double>(count)) : 0.0;
 	st.out          = o;
 }
 
 // ---- the host side ------------------------------------------------------------------------------------------------------
 
-using namespace prim;  // Arena, Scratch, arena_alloc, select_indices, grid
+using namespace prim;  // Arena, Scratch, arena_alloc, select_marked, grid
 static_assert(kThreads == kGridThreads, "grid() counts work groups of kThreads");
-
-struct Marked {
-	const unsigned char* f;
-	__device__ bool      operator()(uint32_t i) const { return f[i] != 0; }
-};
-
-size_t select_bytes(int64_t n)
-{
-	size_t tb = 0;
-	FI_HIP_TRY(select_indices(nullptr, tb, static_cast<uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), static_cast<size_t>(n), Marked{nullptr},
-	                          nullptr));
-	return tb;
-}
-
-// out = the indices i < n with f[i] != 0, ascending; *count = how many
-void select_marked(const unsigned char* f, uint32_t* out, uint32_t* count, int64_t n, const Scratch& tmp, hipStream_t st)
-{
-	size_t tb = 0;
-	FI_HIP_TRY(select_indices(nullptr, tb, out, count, static_cast<size_t>(n), Marked{f}, st));
-	DevBuf more;  // (should the library want more than the sizing pass asked about)
-	if (tb > tmp.bytes) { more.alloc(tb); }
-	FI_HIP_TRY(select_indices(more.p ? more.p : tmp.p, tb, out, count, static_cast<size_t>(n), Marked{f}, st));
-}
-
-// the stop rule: r = (1 - w^3)^T by binary exponentiation from the low bit, w = b / live; add, multiply and compare only
-bool confident(long long b, long long live, long long T, double confidence)
-{
-	const double w = static_cast<double>(b) / static_cast<double>(live);
-	const double p = (w * w) * w;
-	const double q = 1.0 - p;
-	double       r = 1.0, base = q;
-	for (unsigned long long e = static_cast<unsigned long long>(T); e; e >>= 1) {
-		if (e & 1) { r = r * base; }
-		base = base * base;
-	}
-	return r <= 1.0 - confidence;
-}
 
 void identity(fi_alignment* out, int64_t m)
 {
@@ -448,34 +385,20 @@ void align_correspondences(int64_t n_s, const float* source, int64_t n_t, const 
 
 	hipLaunchKernelGGL(k_align_live, grid(m), dim3(kThreads), 0, st, m, n_s, n_t, src, tgt, si, ti, lflag);
 	FI_HIP_TRY(hipGetLastError());
-	select_marked(lflag, pair, &a.state->live, m, tmp, st);
+	select_marked(lflag, pair, &a.state->head.live, m, tmp, st);
 
 	const unsigned tiles = static_cast<unsigned>(std::min<int64_t>((m + kTile - 1) / kTile, kMaxTile));
-	struct {
-		unsigned long long best;
-		uint32_t           live, nvalid;
-	} seen{};
-	long long T = 0, valid = 0;
-	for (int64_t first = 0; first < opt.max_trials; first += kBatch) {
-		const int count = static_cast<int>(std::min<int64_t>(kBatch, opt.max_trials - first));
+	const consensus::Trials ran = consensus::run_batches(&a.state->head, 3, kBatch, opt.max_trials, opt.confidence, st, [&](int64_t first, int count) {
 		hipLaunchKernelGGL(k_align_models, dim3(kBatch / kThreads), dim3(kThreads), 0, st, a, first, count);
 		FI_HIP_TRY(hipGetLastError());
-		select_marked(a.vflag, slot, &a.state->nvalid, kBatch, tmp, st);
+		select_marked(a.vflag, slot, &a.state->head.spare, kBatch, tmp, st);
 		hipLaunchKernelGGL(k_align_score, dim3(tiles, kBatch / kThreads), dim3(kThreads), 0, st, a);
 		hipLaunchKernelGGL(k_align_keys, dim3(kBatch / kThreads), dim3(kThreads), 0, st, a, first);
-		FI_HIP_TRY(hipGetLastError());
-		FI_HIP_TRY(hipMemcpyAsync(&seen, a.state, sizeof(seen), hipMemcpyDeviceToHost, st));
-		FI_HIP_TRY(hipStreamSynchronize(st));
-		if (seen.live < 3u) { break; }  // trials = 0
-		T = first + count;
-		valid += seen.nvalid;
-		const long long b = static_cast<long long>(seen.best >> 32);
-		if (b > 0 && opt.confidence > 0.0 && confident(b, seen.live, T, opt.confidence)) { break; }
-	}
-	out->live   = static_cast<long>(seen.live);
-	out->trials = static_cast<long>(T);
-	out->valid  = static_cast<long>(valid);
-	if (seen.best == 0) {
+	});
+	out->live   = static_cast<long>(ran.seen.live);
+	out->trials = static_cast<long>(ran.T);
+	out->valid  = static_cast<long>(ran.spare);
+	if (ran.seen.best == 0) {
 		if (inliers) {
 			if (to_host) {
 				std::fill(inliers, inliers + m, static_cast<unsigned char>(0));
@@ -486,8 +409,7 @@ void align_correspondences(int64_t n_s, const float* source, int64_t n_t, const 
 		}
 		return;
 	}
-	const uint64_t h = 0xFFFFFFFFu - static_cast<uint32_t>(seen.best & 0xFFFFFFFFull);
-	hipLaunchKernelGGL(k_align_pick, dim3(1), dim3(64), 0, st, a, h);
+	hipLaunchKernelGGL(k_align_pick, dim3(1), dim3(64), 0, st, a, consensus::winner_of(ran.seen.best));
 	hipLaunchKernelGGL(k_align_flags, grid(m), dim3(kThreads), 0, st, a);
 	FI_HIP_TRY(hipGetLastError());
 	select_marked(a.flag, member, &a.state->count, m, tmp, st);
@@ -500,9 +422,9 @@ void align_correspondences(int64_t n_s, const float* source, int64_t n_t, const 
 	FI_HIP_TRY(hipStreamSynchronize(st));
 	*out        = got.out;
 	out->pairs  = static_cast<long>(m);
-	out->live   = static_cast<long>(seen.live);
-	out->trials = static_cast<long>(T);
-	out->valid  = static_cast<long>(valid);
+	out->live   = static_cast<long>(ran.seen.live);
+	out->trials = static_cast<long>(ran.T);
+	out->valid  = static_cast<long>(ran.spare);
 }
 
 }  // namespace fi

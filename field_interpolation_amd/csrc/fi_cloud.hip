@@ -13,9 +13,8 @@
 //   neighbours one thread per SORTED SLOT of the tree, as k_knn_normals: a wave's points are Morton neighbours and walk the
 //              same nodes; fi_knn_list.h's register-resident list in the classes 8 / 16 / 32.  The point itself is left out by
 //              its index, so k neighbours need a list of k, not k + 1.  Results go to the point's own index.
-//   statistics the means in point order: a tree sum per block of 256 consecutive indices, the block sums added in turn by one
-//              wave, twice (the mean, then the squared deviations from it); then the mask.  The order of the sums does not
-//              know the Morton sort.
+//   statistics fi_treesum.h's fixed-order sum over the means in point order, twice (the mean, then the squared deviations
+//              from it); then the mask.  The order of the sums does not know the Morton sort.
 //   thinning   no tree: (cell key, index) pairs sorted by key (fi_prim.h's Onesweep, stable: a cell's points ascend), run heads
 //              scanned into cell numbers, one thread per cell walking its run; one read-back (error bit and cell count), one
 //              device allocation (fi_arena.h) -- fi_simplify.hip's shape.
@@ -25,6 +24,7 @@
 #include "fi_bvh.h"
 #include "fi_knn_list.h"
 #include "fi_prim.h"
+#include "fi_treesum.h"
 
 #include <algorithm>
 
@@ -34,13 +34,6 @@ namespace {
 
 using namespace bvh;
 using namespace knn;
-
-// one add per wave of the lanes whose flag is set (every lane of the wave calls this)
-__device__ inline void count_flags(bool flag, unsigned long long* total)
-{
-	const unsigned long long lanes = __ballot(flag);
-	if ((threadIdx.x & 63) == 0 && lanes != 0) { atomicAdd(total, static_cast<unsigned long long>(__popcll(lanes))); }
-}
 
 // ---- points within a radius ---------------------------------------------------------------------------------------------
 
@@ -95,7 +88,7 @@ __global__ __launch_bounds__(kThreads) void k_cloud_radius(RadiusArgs a)
 			a.counts[i] = c;
 		}
 	}
-	if constexpr (SELF) { count_flags(kept, a.kept); }
+	if constexpr (SELF) { treesum::count_flags(kept, a.kept); }
 }
 
 template <int D>
@@ -208,7 +201,7 @@ void neighbours_on_device(const NearestIndex& t, int k, float max_distance, floa
 
 // ---- the statistical rule -----------------------------------------------------------------------------------------------
 
-constexpr int kSumBlock = 256;  // the contract's block of the fixed-order sum
+constexpr int kSumBlock = treesum::kChunk;  // the indices a workgroup sums
 
 struct StatState {
 	double             mean, stddev, threshold;
@@ -216,76 +209,66 @@ struct StatState {
 	unsigned long long kept;
 };
 
-// the block sums of the counted x (PASS 0, with their number) or of their squared deviations from the mean (PASS 1): the
-// tree s[t] += s[t + w], w = 128 .. 1; an uncounted point and the tail add 0.0
+// the block sums of the counted x (PASS 0, with their number) or of their squared deviations from the mean (PASS 1); an
+// uncounted point and the tail add 0.0.  The number is an integer, no part of the fixed-order sum: it keeps a tree of its own.
 template <int PASS>
 __global__ __launch_bounds__(kSumBlock) void k_cloud_block_sums(int64_t n, const float* __restrict__ x32, const StatState* __restrict__ state,
                                                                 double* __restrict__ part, uint32_t* __restrict__ cnt)
 {
-	__shared__ double   s[kSumBlock];
+	__shared__ double   s[1][kSumBlock];
 	__shared__ uint32_t c[kSumBlock];
-	const int     t = threadIdx.x;
-	const int64_t i = static_cast<int64_t>(blockIdx.x) * kSumBlock + t;
-	double        v = 0.0;
-	uint32_t      m = 0;
+	const int     t    = threadIdx.x;
+	const int64_t i    = static_cast<int64_t>(blockIdx.x) * kSumBlock + t;
+	double        v[1] = {0.0};
+	uint32_t      m    = 0;
 	if (i < n) {
 		const double x = static_cast<double>(x32[i]);
 		if (isfinite(x)) {
 			m = 1;
 			if constexpr (PASS == 0) {
-				v = x;
+				v[0] = x;
 			} else {
 				const double e = x - state->mean;
-				v              = e * e;
+				v[0]           = e * e;
 			}
 		}
 	}
-	s[t] = v;
 	c[t] = m;
-	__syncthreads();
+	treesum::block_tree<1>(v, s);
 	for (int w = kSumBlock / 2; w > 0; w >>= 1) {
-		if (t < w) {
-			s[t] = s[t] + s[t + w];
-			c[t] += c[t + w];
-		}
+		if (t < w) { c[t] += c[t + w]; }
 		__syncthreads();
 	}
 	if (t == 0) {
-		part[blockIdx.x] = s[0];
+		part[blockIdx.x] = s[0][0];
 		if constexpr (PASS == 0) { cnt[blockIdx.x] = c[0]; }
 	}
 }
 
-// one wave: the block sums added in ascending order from 0.0 (64 of them a load, handed to every lane in turn), then the
-// mean (PASS 0) or the standard deviation and the threshold (PASS 1)
+// one wave: the block sums in ascending order, then the mean (PASS 0) or the standard deviation and the threshold (PASS 1)
 template <int PASS>
 __global__ __launch_bounds__(64) void k_cloud_finish(int64_t nb, const double* __restrict__ part, const uint32_t* __restrict__ cnt, float std_ratio,
                                                      StatState* __restrict__ state)
 {
-	const int lane  = threadIdx.x;
-	double    total = 0.0;
-	long long N     = 0;
-	for (int64_t b0 = 0; b0 < nb; b0 += 64) {
-		const bool     have = b0 + lane < nb;
-		const double   v    = have ? part[b0 + lane] : 0.0;
-		const uint32_t c    = PASS == 0 && have ? cnt[b0 + lane] : 0u;
-		const int      e    = nb - b0 < 64 ? static_cast<int>(nb - b0) : 64;
-		for (int l = 0; l < e; ++l) {
-			total = total + __shfl(v, l, 64);
-			N += __shfl(c, l, 64);
-		}
+	const int lane = threadIdx.x;
+	double    total[1];
+	treesum::ordered_sum<1>(part, 1, nb, lane, total);
+	long long N = 0;
+	if constexpr (PASS == 0) {  // the counts of the blocks lane, lane + 64, ...; then the wave's
+		for (int64_t b = lane; b < nb; b += 64) { N += cnt[b]; }
+		for (int o = 32; o > 0; o >>= 1) { N += __shfl_xor(N, o, 64); }
 	}
 	if (lane != 0) { return; }
 	if constexpr (PASS == 0) {
 		state->counted   = N;
 		state->kept      = 0;
-		state->mean      = N > 0 ? total / static_cast<double>(N) : 0.0;
+		state->mean      = N > 0 ? total[0] / static_cast<double>(N) : 0.0;
 		state->stddev    = 0.0;
 		state->threshold = 0.0;
 	} else {
 		N = state->counted;
 		if (N > 0) {
-			const double sd  = sqrt(total / static_cast<double>(N));
+			const double sd  = sqrt(total[0] / static_cast<double>(N));
 			state->stddev    = sd;
 			state->threshold = state->mean + static_cast<double>(std_ratio) * sd;
 		}
@@ -301,7 +284,7 @@ __global__ __launch_bounds__(kThreads) void k_cloud_keep(int64_t n, const float*
 		kept           = isfinite(x) && x <= state->threshold;
 		if (keep) { keep[i] = kept ? 1 : 0; }
 	}
-	count_flags(kept, &state->kept);
+	treesum::count_flags(kept, &state->kept);
 }
 
 // ---- thinning -----------------------------------------------------------------------------------------------------------

@@ -29,6 +29,7 @@
 #include "fi_bvh.h"
 #include "fi_knn_list.h"
 #include "fi_prim.h"
+#include "fi_treesum.h"
 #include "fi_unionfind.h"
 
 #include <algorithm>
@@ -41,13 +42,6 @@ namespace {
 using namespace bvh;
 using namespace unionfind;
 using knn::Staged;
-
-// one add per wave of the lanes whose flag is set (every lane of the wave calls this)
-__device__ inline void count_flags(bool flag, unsigned long long* total)
-{
-	const unsigned long long lanes = __ballot(flag);
-	if ((threadIdx.x & 63) == 0 && lanes != 0) { atomicAdd(total, static_cast<unsigned long long>(__popcll(lanes))); }
-}
 
 // ---- labels ---------------------------------------------------------------------------------------------------------
 
@@ -172,8 +166,8 @@ __global__ __launch_bounds__(kThreads) void k_cluster_border(ClusterArgs a)
 		}
 		if (a.labels) { a.labels[me] = at_core == kNone ? -1 : static_cast<int>(a.number[a.parent[at_core]]); }
 	}
-	count_flags(is_core, &a.totals[0]);
-	count_flags(is_border, &a.totals[1]);
+	treesum::count_flags(is_core, &a.totals[0]);
+	treesum::count_flags(is_border, &a.totals[1]);
 }
 
 template <int D>
@@ -199,7 +193,7 @@ void launch_labels(int D, const ClusterArgs& a, hipStream_t st, int step)
 
 // ---- the table ------------------------------------------------------------------------------------------------------
 
-constexpr int      kChunk    = 256;  // the contract's chunk of the fixed-order sum: members a workgroup sums, one each
+constexpr int      kChunk    = treesum::kChunk;  // the contract's chunk of the fixed-order sum: members a workgroup sums, one each
 constexpr uint32_t kErrLabel = 1u;
 
 // (label, index) of every point; a point of no cluster gets the key `nc`, behind every cluster's
@@ -237,7 +231,7 @@ __global__ __launch_bounds__(kThreads) void k_cluster_chunk_counts(int64_t nc, c
 {
 	const int64_t c = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
 	if (c > nc) { return; }
-	nchunks[c] = c < nc ? (first[c + 1] - first[c] + kChunk - 1) / kChunk : 0u;
+	nchunks[c] = treesum::chunks_of(first, c, nc);
 }
 
 struct ChunkPartial {
@@ -258,17 +252,7 @@ __global__ __launch_bounds__(kChunk) void k_cluster_chunks(int64_t nc, const uin
 	__shared__ uint32_t s_core[kChunk];
 	const uint32_t chunk = blockIdx.x;
 	if (chunk >= chunk_first[nc]) { return; }  // (the grid is the bound n / kChunk + nc: the whole workgroup leaves)
-	// the cluster of this chunk: the last c with chunk_first[c] <= chunk (a cluster without members has no chunk and shares
-	// its entry with the next one)
-	int64_t lo = 0, hi = nc - 1;
-	while (lo < hi) {
-		const int64_t mid = (lo + hi + 1) / 2;
-		if (chunk_first[mid] <= chunk) {
-			lo = mid;
-		} else {
-			hi = mid - 1;
-		}
-	}
+	const int64_t  lo    = treesum::owner_of(chunk_first, nc, chunk);  // the cluster of this chunk
 	const uint32_t begin = first[lo] + (chunk - chunk_first[lo]) * kChunk, end = first[lo + 1];
 	const int      t     = threadIdx.x;
 	const uint32_t s     = begin + t;

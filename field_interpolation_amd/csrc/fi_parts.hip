@@ -23,6 +23,7 @@
 #include "fi_solver_internal.h"
 #include "fi_parts.h"
 #include "fi_prim.h"
+#include "fi_treesum.h"
 #include "fi_unionfind.h"
 
 #include <algorithm>
@@ -42,7 +43,7 @@ namespace {
 
 using namespace unionfind;  // word_load, word_store, find_root, unite
 
-constexpr int kChunk = 256;  // primitives a workgroup of the measuring pass sums: one each
+constexpr int kChunk = treesum::kChunk;  // primitives a workgroup of the measuring pass sums: one each
 
 // ---- labels ---------------------------------------------------------------------------------------------------------
 
@@ -260,7 +261,7 @@ __global__ __launch_bounds__(kThreads) void k_parts_chunk_counts(int64_t nparts,
 {
 	const int64_t c = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
 	if (c > nparts) { return; }
-	nchunks[c] = c < nparts ? (first[c + 1] - first[c] + kChunk - 1) / kChunk : 0u;
+	nchunks[c] = treesum::chunks_of(first, c, nparts);
 }
 
 struct ChunkPartial {
@@ -291,16 +292,7 @@ __global__ __launch_bounds__(kChunk) void k_parts_chunks(int64_t nparts, const u
 	__shared__ double s_sum[2][kChunk / 64];
 	__shared__ float  s_box[6][kChunk / 64];
 	const uint32_t chunk = blockIdx.x;
-	// the part of this chunk: the last c with chunk_first[c] <= chunk (chunk_first ascends strictly: every part has a chunk)
-	int64_t lo = 0, hi = nparts - 1;
-	while (lo < hi) {
-		const int64_t mid = (lo + hi + 1) / 2;
-		if (chunk_first[mid] <= chunk) {
-			lo = mid;
-		} else {
-			hi = mid - 1;
-		}
-	}
+	const int64_t  lo    = treesum::owner_of(chunk_first, nparts, chunk);  // the part of this chunk (every part has one)
 	const uint32_t begin = first[lo] + (chunk - chunk_first[lo]) * kChunk, end = first[lo + 1];
 	const uint32_t s     = begin + threadIdx.x;
 	double         size = 0.0, enclosed = 0.0;

@@ -15,18 +15,17 @@
 //              per instruction (a broadcast, no bank conflict), so the count needs no cross-lane operation and no atomic in
 //              the loop.  The grid is (point tiles, capped and strided) x (4 groups of 256 hypotheses); a workgroup adds its
 //              256 counts with integer atomics: integers add up the same in any order.
-//   best       k_plane_keys: count << 32 | (0xFFFFFFFF - h) per valid hypothesis, one 64-bit maximum kept across batches on
-//              the device; the host reads it (and the candidate count) once a batch and runs the stop rule.
+//   best       k_plane_keys and the batch loop: fi_consensus.h, as the draw at the head of a hypothesis.
 //   refits     k_plane_flags (one thread per point against the current model), select_indices (the members, ascending),
-//              k_plane_chunks (one workgroup per 256 members: the contract's tree in LDS) and k_plane_finish (one wave adds
-//              the chunk sums in ascending order; Jacobi, the sign, the model).  The refit loop never returns to the host: a
-//              `done` word on the device turns the remaining rounds into no-ops.
+//              k_plane_chunks and k_plane_finish (fi_treesum.h's fixed-order sum; then Jacobi, the sign, the model).  The
+//              refit loop never returns to the host: a `done` word on the device turns the remaining rounds into no-ops.
 // One device allocation (fi_arena.h) a call; per plane one read-back a batch and one for the model.
 #include "fi_solver_internal.h"
 #include "fi_plane.h"
+#include "fi_consensus.h"
 #include "fi_jacobi.h"
 #include "fi_prim.h"
-#include "fi_uniform.h"
+#include "fi_treesum.h"
 
 #include <algorithm>
 #include <cmath>
@@ -36,7 +35,7 @@ namespace {
 
 constexpr int kBatch   = 1024;  // FI_PLANE_BATCH: the hypotheses scored before the stop rule is asked
 constexpr int kTile    = 256;   // the candidates a workgroup stages at a time
-constexpr int kChunk   = 256;   // the contract's chunk of the fixed-order sum
+constexpr int kChunk   = treesum::kChunk;  // the members a workgroup sums
 constexpr int kMaxK    = 6;     // the sums of a chunk pass: D centroid sums, D (D + 1) / 2 moments, or e^2
 constexpr int kMaxTile = 512;   // the cap of the score grid's x (Guideline 11: 512 x 4 = 2048 workgroups)
 static_assert(kBatch == FI_PLANE_BATCH, "the batch is part of the contract");
@@ -44,10 +43,9 @@ static_assert(kBatch % kThreads == 0 && kTile == kThreads && kChunk == kThreads,
 
 // what stays on the device between the kernels of one plane
 struct PlaneState {
-	unsigned long long best;   // the largest key so far (0: no valid hypothesis yet)
-	uint32_t           m;      // the candidates (select_indices writes it)
-	uint32_t           count;  // the members of the current model (select_indices writes it)
-	int                done;   // the refits have ended
+	consensus::Head head;   // head.live: the candidates; the spare word is not used
+	uint32_t        count;  // the members of the current model (select_indices writes it)
+	int             done;   // the refits have ended
 	int                refits;
 	double             n[3], d;  // the current model
 	double             c[3];     // the members' centroid
@@ -68,7 +66,7 @@ struct PlaneArgs {
 	int                  constrained;
 	double               thr;     // (double)threshold
 	double*              hyp;     // double[4][kBatch]: n_0, n_1, n_2 (unused in 2-D), d of the batch
-	uint32_t*            valid;   // uint32[kBatch]
+	unsigned char*       valid;   // uint8[kBatch]: a valid hypothesis
 	uint32_t*            counts;  // uint32[kBatch]; zero between batches
 	double*              partial; // double[chunks][kMaxK]
 };
@@ -94,16 +92,9 @@ template <int D>
 __device__ inline bool hypothesis(const PlaneArgs& a, uint64_t h, uint32_t m, double (&n)[D], double& d)
 {
 	if (m < static_cast<uint32_t>(D)) { return false; }
-	uint32_t j[D];
-#pragma unroll
-	for (int k = 0; k < D; ++k) {
-		const double   u  = counter::uniform(a.seed, h * D + k);
-		const uint64_t at = static_cast<uint64_t>(floor(u * static_cast<double>(m)));
-		j[k]              = at < m - 1 ? static_cast<uint32_t>(at) : m - 1;
-	}
-	bool distinct = j[0] != j[1];
-	if constexpr (D == 3) { distinct = distinct && j[0] != j[2] && j[1] != j[2]; }
-	double p[D][D];
+	uint32_t   j[D];
+	const bool distinct = consensus::draw<D>(a.seed, h, m, j);
+	double     p[D][D];
 #pragma unroll
 	for (int k = 0; k < D; ++k) { load_point<D>(a.pos, a.cand[j[k]], p[k]); }
 	if constexpr (D == 3) {
@@ -164,11 +155,11 @@ __global__ __launch_bounds__(kThreads) void k_plane_models(PlaneArgs a, int64_t 
 {
 	const int t = blockIdx.x * kThreads + threadIdx.x;
 	double    n[D], d = 0.0;
-	const bool ok = t < count && hypothesis<D>(a, static_cast<uint64_t>(first + t), a.state->m, n, d);
+	const bool ok = t < count && hypothesis<D>(a, static_cast<uint64_t>(first + t), a.state->head.live, n, d);
 #pragma unroll
 	for (int x = 0; x < D; ++x) { a.hyp[x * kBatch + t] = ok ? n[x] : NAN; }
 	a.hyp[3 * kBatch + t] = ok ? d : NAN;
-	a.valid[t]            = ok ? 1u : 0u;
+	a.valid[t]            = ok ? 1 : 0;
 }
 
 // lane t of group blockIdx.y owns hypothesis slot blockIdx.y * 256 + t; the workgroup walks the tiles blockIdx.x,
@@ -180,7 +171,7 @@ __global__ __launch_bounds__(kThreads) void k_plane_score(PlaneArgs a)
 	__shared__ double s[kTile][W];
 	const int         t    = threadIdx.x;
 	const int         slot = blockIdx.y * kThreads + t;
-	const int64_t     m    = a.state->m;
+	const int64_t     m    = a.state->head.live;
 	double            n[D];
 #pragma unroll
 	for (int x = 0; x < D; ++x) { n[x] = a.hyp[x * kBatch + slot]; }
@@ -209,18 +200,9 @@ __global__ __launch_bounds__(kThreads) void k_plane_score(PlaneArgs a)
 	if (count != 0) { atomicAdd(&a.counts[slot], count); }
 }
 
-// the key of every valid slot, the maximum of a wave by shuffles, one 64-bit integer atomic a wave; the counts are left zero
 __global__ __launch_bounds__(kThreads) void k_plane_keys(PlaneArgs a, int64_t first)
 {
-	const int          t   = blockIdx.x * kThreads + threadIdx.x;
-	const uint32_t     h   = static_cast<uint32_t>(first + t);
-	unsigned long long key = a.valid[t] ? (static_cast<unsigned long long>(a.counts[t]) << 32) | (0xFFFFFFFFu - h) : 0ull;
-	a.counts[t]            = 0;
-	for (int o = 32; o > 0; o >>= 1) {
-		const unsigned long long other = __shfl_xor(key, o, 64);
-		key                            = other > key ? other : key;
-	}
-	if ((threadIdx.x & 63) == 0 && key != 0) { atomicMax(&a.state->best, key); }
+	consensus::keep_best(blockIdx.x * kThreads + threadIdx.x, first, a.valid, a.counts, &a.state->head);
 }
 
 // the winner becomes the current model: the same function of (seed, h, candidates), so the same bits
@@ -229,7 +211,7 @@ __global__ __launch_bounds__(64) void k_plane_pick(PlaneArgs a, uint64_t h)
 {
 	if (threadIdx.x != 0) { return; }
 	double n[D], d = 0.0;
-	hypothesis<D>(a, h, a.state->m, n, d);
+	hypothesis<D>(a, h, a.state->head.live, n, d);
 #pragma unroll
 	for (int x = 0; x < D; ++x) { a.state->n[x] = n[x]; }
 	a.state->d = d;
@@ -253,7 +235,7 @@ __global__ __launch_bounds__(kThreads) void k_plane_flags(PlaneArgs a, int again
 template <int D, int PASS>
 constexpr int sums_of() { return PASS == 0 ? D : PASS == 1 ? D * (D + 1) / 2 : 1; }
 
-// one workgroup per chunk of 256 consecutive members: s[t] += s[t + w], w = 128 .. 1; the tail adds 0.0
+// one workgroup per chunk of 256 consecutive members: the block tree of their terms; the tail adds 0.0
 template <int D, int PASS>
 __global__ __launch_bounds__(kChunk) void k_plane_chunks(PlaneArgs a)
 {
@@ -291,21 +273,11 @@ __global__ __launch_bounds__(kChunk) void k_plane_chunks(PlaneArgs a)
 			v[0]           = e * e;
 		}
 	}
-#pragma unroll
-	for (int k = 0; k < K; ++k) { s[k][t] = v[k]; }
-	__syncthreads();
-	for (int w = kChunk / 2; w > 0; w >>= 1) {
-		if (t < w) {
-#pragma unroll
-			for (int k = 0; k < K; ++k) { s[k][t] = s[k][t] + s[k][t + w]; }
-		}
-		__syncthreads();
-	}
+	treesum::block_tree<K>(v, s);
 	if (t < K) { a.partial[static_cast<int64_t>(blockIdx.x) * kMaxK + t] = s[t][0]; }
 }
 
-// one wave: the chunk sums added in ascending order from 0.0 (64 chunks a load, handed to every lane in turn); then the
-// centroid (PASS 0), the refitted model (PASS 1) or the result (PASS 2)
+// one wave: the chunk sums in ascending order; then the centroid (PASS 0), the refitted model (PASS 1) or the result (PASS 2)
 template <int D, int PASS>
 __global__ __launch_bounds__(64) void k_plane_finish(PlaneArgs a)
 {
@@ -320,19 +292,7 @@ __global__ __launch_bounds__(64) void k_plane_finish(PlaneArgs a)
 	}
 	const int64_t nb = (count + kChunk - 1) / kChunk;
 	double        total[K];
-#pragma unroll
-	for (int k = 0; k < K; ++k) { total[k] = 0.0; }
-	for (int64_t b0 = 0; b0 < nb; b0 += 64) {
-		const bool have = b0 + lane < nb;
-		double     v[K];
-#pragma unroll
-		for (int k = 0; k < K; ++k) { v[k] = have ? a.partial[(b0 + lane) * kMaxK + k] : 0.0; }
-		const int e = nb - b0 < 64 ? static_cast<int>(nb - b0) : 64;
-		for (int l = 0; l < e; ++l) {
-#pragma unroll
-			for (int k = 0; k < K; ++k) { total[k] = total[k] + __shfl(v[k], l, 64); }
-		}
-	}
+	treesum::ordered_sum<K>(a.partial, kMaxK, nb, lane, total);
 	if (lane != 0) { return; }
 	if constexpr (PASS == 0) {
 #pragma unroll
@@ -411,46 +371,8 @@ __global__ __launch_bounds__(kThreads) void k_plane_label(int64_t n, const unsig
 
 // ---- the host side ------------------------------------------------------------------------------------------------------
 
-using namespace prim;  // Arena, Scratch, arena_alloc, select_indices, grid
+using namespace prim;  // Arena, Scratch, arena_alloc, select_marked, grid
 static_assert(kThreads == kGridThreads, "grid() counts work groups of kThreads");
-
-struct Marked {
-	const unsigned char* f;
-	__device__ bool      operator()(uint32_t i) const { return f[i] != 0; }
-};
-
-size_t select_bytes(int64_t n)
-{
-	size_t tb = 0;
-	FI_HIP_TRY(select_indices(nullptr, tb, static_cast<uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), static_cast<size_t>(n), Marked{nullptr},
-	                          nullptr));
-	return tb;
-}
-
-// out = the indices i < n with f[i] != 0, ascending; *count = how many
-void select_marked(const unsigned char* f, uint32_t* out, uint32_t* count, int64_t n, const Scratch& tmp, hipStream_t st)
-{
-	size_t tb = 0;
-	FI_HIP_TRY(select_indices(nullptr, tb, out, count, static_cast<size_t>(n), Marked{f}, st));
-	DevBuf more;  // (should the library want more than the sizing pass asked about)
-	if (tb > tmp.bytes) { more.alloc(tb); }
-	FI_HIP_TRY(select_indices(more.p ? more.p : tmp.p, tb, out, count, static_cast<size_t>(n), Marked{f}, st));
-}
-
-// the stop rule: r = (1 - w^D)^T by binary exponentiation from the low bit, w = b / m; add, multiply and compare only
-bool confident(long long b, long long m, long long T, int D, double confidence)
-{
-	const double w = static_cast<double>(b) / static_cast<double>(m);
-	double       p = w * w;
-	if (D == 3) { p = p * w; }
-	const double q = 1.0 - p;
-	double       r = 1.0, base = q;
-	for (unsigned long long e = static_cast<unsigned long long>(T); e; e >>= 1) {
-		if (e & 1) { r = r * base; }
-		base = base * base;
-	}
-	return r <= 1.0 - confidence;
-}
 
 // a call's temporaries; with host buffers also the staged inputs
 struct PlaneWork {
@@ -473,7 +395,7 @@ void lay_out(PlaneWork& w, DevBuf& block, int64_t n, const float* positions, con
 	arena_alloc(block, [&](Arena& ar) {
 		w.a.state   = ar.take<PlaneState>(1);
 		w.a.hyp     = ar.take<double>(4 * kBatch);
-		w.a.valid   = ar.take<uint32_t>(kBatch);
+		w.a.valid   = ar.take<unsigned char>(kBatch);
 		w.a.counts  = ar.take<uint32_t>(kBatch);
 		w.a.partial = ar.take<double>(chunks * kMaxK);
 		w.cflag     = ar.take<unsigned char>(n);
@@ -521,35 +443,21 @@ void fit_one(PlaneWork& w, const fi_plane_options& opt, uint64_t seed, const int
 	FI_HIP_TRY(hipMemsetAsync(a.state, 0, sizeof(PlaneState), st));
 	hipLaunchKernelGGL(k_plane_cand<D>, grid(n), dim3(kThreads), 0, st, n, a.pos, w.mask, labels, w.cflag);
 	FI_HIP_TRY(hipGetLastError());
-	select_marked(w.cflag, w.cand, &a.state->m, n, w.tmp, st);
+	select_marked(w.cflag, w.cand, &a.state->head.live, n, w.tmp, st);
 
 	const unsigned tiles = static_cast<unsigned>(std::min<int64_t>((n + kTile - 1) / kTile, kMaxTile));
-	struct {
-		unsigned long long best;
-		uint32_t           m, count;
-	} seen{};
-	long long T = 0;
-	for (int64_t first = 0; first < opt.max_trials; first += kBatch) {
-		const int count = static_cast<int>(std::min<int64_t>(kBatch, opt.max_trials - first));
+	const consensus::Trials ran = consensus::run_batches(&a.state->head, D, kBatch, opt.max_trials, opt.confidence, st, [&](int64_t first, int count) {
 		hipLaunchKernelGGL(k_plane_models<D>, dim3(kBatch / kThreads), dim3(kThreads), 0, st, a, first, count);
 		hipLaunchKernelGGL(k_plane_score<D>, dim3(tiles, (count + kThreads - 1) / kThreads), dim3(kThreads), 0, st, a);
 		hipLaunchKernelGGL(k_plane_keys, dim3(kBatch / kThreads), dim3(kThreads), 0, st, a, first);
-		FI_HIP_TRY(hipGetLastError());
-		FI_HIP_TRY(hipMemcpyAsync(&seen, a.state, sizeof(seen), hipMemcpyDeviceToHost, st));
-		FI_HIP_TRY(hipStreamSynchronize(st));
-		if (seen.m < static_cast<uint32_t>(D)) { break; }  // trials = 0
-		T                 = first + count;
-		const long long b = static_cast<long long>(seen.best >> 32);
-		if (b > 0 && opt.confidence > 0.0 && confident(b, seen.m, T, D, opt.confidence)) { break; }
-	}
-	model->candidates = static_cast<long>(seen.m);
-	model->trials     = static_cast<long>(T);
-	if (seen.best == 0) {
+	});
+	model->candidates = static_cast<long>(ran.seen.live);
+	model->trials     = static_cast<long>(ran.T);
+	if (ran.seen.best == 0) {
 		FI_HIP_TRY(hipMemsetAsync(a.flag, 0, n, st));
 		return;
 	}
-	const uint64_t h = 0xFFFFFFFFu - static_cast<uint32_t>(seen.best & 0xFFFFFFFFull);
-	hipLaunchKernelGGL(k_plane_pick<D>, dim3(1), dim3(64), 0, st, a, h);
+	hipLaunchKernelGGL(k_plane_pick<D>, dim3(1), dim3(64), 0, st, a, consensus::winner_of(ran.seen.best));
 	const dim3 chunks(static_cast<unsigned>((n + kChunk - 1) / kChunk));
 	for (int round = 0; round <= opt.refine; ++round) {
 		hipLaunchKernelGGL(k_plane_flags<D>, grid(n), dim3(kThreads), 0, st, a, round > 0 ? 1 : 0);
@@ -568,8 +476,8 @@ void fit_one(PlaneWork& w, const fi_plane_options& opt, uint64_t seed, const int
 	FI_HIP_TRY(hipMemcpyAsync(&got, a.state, sizeof(got), hipMemcpyDeviceToHost, st));
 	FI_HIP_TRY(hipStreamSynchronize(st));
 	*model            = got.out;
-	model->candidates = static_cast<long>(seen.m);
-	model->trials     = static_cast<long>(T);
+	model->candidates = static_cast<long>(ran.seen.live);
+	model->trials     = static_cast<long>(ran.T);
 }
 
 template <int D>

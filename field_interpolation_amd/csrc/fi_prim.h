@@ -1,7 +1,7 @@
 // fi_prim.h -- the device-wide primitives of the assembly (scans, run-length encoding, selection, 64-bit
 // pair sorts) straight on rocPRIM, ROCm's own primitive library (rounds 1-4 went through hipCUB, the CUB-shaped layer over
 // it).  Same call shape as the library's: a first call with a null workspace returns the bytes it wants.  Below them the
-// host side the mesh units share: a call's temporaries as pieces of one block, the size-then-run pairs around the sorts and scans.
+// host side the units share: a call's temporaries as pieces of one block, the size-then-run pairs (sorts, scans, selections).
 #pragma once
 
 #include <cstring>
@@ -81,6 +81,18 @@ inline void arena_alloc(DevBuf& block, F&& lay_out)
 	lay_out(arena);
 }
 
+// the run of a size-then-run pair: call(workspace, bytes) is asked with a null workspace, then run in tmp -- or in a block of
+// its own, should the library want more for fewer items or bits than the sizing pass asked about
+template <class Call>
+inline void run_in(const Scratch& tmp, Call&& call)
+{
+	size_t tb = 0;
+	FI_HIP_TRY(call(nullptr, tb));
+	DevBuf more;
+	if (tb > tmp.bytes) { more.alloc(tb); }
+	FI_HIP_TRY(call(more.p ? more.p : tmp.p, tb));
+}
+
 template <typename Out = uint32_t>
 inline size_t scan_bytes(int64_t n)
 {
@@ -93,11 +105,7 @@ inline size_t scan_bytes(int64_t n)
 template <typename Out>
 inline void scan_u32(const uint32_t* in, Out* out, int64_t n, const Scratch& tmp, hipStream_t st)
 {
-	size_t tb = 0;
-	FI_HIP_TRY(exclusive_sum(nullptr, tb, in, out, static_cast<size_t>(n), st));
-	DevBuf more;  // (should the library want more for fewer items or bits than the sizing pass asked about)
-	if (tb > tmp.bytes) { more.alloc(tb); }
-	FI_HIP_TRY(exclusive_sum(more.p ? more.p : tmp.p, tb, in, out, static_cast<size_t>(n), st));
+	run_in(tmp, [&](void* p, size_t& tb) { return exclusive_sum(p, tb, in, out, static_cast<size_t>(n), st); });
 }
 
 // the same scan of n uint64 (fi_meshpts.hip's integer weights reach 2^32: one bit more than a uint32 holds)
@@ -110,11 +118,7 @@ inline size_t scan_u64_bytes(int64_t n)
 
 inline void scan_u64(const uint64_t* in, uint64_t* out, int64_t n, const Scratch& tmp, hipStream_t st)
 {
-	size_t tb = 0;
-	FI_HIP_TRY(exclusive_sum(nullptr, tb, in, out, static_cast<size_t>(n), st));
-	DevBuf more;
-	if (tb > tmp.bytes) { more.alloc(tb); }
-	FI_HIP_TRY(exclusive_sum(more.p ? more.p : tmp.p, tb, in, out, static_cast<size_t>(n), st));
+	run_in(tmp, [&](void* p, size_t& tb) { return exclusive_sum(p, tb, in, out, static_cast<size_t>(n), st); });
 }
 
 template <typename V = uint32_t>
@@ -131,11 +135,7 @@ template <typename V>
 inline void sort_u64(const uint64_t* kin, uint64_t* kout, const V* vin, V* vout, int64_t n, int begin_bit, int end_bit, const Scratch& tmp,
                      hipStream_t st)
 {
-	size_t tb = 0;
-	FI_HIP_TRY(sort_pairs_u64(nullptr, tb, kin, kout, vin, vout, static_cast<size_t>(n), begin_bit, end_bit, st));
-	DevBuf more;
-	if (tb > tmp.bytes) { more.alloc(tb); }
-	FI_HIP_TRY(sort_pairs_u64(more.p ? more.p : tmp.p, tb, kin, kout, vin, vout, static_cast<size_t>(n), begin_bit, end_bit, st));
+	run_in(tmp, [&](void* p, size_t& tb) { return sort_pairs_u64(p, tb, kin, kout, vin, vout, static_cast<size_t>(n), begin_bit, end_bit, st); });
 }
 
 inline size_t sort_keys_bytes(int64_t n, int begin_bit, int end_bit)
@@ -149,11 +149,27 @@ inline size_t sort_keys_bytes(int64_t n, int begin_bit, int end_bit)
 // kout = the keys kin in ascending order of bits [begin_bit, end_bit)
 inline void sort_keys(const uint64_t* kin, uint64_t* kout, int64_t n, int begin_bit, int end_bit, const Scratch& tmp, hipStream_t st)
 {
+	run_in(tmp, [&](void* p, size_t& tb) { return sort_keys_u64(p, tb, kin, kout, static_cast<size_t>(n), begin_bit, end_bit, st); });
+}
+
+// a selection by flags: the predicate of select_indices over uint8 marks
+struct Marked {
+	const unsigned char* f;
+	__device__ bool      operator()(uint32_t i) const { return f[i] != 0; }
+};
+
+inline size_t select_bytes(int64_t n)
+{
 	size_t tb = 0;
-	FI_HIP_TRY(sort_keys_u64(nullptr, tb, kin, kout, static_cast<size_t>(n), begin_bit, end_bit, st));
-	DevBuf more;
-	if (tb > tmp.bytes) { more.alloc(tb); }
-	FI_HIP_TRY(sort_keys_u64(more.p ? more.p : tmp.p, tb, kin, kout, static_cast<size_t>(n), begin_bit, end_bit, st));
+	FI_HIP_TRY(select_indices(nullptr, tb, static_cast<uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), static_cast<size_t>(n), Marked{nullptr},
+	                          nullptr));
+	return tb;
+}
+
+// out = the indices i < n with f[i] != 0, ascending; *count = how many
+inline void select_marked(const unsigned char* f, uint32_t* out, uint32_t* count, int64_t n, const Scratch& tmp, hipStream_t st)
+{
+	run_in(tmp, [&](void* p, size_t& tb) { return select_indices(p, tb, out, count, static_cast<size_t>(n), Marked{f}, st); });
 }
 
 inline uint32_t read_u32(const uint32_t* dev, hipStream_t st)

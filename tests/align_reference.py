@@ -6,6 +6,7 @@ device must produce.  Only numpy and meshpts_reference.uniform / tree_sum."""
 import numpy as np
 
 from meshpts_reference import tree_sum, uniform
+from plane_reference import confident as plane_confident
 
 BATCH = 16384
 SLICE = 256          # hypotheses scored at a time (memory only)
@@ -110,17 +111,8 @@ def scores(X, Y, R, t, valid, threshold):
 
 
 def confident(b, live, T, confidence):
-    """the stop rule: (1 - w^3)^T <= 1 - confidence by binary exponentiation from the low bit; add, multiply, compare only"""
-    w = np.float64(b) / np.float64(live)
-    p = (w * w) * w
-    q = np.float64(1.0) - p
-    r, base, e = np.float64(1.0), q, int(T)
-    while e:
-        if e & 1:
-            r = r * base
-        base = base * base
-        e >>= 1
-    return bool(r <= np.float64(1.0) - np.float64(confidence))
+    """the stop rule (1 - w^3)^T <= 1 - confidence: plane_reference's, for samples of three"""
+    return plane_confident(b, live, T, 3, confidence)
 
 
 def align(source, target, src_index, tgt_index, threshold, similarity=0.9, max_trials=100000, confidence=0.999, seed=0):

@@ -22,7 +22,8 @@ from test_align_reference import lattice_pairs, moved_exactly
 pytestmark = pytest.mark.gpu
 
 COUNTS = [0, 2, 3, 255, 256, 257, 1000]                  # both sides of a tile and a chunk (256); four of them
-TRIALS = [1, 16383, 16384, 16385, 40000]                 # both sides of a batch (16384), two batches and a partial one
+MANY = [16384, 16385]                                    # all inliers: 64 chunks, one load of the ordered sum, and a 65th
+TRIALS = [1, 16383, 16384, 16385, 40000]                # both sides of a batch (16384), two batches and a partial one
 INTS = ("found", "pairs", "live", "trials", "valid", "inliers")
 
 
@@ -78,7 +79,7 @@ def _check(fi, src, tgt, si, ti, what="", **kw):
 @pytest.mark.parametrize("share", [0.1, 1.0])
 @pytest.mark.parametrize("similarity", [0.0, 0.9])
 def test_sizes(fi, similarity, share):
-    for m in COUNTS:
+    for m in COUNTS + (MANY if share == 1.0 else []):
         src, tgt, _, _ = AR.moved_pairs(10 + m, m, share)
         idx = np.arange(m)
         want, _ = _check(fi, src, tgt, idx, idx, (m, similarity, share), threshold=0.05, similarity=similarity, max_trials=3000,
@@ -86,6 +87,8 @@ def test_sizes(fi, similarity, share):
         assert want["trials"] == (3000 if m >= 3 else 0)
         if m >= 255 and share == 1.0:
             assert want["found"] == 1 and want["inliers"] > 0.5 * m
+        if m in MANY:
+            assert want["inliers"] == m
 
 
 @pytest.mark.parametrize("confidence", [0.0, 0.999])

@@ -119,6 +119,21 @@ def test_leaf_and_block_edges(fi, n):
     _check_counts(index, pos, np.concatenate([pos, _queries(rng, sizes, 50)]), 3, 4.0)
 
 
+@pytest.mark.parametrize("n", [64 * 256, 64 * 256 + 1])
+def test_more_blocks_than_one_load_of_the_ordered_sum(fi, n):
+    """64 blocks of the fixed-order sum, one load of the wave that adds them, and a 65th.  The restatement's table of all pairs
+    is too slow here; the means come from neighbour_distances, which the other tests hold to it"""
+    rng = np.random.default_rng(n)
+    pos = rng.uniform(0.0, 1000.0, size=(n, 1)).astype(np.float32)
+    index = fi.PointIndex(pos, ndim=1)
+    mean = index.neighbour_distances(4)[0]
+    wkeep, wstats = CR.statistics(mean, 1.0)
+    keep, stats = index.statistical_outliers(4, 1.0)
+    _same_int(keep, wkeep.astype(bool), np.bool_)
+    _same_stats(stats, wstats)
+    assert stats["counted"] == n
+
+
 def test_more_neighbours_asked_than_points_exist(fi):
     sizes = [20, 18, 16]
     rng = np.random.default_rng(6)

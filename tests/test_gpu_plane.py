@@ -20,7 +20,8 @@ from test_plane_reference import cube_faces, grid_plane, off_points
 pytestmark = pytest.mark.gpu
 
 COUNTS = [2, 3, 63, 64, 65, 255, 256, 257, 1000, 4099]     # both sides of a wave (64), of a tile and a chunk (256); 17 chunks
-TRIALS = [1, 1023, 1024, 1025, 3000]                        # both sides of a batch (1024), two batches and a partial one
+MANY = [16384, 16385]                                       # all inliers: 64 chunks, one load of the ordered sum, and a 65th
+TRIALS = [1, 1023, 1024, 1025, 3000]                       # both sides of a batch (1024), two batches and a partial one
 SHARES = [0.1, 0.5, 1.0]
 INTS = ("found", "refits", "inliers", "candidates", "trials")
 
@@ -103,10 +104,14 @@ def _check_segment(fi, P, max_planes, what="", mask=None, max_angle=None, **kw):
 @pytest.mark.parametrize("share", SHARES)
 @pytest.mark.parametrize("D", [2, 3])
 def test_sizes(fi, D, share):
-    for n in COUNTS:
+    for n in COUNTS + (MANY if share == 1.0 else []):
         P = PR.plane_cloud(100 * D + n, n, share, D)
         want, _ = _check_fit(fi, P, (D, n, share), threshold=0.1, max_trials=1025, refine=1, seed=n)
         assert want["found"] == (1 if n >= D else 0)
+        if n == 16384:
+            assert want["inliers"] == 64 * 256
+        if n == 16385:
+            assert want["inliers"] > 64 * 256
 
 
 @pytest.mark.parametrize("confidence", [0.0, 0.999])
