@@ -25,6 +25,7 @@
 //              sum; then the rms, the result).
 // One device allocation (fi_arena.h) a call; one read-back a batch and one for the result.
 #include "fi_solver_internal.h"
+#include "fi_stage.h"
 #include "fi_align.h"
 #include "fi_consensus.h"
 #include "fi_prim.h"
@@ -333,47 +334,33 @@ void align_correspondences(int64_t n_s, const float* source, int64_t n_t, const 
 	identity(out, m);
 	if (m == 0) { return; }
 	hipStream_t   st      = nullptr;
-	const bool    host    = memory == FI_HOST;
-	const bool    to_host = inliers && host;
 	const int64_t chunks  = (m + kChunk - 1) / kChunk;
 	AlignArgs     a{};
 	DevBuf        block;
 	Scratch       tmp;
 	unsigned char* lflag  = nullptr;
 	uint32_t *     pair = nullptr, *member = nullptr, *slot = nullptr;
-	float *        src = nullptr, *tgt = nullptr;
-	long long *    si = nullptr, *ti = nullptr;
 	tmp.bytes = std::max(select_bytes(m), select_bytes(kBatch));
-	arena_alloc(block, [&](Arena& ar) {
+	arena_alloc(block, [&](Arena& ar) {  // (an empty set is not uploaded)
 		a.state   = ar.take<AlignState>(1);
 		a.hyp     = ar.take<double>(12 * kBatch);
 		a.partial = ar.take<double>(chunks);
-		si        = host ? ar.take<long long>(m) : const_cast<long long*>(src_index);
-		ti        = host ? ar.take<long long>(m) : const_cast<long long*>(tgt_index);
+		a.si      = stage::in(ar, src_index, m, memory, st);
+		a.ti      = stage::in(ar, tgt_index, m, memory, st);
 		a.counts  = ar.take<uint32_t>(kBatch);
 		slot      = ar.take<uint32_t>(kBatch);
 		pair      = ar.take<uint32_t>(m);
 		member    = ar.take<uint32_t>(m);
-		src       = host ? ar.take<float>(n_s * 3) : const_cast<float*>(source);
-		tgt       = host ? ar.take<float>(n_t * 3) : const_cast<float*>(target);
+		a.src     = stage::in(ar, source, n_s * 3, memory, st);
+		a.tgt     = stage::in(ar, target, n_t * 3, memory, st);
 		a.vflag   = ar.take<unsigned char>(kBatch);
 		lflag     = ar.take<unsigned char>(m);
-		a.flag    = inliers && !to_host ? inliers : ar.take<unsigned char>(m);
+		a.flag    = stage::work(ar, inliers, m, memory);
 		tmp.p     = ar.take<char>(static_cast<int64_t>(tmp.bytes));
 	});
-	if (host) {
-		if (n_s > 0) { FI_HIP_TRY(hipMemcpyAsync(src, source, sizeof(float) * 3 * n_s, hipMemcpyHostToDevice, st)); }
-		if (n_t > 0) { FI_HIP_TRY(hipMemcpyAsync(tgt, target, sizeof(float) * 3 * n_t, hipMemcpyHostToDevice, st)); }
-		FI_HIP_TRY(hipMemcpyAsync(si, src_index, sizeof(long long) * m, hipMemcpyHostToDevice, st));
-		FI_HIP_TRY(hipMemcpyAsync(ti, tgt_index, sizeof(long long) * m, hipMemcpyHostToDevice, st));
-	}
 	FI_HIP_TRY(hipMemsetAsync(a.counts, 0, sizeof(uint32_t) * kBatch, st));
 	FI_HIP_TRY(hipMemsetAsync(a.state, 0, sizeof(AlignState), st));
 	a.m      = m;
-	a.src    = src;
-	a.tgt    = tgt;
-	a.si     = si;
-	a.ti     = ti;
 	a.lflag  = lflag;
 	a.pair   = pair;
 	a.member = member;
@@ -383,7 +370,7 @@ void align_correspondences(int64_t n_s, const float* source, int64_t n_t, const 
 	a.sim2   = sim * sim;
 	a.thr2   = thr * thr;
 
-	hipLaunchKernelGGL(k_align_live, grid(m), dim3(kThreads), 0, st, m, n_s, n_t, src, tgt, si, ti, lflag);
+	hipLaunchKernelGGL(k_align_live, grid(m), dim3(kThreads), 0, st, m, n_s, n_t, a.src, a.tgt, a.si, a.ti, lflag);
 	FI_HIP_TRY(hipGetLastError());
 	select_marked(lflag, pair, &a.state->head.live, m, tmp, st);
 
@@ -400,7 +387,7 @@ void align_correspondences(int64_t n_s, const float* source, int64_t n_t, const 
 	out->valid  = static_cast<long>(ran.spare);
 	if (ran.seen.best == 0) {
 		if (inliers) {
-			if (to_host) {
+			if (stage::staged(memory)) {
 				std::fill(inliers, inliers + m, static_cast<unsigned char>(0));
 			} else {
 				FI_HIP_TRY(hipMemsetAsync(inliers, 0, m, st));
@@ -418,7 +405,7 @@ void align_correspondences(int64_t n_s, const float* source, int64_t n_t, const 
 	FI_HIP_TRY(hipGetLastError());
 	AlignState got{};
 	FI_HIP_TRY(hipMemcpyAsync(&got, a.state, sizeof(got), hipMemcpyDeviceToHost, st));
-	if (to_host) { FI_HIP_TRY(hipMemcpyAsync(inliers, a.flag, m, hipMemcpyDeviceToHost, st)); }
+	stage::back(inliers, a.flag, m, memory, st);
 	FI_HIP_TRY(hipStreamSynchronize(st));
 	*out        = got.out;
 	out->pairs  = static_cast<long>(m);

@@ -19,6 +19,7 @@
 
 #include "fi_solver_internal.h"
 #include "fi_prim.h"
+#include "fi_stage.h"
 
 #include <cmath>
 
@@ -426,50 +427,21 @@ __device__ inline float distance_of(bool finite, float best, float lim, uint32_t
 
 __device__ inline long long index_of(uint32_t bidx) { return bidx == kNone ? -1LL : static_cast<long long>(bidx); }
 
-// n queries of D floats in `memory` on the device: the caller's, or a copy in bq
-inline const float* stage_queries(const float* queries, int64_t n, int D, int memory, DevBuf& bq, hipStream_t st)
-{
-	if (memory != FI_HOST) { return queries; }
-	bq.alloc(sizeof(float) * D * n);
-	FI_HIP_TRY(hipMemcpyAsync(bq.p, queries, sizeof(float) * D * n, hipMemcpyHostToDevice, st));
-	return bq.as<float>();
-}
-
-// outputs of a call on the device: the caller's (FI_DEVICE) or staged (FI_HOST), copied back by finish(); indices and
-// closest (n x D) may be null
+// the three outputs of a query on the device (fi_stage.h): the caller's or staged, copied back by finish(), which also ends
+// the call; indices and closest (n x D) may be null
 struct Outputs {
-	int64_t    n;
-	int        D, memory;
-	float*     dist;
-	long long* idx;
-	float*     cl;
-	float*     host_dist;
-	long long* host_idx;
-	float*     host_cl;
-	DevBuf     bd, bi, bc;
-	Outputs(int64_t count, int ndim, float* distances, long long* indices, float* closest, int mem)
-	    : n(count), D(ndim), memory(mem), dist(distances), idx(indices), cl(closest), host_dist(distances), host_idx(indices),
-	      host_cl(closest)
+	stage::Out<float>     dist;
+	stage::Out<long long> idx;
+	stage::Out<float>     cl;
+	Outputs(int64_t n, int D, float* distances, long long* indices, float* closest, int memory)
+	    : dist(distances, n, memory), idx(indices, n, memory), cl(closest, D * n, memory)
 	{
-		if (memory == FI_DEVICE) { return; }
-		bd.alloc(sizeof(float) * n);
-		dist = bd.as<float>();
-		if (indices) {
-			bi.alloc(sizeof(long long) * n);
-			idx = bi.as<long long>();
-		}
-		if (closest) {
-			bc.alloc(sizeof(float) * D * n);
-			cl = bc.as<float>();
-		}
 	}
 	void finish(hipStream_t st)
 	{
-		if (memory == FI_HOST) {
-			FI_HIP_TRY(hipMemcpyAsync(host_dist, dist, sizeof(float) * n, hipMemcpyDeviceToHost, st));
-			if (idx) { FI_HIP_TRY(hipMemcpyAsync(host_idx, idx, sizeof(long long) * n, hipMemcpyDeviceToHost, st)); }
-			if (cl) { FI_HIP_TRY(hipMemcpyAsync(host_cl, cl, sizeof(float) * D * n, hipMemcpyDeviceToHost, st)); }
-		}
+		dist.back(st);
+		idx.back(st);
+		cl.back(st);
 		FI_HIP_TRY(hipStreamSynchronize(st));
 	}
 };

@@ -1,6 +1,7 @@
 // fi_capi.hip -- the C ABI of include/fi_hip.h (every entry point cites the reference interface it replaces there): contexts,
 // model, points, assemble, the solver entry points and their options, statistics.  Nothing throws or aborts across it.
 #include "fi_solver_internal.h"
+#include "fi_stage.h"
 #include "fi_workers.h"
 #include "fi_iso.h"
 #include "fi_dual.h"
@@ -97,16 +98,6 @@ int64_t lattice_points(int ndim, const int* sizes)
 		n *= sizes[d];
 	}
 	return n;
-}
-
-// n elements in `memory` on the device: the caller's, or a copy of the host array in buf
-template <typename T>
-const T* on_device(const T* src, int64_t n, int memory, DevBuf& buf)
-{
-	if (memory != FI_HOST) { return src; }
-	buf.alloc(sizeof(T) * n);
-	FI_HIP_TRY(hipMemcpy(buf.p, src, sizeof(T) * n, hipMemcpyHostToDevice));
-	return buf.as<T>();
 }
 
 // fi_mesh_destroy / fi_points_destroy / fi_surface_destroy: the object's buffers go back on the device it lives on
@@ -369,7 +360,7 @@ int fi_add_points(fi_ctx* c, long n, const float* positions, const float* normal
 		           gradient_kernel);  // ABORT_F, cpp:238
 // (GradientKernel::kLinearInterpolation over slabs: its rows are kept as triplets with local columns, fi_generic.hip)
 	}
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	const int D = c->g.ndim;
 	fi::DevBuf dpos, dnrm, dpw, dval;
 	const float *p = positions, *g = normals, *w = point_weights, *v = values;
@@ -473,7 +464,7 @@ int fi_add_rows_coo(fi_ctx* c, long nrows, long ntriplets, const fi_triplet* tri
 	fi::check_ctx(c);
 	fi::bind_device(c);
 	FI_REQUIRE(nrows >= 0 && ntriplets >= 0, FI_ERR_INVALID, "negative count");
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	FI_REQUIRE(c->nranks == 1, FI_ERR_UNSUPPORTED, "generic rows need an undivided lattice");
 	FI_REQUIRE((ntriplets == 0 || triplets) && (nrows == 0 || rhs), FI_ERR_INVALID, "null buffer");
 	fi::generic_add_coo(c, nrows, ntriplets, triplets, rhs, memory);
@@ -800,7 +791,7 @@ int fi_solve_cg(fi_ctx* c, const float* guess, int max_iterations, float tol, fl
 	FI_API_BEGIN
 	fi::check_assembled(c);
 	fi::bind_device(c);
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	fi::AllocStream alloc_on(c->stream);  // (every level of a hierarchy solves on the finest level's stream)
 	if (c->dtype == FI_F64) {
 		fi::solve_cg_t<double>(c, guess, max_iterations, tol, out, iterations, rel_residual, memory);
@@ -883,7 +874,7 @@ int fi_jacobi(fi_ctx* c, const float* guess, int num_iterations, float weight, f
 	FI_API_BEGIN
 	fi::check_assembled(c);
 	fi::bind_device(c);
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	if (num_iterations < 0) { num_iterations = 0; }  // sparse_linear.cpp:220: returns the guess
 	if (c->dtype == FI_F64) {
 		fi::jacobi_t<double>(c, guess, num_iterations, weight, out, memory);
@@ -898,7 +889,7 @@ int fi_error_map(fi_ctx* c, const float* solution, float* out, int memory)
 	FI_API_BEGIN
 	fi::check_assembled(c);
 	fi::bind_device(c);
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	FI_REQUIRE(solution && out, FI_ERR_INVALID, "fi_error_map needs a solution and an output buffer");
 	fi::ensure_vectors(c);
 	fi::RankSet R{c};
@@ -931,7 +922,7 @@ int fi_point_residuals(fi_ctx* c, const float* field, float* residuals, int memo
 	FI_API_BEGIN
 	fi::check_ctx(c);
 	fi::bind_device(c);
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	fi::robust_residuals(c, field, residuals, memory);
 	FI_API_END
 }
@@ -942,7 +933,7 @@ int fi_robust_reweight(fi_ctx* c, const float* field, const fi_robust_options* o
 	fi::check_ctx(c);
 	fi::bind_device(c);
 	FI_REQUIRE(options != nullptr, FI_ERR_INVALID, "options is null");
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	const fi::RobustStep step = fi::robust_reweight(c, field, options->loss, options->tuning, options->scale, omega, memory);
 	if (scale) { *scale = step.scale; }
 	FI_API_END
@@ -964,7 +955,7 @@ int fi_solve_robust(fi_ctx* c, const float* guess, const fi_robust_options* opti
 	fi::check_ctx(c);
 	fi::bind_device(c);
 	FI_REQUIRE(options != nullptr, FI_ERR_INVALID, "options is null");
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	FI_REQUIRE(options->rounds >= 0, FI_ERR_INVALID, "rounds = %d", options->rounds);
 	FI_REQUIRE(options->weight_tolerance >= 0.0f, FI_ERR_INVALID, "weight_tolerance must be >= 0");
 	const long n = fi::robust_check(c);  // (every refusal before any work)
@@ -1022,7 +1013,7 @@ int fi_tile_pass(fi_ctx* c, const float* guess, int tile_size, float* out, int m
 	FI_API_BEGIN
 	fi::check_assembled(c);
 	fi::bind_device(c);
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	FI_REQUIRE(tile_size >= 2, FI_ERR_INVALID, "tile_size %d < 2 (sparse_linear.cpp:254)", tile_size);
 	FI_REQUIRE(guess && out, FI_ERR_INVALID, "fi_tile_pass needs a guess and an output buffer");
 	FI_REQUIRE(c->nranks == 1 || c->generic.ntrip == 0, FI_ERR_UNSUPPORTED, "the tile pre-solver over triplet rows needs an undivided lattice");
@@ -1152,7 +1143,7 @@ int fi_upscale_field(const float* small_field, int ndim, const int* small_sizes,
 	FI_API_BEGIN
 	FI_REQUIRE(small_field && small_sizes && large_sizes && out, FI_ERR_INVALID, "null argument");
 	FI_REQUIRE(1 <= ndim && ndim <= FI_MAX_DIM, FI_ERR_INVALID, "ndim must be 1..3");
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	fi::UpscaleArgs a{};
 	a.ndim = ndim;
 	int64_t ns = 1, nl = 1;
@@ -1163,17 +1154,12 @@ int fi_upscale_field(const float* small_field, int ndim, const int* small_sizes,
 		ns *= small_sizes[d];
 		nl *= large_sizes[d];
 	}
-	fi::DevBuf ds, dl;
-	const float* s = fi::on_device(small_field, ns, memory, ds);
-	float*       o = out;
-	if (memory == FI_HOST) {
-		dl.alloc(sizeof(float) * nl);
-		o = dl.as<float>();
-	}
-	hipLaunchKernelGGL(fi::k_upscale, dim3(fi::blocks_for(nl)), dim3(fi::kThreads), 0, nullptr, a, nl, s, o);
+	fi::stage::In<float>  s(small_field, ns, memory, nullptr);
+	fi::stage::Out<float> o(out, nl, memory);
+	hipLaunchKernelGGL(fi::k_upscale, dim3(fi::blocks_for(nl)), dim3(fi::kThreads), 0, nullptr, a, nl, s.dev, o.dev);
 	FI_HIP_TRY(hipGetLastError());
+	o.back(nullptr);
 	FI_HIP_TRY(hipDeviceSynchronize());
-	if (memory == FI_HOST) { FI_HIP_TRY(hipMemcpy(out, dl.p, sizeof(float) * nl, hipMemcpyDeviceToHost)); }
 	FI_API_END
 }
 
@@ -1194,13 +1180,12 @@ int fi_iso_extract_field(const float* field, int ndim, const int* sizes, float i
 {
 	FI_API_BEGIN
 	FI_REQUIRE(field && sizes && out, FI_ERR_INVALID, "null argument");
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	*out = nullptr;
 	FI_REQUIRE(ndim != 1, FI_ERR_UNSUPPORTED, "iso-contours of a 1-D lattice are not supported");
 	FI_REQUIRE(ndim == 2 || ndim == 3, FI_ERR_INVALID, "ndim must be 2 or 3 (got %d)", ndim);
 	const int64_t n = fi::lattice_points(ndim, sizes);
-	fi::DevBuf   df;
-	const float* f = fi::on_device(field, n, memory, df);
+	fi::stage::In<float> f(field, n, memory, nullptr);
 	fi::iso_extract_whole(f, ndim, sizes, iso, 1, nullptr, nullptr, nullptr, out);
 	FI_API_END
 }
@@ -1222,14 +1207,12 @@ int fi_dual_contour_field(const float* field, const float* gradients, int ndim, 
 {
 	FI_API_BEGIN
 	FI_REQUIRE(field && sizes && out, FI_ERR_INVALID, "null argument");
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	*out = nullptr;
 	FI_REQUIRE(ndim != 1, FI_ERR_UNSUPPORTED, "dual contouring of a 1-D lattice is not supported");
 	FI_REQUIRE(ndim == 2 || ndim == 3, FI_ERR_INVALID, "ndim must be 2 or 3 (got %d)", ndim);
 	const int64_t n = fi::lattice_points(ndim, sizes);
-	fi::DevBuf   df, dg;
-	const float* f = fi::on_device(field, n, memory, df);
-	const float* g = gradients ? fi::on_device(gradients, ndim * n, memory, dg) : nullptr;
+	fi::stage::In<float> f(field, n, memory, nullptr), g(gradients, ndim * n, memory, nullptr);
 	fi::dual_contour_whole(f, g, ndim, sizes, iso, nullptr, out);
 	FI_API_END
 }
@@ -1248,7 +1231,7 @@ int fi_mesh_copy(const fi_mesh* m, float* vertices, float* normals, int* indices
 {
 	FI_API_BEGIN
 	FI_REQUIRE(m != nullptr, FI_ERR_INVALID, "null mesh");
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	FI_HIP_TRY(hipSetDevice(m->device));
 	const hipMemcpyKind kind = memory == FI_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
 	const size_t nv = static_cast<size_t>(m->nv), np = static_cast<size_t>(m->np), D = static_cast<size_t>(m->ndim);
@@ -1377,7 +1360,7 @@ void check_nearest(long n, const float* queries, float max_distance, const float
 	FI_REQUIRE(n >= 0, FI_ERR_INVALID, "n = %ld", n);
 	FI_REQUIRE(queries != nullptr && distances != nullptr, FI_ERR_INVALID, "null queries or distances");
 	FI_REQUIRE(max_distance >= 0.0f, FI_ERR_INVALID, "max_distance must be >= 0 (got %g)", static_cast<double>(max_distance));  // (NaN fails)
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	// (one thread per query, 32-bit counts)
 	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld queries in one call", n);
 }
@@ -1386,7 +1369,7 @@ void check_field_out(float max_distance, const float* out, int memory)
 {
 	FI_REQUIRE(out != nullptr, FI_ERR_INVALID, "out is null");
 	FI_REQUIRE(max_distance >= 0.0f, FI_ERR_INVALID, "max_distance must be >= 0 (got %g)", static_cast<double>(max_distance));
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 }
 
 // the border prior's reason: a slab context holds only the points near its slab
@@ -1433,17 +1416,12 @@ int fi_points_create(fi_points** out, int ndim, long n, const float* positions, 
 	FI_REQUIRE(1 <= ndim && ndim <= FI_MAX_DIM, FI_ERR_INVALID, "ndim must be 1..%d (got %d)", FI_MAX_DIM, ndim);
 	FI_REQUIRE(n >= 0, FI_ERR_INVALID, "n = %ld", n);
 	FI_REQUIRE(n == 0 || positions != nullptr, FI_ERR_INVALID, "positions is null");
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld points: nearest-point indices are 32-bit", n);
 	std::unique_ptr<fi_points> h(new fi_points());
 	FI_HIP_TRY(hipGetDevice(&h->device));
-	fi::DevBuf   buf;
-	const float* p = positions;
-	if (n > 0 && memory == FI_HOST) {
-		buf.alloc(sizeof(float) * ndim * n);
-		FI_HIP_TRY(hipMemcpy(buf.p, positions, sizeof(float) * ndim * n, hipMemcpyHostToDevice));
-		p = buf.as<float>();
-	}
+	fi::stage::In<float> pos(n > 0 ? positions : nullptr, static_cast<int64_t>(ndim) * n, memory, nullptr);
+	const float*  p   = pos;
 	const int64_t cnt = n;
 	fi::nearest_build(h->t, ndim, cnt, &p, &cnt, 1, nullptr);
 	*out = h.release();
@@ -1489,7 +1467,7 @@ void check_normals(const fi::NearestIndex* t, int ndim, int k, float max_distanc
 	FI_REQUIRE(k >= ndim, FI_ERR_INVALID, "k = %d neighbours span no plane in %d dimensions", k, ndim);
 	FI_REQUIRE(normals != nullptr, FI_ERR_INVALID, "normals is null");
 	FI_REQUIRE(max_distance >= 0.0f, FI_ERR_INVALID, "max_distance must be >= 0 (got %g)", static_cast<double>(max_distance));
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	FI_REQUIRE(orient == FI_ORIENT_NONE || orient == FI_ORIENT_VIEWPOINTS || orient == FI_ORIENT_DIRECTIONS, FI_ERR_INVALID,
 	           "bad orientation mode %d", orient);
 	if (orient == FI_ORIENT_NONE || !t) { return; }
@@ -1554,7 +1532,7 @@ void check_radius(float radius, int least, const char* what, int memory)
 {
 	FI_REQUIRE(radius >= 0.0f, FI_ERR_INVALID, "radius must be >= 0 (got %g)", static_cast<double>(radius));  // (NaN fails)
 	FI_REQUIRE(least >= 1, FI_ERR_INVALID, "%s must be >= 1 (got %d)", what, least);
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 }
 
 void check_radius_count(long n, const float* queries, float radius, int limit, const int* counts, int memory)
@@ -1569,7 +1547,7 @@ void check_neighbours(int k, float max_distance, bool any_output, int memory)
 {
 	check_k(k);
 	FI_REQUIRE(max_distance >= 0.0f, FI_ERR_INVALID, "max_distance must be >= 0 (got %g)", static_cast<double>(max_distance));
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	FI_REQUIRE(any_output, FI_ERR_INVALID, "every output is null");
 }
 
@@ -1678,7 +1656,7 @@ int fi_cloud_thin(int ndim, long n, const float* positions, const float* normals
 	FI_REQUIRE(values != nullptr || out_values == nullptr, FI_ERR_INVALID, "out_values without values");
 	FI_REQUIRE(cell > 0.0f, FI_ERR_INVALID, "cell must be > 0 (got %g)", static_cast<double>(cell));  // (false for a NaN)
 	FI_REQUIRE(mode == FI_THIN_MEAN || mode == FI_THIN_FIRST, FI_ERR_INVALID, "bad mode %d", mode);
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld points in one call", n);
 	fi::cloud_thin(ndim, n, positions, normals, values, cell, origin, mode, out_positions, out_normals, out_values, out_counts, out_indices,
 	               cell_map, num_out, memory);
@@ -1692,7 +1670,7 @@ void check_cluster(float eps, int min_points, const int* labels, const fi_cluste
 {
 	FI_REQUIRE(eps >= 0.0f && !std::isinf(eps), FI_ERR_INVALID, "eps must be finite and >= 0 (got %g)", static_cast<double>(eps));  // (NaN fails)
 	FI_REQUIRE(min_points >= 1, FI_ERR_INVALID, "min_points must be >= 1 (got %d)", min_points);
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	FI_REQUIRE(labels || stats, FI_ERR_INVALID, "every output is null");
 }
 }  // namespace
@@ -1725,7 +1703,7 @@ int fi_cluster_measure(int ndim, long n, const float* positions, const int* labe
 	FI_REQUIRE(n >= 0 && num_clusters >= 0, FI_ERR_INVALID, "n = %ld, num_clusters = %ld", n, num_clusters);
 	FI_REQUIRE(n == 0 || (positions != nullptr && labels != nullptr), FI_ERR_INVALID, "null positions or labels");
 	FI_REQUIRE(num_clusters == 0 || rows != nullptr, FI_ERR_INVALID, "rows is null");
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	FI_REQUIRE(n < (1L << 31) && num_clusters < (1L << 31), FI_ERR_UNSUPPORTED, "%ld points, %ld clusters in one call", n, num_clusters);
 	fi::cluster_measure(ndim, n, positions, labels, core, num_clusters, rows, memory);
 	FI_API_END
@@ -1755,7 +1733,7 @@ void check_plane(int ndim, long n, const float* positions, const fi_plane_option
 		}
 		FI_REQUIRE(finite && !zero, FI_ERR_INVALID, "min_cos > 0 needs a finite axis that is not zero");
 	}
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 }
 }  // namespace
 
@@ -1803,7 +1781,7 @@ int fi_align_correspondences(long n_s, const float* source, long n_t, const floa
 	FI_REQUIRE(opt->confidence >= 0.0 && opt->confidence < 1.0, FI_ERR_INVALID, "confidence must be in [0, 1) (got %g)", opt->confidence);
 	FI_REQUIRE(1 <= opt->max_trials && opt->max_trials <= 0x7FFFFFFFL, FI_ERR_INVALID, "max_trials must be 1..2^31 - 1 (got %ld)",
 	           opt->max_trials);
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	FI_REQUIRE(m == 0 || (src_index != nullptr && tgt_index != nullptr), FI_ERR_INVALID, "null indices");
 	FI_REQUIRE(m == 0 || ((n_s == 0 || source != nullptr) && (n_t == 0 || target != nullptr)), FI_ERR_INVALID, "null points");
 	FI_REQUIRE(m < (1L << 31) && n_s < (1L << 31) && n_t < (1L << 31), FI_ERR_UNSUPPORTED, "%ld pairs over %ld and %ld points in one call", m,
@@ -1821,7 +1799,7 @@ int fi_points_describe(fi_points* h, const float* normals, int k, float max_dist
 	check_k(k);
 	FI_REQUIRE(normals != nullptr && features != nullptr, FI_ERR_INVALID, "null normals or features");
 	FI_REQUIRE(max_distance >= 0.0f, FI_ERR_INVALID, "max_distance must be >= 0 (got %g)", static_cast<double>(max_distance));  // (NaN fails)
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	FI_REQUIRE(h->t.D == 3, FI_ERR_UNSUPPORTED, "descriptors need 3 dimensions (the set has %d)", h->t.D);
 	fi::points_describe(h->t, normals, k, max_distance, features, valid, memory, nullptr);
 	FI_API_END
@@ -1835,7 +1813,7 @@ int fi_feature_match(int dim, long n_a, const float* a, const unsigned char* val
 	FI_REQUIRE(n_a >= 0 && n_b >= 0, FI_ERR_INVALID, "n_a = %ld, n_b = %ld", n_a, n_b);
 	FI_REQUIRE(n_a == 0 || (a != nullptr && indices != nullptr), FI_ERR_INVALID, "null a or indices");
 	FI_REQUIRE(n_a == 0 || n_b == 0 || b != nullptr, FI_ERR_INVALID, "b is null");
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	FI_REQUIRE(n_a < (1L << 31) && n_b < (1L << 31), FI_ERR_UNSUPPORTED, "%ld rows against %ld in one call", n_a, n_b);
 	fi::feature_match(dim, n_a, a, valid_a, n_b, b, valid_b, indices, distances, memory);
 	FI_API_END
@@ -1851,7 +1829,7 @@ void check_orient(const fi::NearestIndex* t, int ndim, int k, float max_distance
 	check_k(k);
 	FI_REQUIRE(normals != nullptr, FI_ERR_INVALID, "normals is null");
 	FI_REQUIRE(max_distance >= 0.0f, FI_ERR_INVALID, "max_distance must be >= 0 (got %g)", static_cast<double>(max_distance));
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	FI_REQUIRE(anchor == FI_ORIENT_NONE || anchor == FI_ORIENT_VIEWPOINTS || anchor == FI_ORIENT_DIRECTIONS, FI_ERR_INVALID,
 	           "bad anchor %d", anchor);
 	if (anchor == FI_ORIENT_NONE || !t) { return; }
@@ -1911,13 +1889,12 @@ int fi_surface_create(fi_surface** out, int ndim, long num_vertices, const float
 	FI_REQUIRE(num_vertices >= 0 && num_primitives >= 0, FI_ERR_INVALID, "%ld vertices, %ld primitives", num_vertices, num_primitives);
 	FI_REQUIRE(num_vertices == 0 || vertices != nullptr, FI_ERR_INVALID, "vertices is null");
 	FI_REQUIRE(num_primitives == 0 || indices != nullptr, FI_ERR_INVALID, "indices is null");
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	FI_REQUIRE(num_primitives < (1L << 31), FI_ERR_UNSUPPORTED, "%ld primitives: primitive indices are 32-bit", num_primitives);
 	std::unique_ptr<fi_surface> h(new fi_surface());
 	FI_HIP_TRY(hipGetDevice(&h->device));
-	fi::DevBuf   bv, bi;
-	const float* v = num_vertices > 0 ? fi::on_device(vertices, static_cast<int64_t>(ndim) * num_vertices, memory, bv) : vertices;
-	const int*   i = num_primitives > 0 ? fi::on_device(indices, static_cast<int64_t>(ndim) * num_primitives, memory, bi) : indices;
+	fi::stage::In<float> v(num_vertices > 0 ? vertices : nullptr, static_cast<int64_t>(ndim) * num_vertices, memory, nullptr);
+	fi::stage::In<int>   i(num_primitives > 0 ? indices : nullptr, static_cast<int64_t>(ndim) * num_primitives, memory, nullptr);
 	fi::surface_build(h->t, ndim, num_vertices, v, num_primitives, i, nullptr);
 	*out = h.release();
 	FI_API_END
@@ -1966,7 +1943,7 @@ void check_rays(long n, const float* origins, const float* directions, float t_m
 	FI_REQUIRE(n >= 0, FI_ERR_INVALID, "n = %ld", n);
 	FI_REQUIRE(origins != nullptr && directions != nullptr && out != nullptr, FI_ERR_INVALID, "null origins, directions or output");
 	FI_REQUIRE(t_min <= t_max, FI_ERR_INVALID, "t_min = %g, t_max = %g", static_cast<double>(t_min), static_cast<double>(t_max));  // (NaN fails)
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	fi::check_memory(memory);
 	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld rays in one call", n);
 }
 }  // namespace
@@ -2045,8 +2022,7 @@ int fi_redistance_field(const float* field, int ndim, const int* sizes, float is
 	FI_REQUIRE(ndim == 2 || ndim == 3, FI_ERR_UNSUPPORTED, "redistancing a %d-D lattice is not supported", ndim);
 	const int64_t n = fi::lattice_points(ndim, sizes);
 	FI_REQUIRE(n < (int64_t(1) << 31), FI_ERR_UNSUPPORTED, "a lattice of %lld points", static_cast<long long>(n));
-	fi::DevBuf   df;
-	const float* f = fi::on_device(field, n, memory, df);
+	fi::stage::In<float> f(field, n, memory, nullptr);
 	fi::redistance_whole(f, ndim, sizes, iso, method, max_distance, out, primitives, mesh, memory, nullptr);
 	FI_API_END
 }

@@ -417,19 +417,12 @@ struct ThinWork {
 	uint32_t* info;  // [0]: the error bits, [1]: the number of cells; zeroed
 	uint64_t *key, *key2;
 	uint32_t *val, *order, *head, *number, *first;
-	float *   pos, *nrm, *value;
+	const float *pos, *nrm, *value;
 	float *   opos, *onrm, *ovalue;
 	int *     ocount, *map;
 	long long* oindex;
 	Scratch   tmp;
 };
-
-// a host output's stand-in on the device (n elements of it), or the caller's device buffer itself
-template <typename T>
-T* stage_out(Arena& a, T* out, int64_t count, int memory)
-{
-	return out && memory == FI_HOST ? a.take<T>(count) : out;
-}
 
 template <int D>
 void thin(int64_t n, const float* positions, const float* normals, const float* values, const Grid& g, int mode, float* out_positions,
@@ -438,7 +431,6 @@ void thin(int64_t n, const float* positions, const float* normals, const float* 
 {
 	const uint64_t sentinel  = uint64_t(1) << (21 * D);
 	const size_t   tmp_bytes = std::max(sort_bytes(n, 0, 21 * D + 1), scan_bytes(n + 1));
-	const bool     host      = memory == FI_HOST;
 	ThinWork       w{};
 	DevBuf         block;
 	arena_alloc(block, [&](Arena& a) {
@@ -450,24 +442,19 @@ void thin(int64_t n, const float* positions, const float* normals, const float* 
 		w.head   = a.take<uint32_t>(n + 1);
 		w.number = a.take<uint32_t>(n + 1);
 		w.first  = a.take<uint32_t>(n + 1);
-		w.pos    = host ? a.take<float>(n * D) : const_cast<float*>(positions);
-		w.nrm    = !out_normals ? nullptr : host ? a.take<float>(n * D) : const_cast<float*>(normals);  // (read only for its output)
-		w.value  = !out_values ? nullptr : host ? a.take<float>(n) : const_cast<float*>(values);
-		w.opos   = stage_out(a, out_positions, n * D, memory);
-		w.onrm   = stage_out(a, out_normals, n * D, memory);
-		w.ovalue = stage_out(a, out_values, n, memory);
-		w.ocount = stage_out(a, out_counts, n, memory);
-		w.oindex = stage_out(a, out_indices, n, memory);
-		w.map    = stage_out(a, cell_map, n, memory);
+		w.pos    = stage::in(a, positions, n * D, memory, st);
+		w.nrm    = stage::in(a, out_normals ? normals : nullptr, n * D, memory, st);  // (read only for its output)
+		w.value  = stage::in(a, out_values ? values : nullptr, n, memory, st);
+		w.opos   = stage::out(a, out_positions, n * D, memory);
+		w.onrm   = stage::out(a, out_normals, n * D, memory);
+		w.ovalue = stage::out(a, out_values, n, memory);
+		w.ocount = stage::out(a, out_counts, n, memory);
+		w.oindex = stage::out(a, out_indices, n, memory);
+		w.map    = stage::out(a, cell_map, n, memory);
 		w.tmp.p     = a.take<char>(static_cast<int64_t>(tmp_bytes));
 		w.tmp.bytes = tmp_bytes;
 	});
 	FI_HIP_TRY(hipMemsetAsync(w.info, 0, 2 * sizeof(uint32_t), st));
-	if (host) {
-		FI_HIP_TRY(hipMemcpyAsync(w.pos, positions, sizeof(float) * D * n, hipMemcpyHostToDevice, st));
-		if (w.nrm) { FI_HIP_TRY(hipMemcpyAsync(w.nrm, normals, sizeof(float) * D * n, hipMemcpyHostToDevice, st)); }
-		if (w.value) { FI_HIP_TRY(hipMemcpyAsync(w.value, values, sizeof(float) * n, hipMemcpyHostToDevice, st)); }
-	}
 	hipLaunchKernelGGL(k_cloud_thin_keys<D>, grid(n), dim3(kThreads), 0, st, n, w.pos, g, sentinel, w.key, w.val, w.info);
 	FI_HIP_TRY(hipGetLastError());
 	sort_u64(w.key, w.key2, w.val, w.order, n, 0, 21 * D + 1, w.tmp, st);
@@ -500,16 +487,14 @@ void thin(int64_t n, const float* positions, const float* normals, const float* 
 		hipLaunchKernelGGL(k_cloud_thin_cells<D>, grid(nc), dim3(kThreads), 0, st, a);
 		FI_HIP_TRY(hipGetLastError());
 	}
-	if (host) {
-		if (nc > 0) {
-			FI_HIP_TRY(hipMemcpyAsync(out_positions, w.opos, sizeof(float) * D * nc, hipMemcpyDeviceToHost, st));
-			if (out_normals) { FI_HIP_TRY(hipMemcpyAsync(out_normals, w.onrm, sizeof(float) * D * nc, hipMemcpyDeviceToHost, st)); }
-			if (out_values) { FI_HIP_TRY(hipMemcpyAsync(out_values, w.ovalue, sizeof(float) * nc, hipMemcpyDeviceToHost, st)); }
-			if (out_counts) { FI_HIP_TRY(hipMemcpyAsync(out_counts, w.ocount, sizeof(int) * nc, hipMemcpyDeviceToHost, st)); }
-			if (out_indices) { FI_HIP_TRY(hipMemcpyAsync(out_indices, w.oindex, sizeof(long long) * nc, hipMemcpyDeviceToHost, st)); }
-		}
-		if (cell_map) { FI_HIP_TRY(hipMemcpyAsync(cell_map, w.map, sizeof(int) * n, hipMemcpyDeviceToHost, st)); }
+	if (nc > 0) {  // nc rows of the per-cell outputs, n of the map
+		stage::back(out_positions, w.opos, D * nc, memory, st);
+		stage::back(out_normals, w.onrm, D * nc, memory, st);
+		stage::back(out_values, w.ovalue, nc, memory, st);
+		stage::back(out_counts, w.ocount, nc, memory, st);
+		stage::back(out_indices, w.oindex, nc, memory, st);
 	}
+	stage::back(cell_map, w.map, n, memory, st);
 	FI_HIP_TRY(hipStreamSynchronize(st));
 	*num_out = static_cast<long>(nc);
 }
@@ -521,12 +506,12 @@ void cloud_radius_count(const NearestIndex& t, int64_t n, const float* queries, 
 {
 	if (n == 0) { return; }
 	AllocStream alloc_on(st);
-	Staged<int> c(counts, n, memory);
-	DevBuf      bq;
+	stage::Out<int> c(counts, n, memory);
+	stage::In<float> q(queries, n * t.D, memory, st);
 	RadiusArgs  a{};
 	a.t      = tree_of(t);
 	a.n      = n;
-	a.q      = stage_queries(queries, n, t.D, memory, bq, st);
+	a.q      = q;
 	a.lim    = limit_for(radius);
 	a.limit  = limit;
 	a.counts = c.dev;
@@ -540,9 +525,9 @@ void cloud_neighbour_distances(const NearestIndex& t, int k, float max_distance,
 {
 	if (t.n == 0) { return; }
 	AllocStream   alloc_on(st);
-	Staged<float> m(mean, t.n, memory);
-	Staged<float> kt(kth, t.n, memory);
-	Staged<int>   c(counts, t.n, memory);
+	stage::Out<float> m(mean, t.n, memory);
+	stage::Out<float> kt(kth, t.n, memory);
+	stage::Out<int>   c(counts, t.n, memory);
 	neighbours_on_device(t, k, max_distance, m.dev, kt.dev, c.dev, st);
 	m.back(st);
 	kt.back(st);
@@ -556,7 +541,7 @@ void cloud_outliers_statistical(const NearestIndex& t, int k, float max_distance
 	if (stats) { *stats = fi_outlier_stats{0, 0, 0.0, 0.0, 0.0}; }
 	if (t.n == 0) { return; }
 	AllocStream           alloc_on(st);
-	Staged<unsigned char> kp(keep, t.n, memory);
+	stage::Out<unsigned char> kp(keep, t.n, memory);
 	const int64_t         nb = (t.n + kSumBlock - 1) / kSumBlock;
 	float*                mean  = nullptr;
 	double*               part  = nullptr;
@@ -596,7 +581,7 @@ void cloud_outliers_radius(const NearestIndex& t, float radius, int min_neighbou
 	if (num_kept) { *num_kept = 0; }
 	if (t.n == 0) { return; }
 	AllocStream           alloc_on(st);
-	Staged<unsigned char> kp(keep, t.n, memory);
+	stage::Out<unsigned char> kp(keep, t.n, memory);
 	DevBuf                total;
 	total.alloc(sizeof(unsigned long long));
 	FI_HIP_TRY(hipMemsetAsync(total.p, 0, sizeof(unsigned long long), st));

@@ -41,7 +41,6 @@ namespace {
 
 using namespace bvh;
 using namespace unionfind;
-using knn::Staged;
 
 // ---- labels ---------------------------------------------------------------------------------------------------------
 
@@ -355,9 +354,9 @@ struct MeasureWork {
 	uint32_t*       info;  // the error bits; zeroed
 	uint64_t *      key, *key2;
 	uint32_t *      val, *order, *first, *nchunks, *chunk_first;
-	float*          pos;
-	int*            labels;
-	unsigned char*  core;
+	const float*    pos;
+	const int*      labels;
+	const unsigned char* core;
 	ChunkPartial*   partial;
 	fi_cluster_row* rows;
 	Scratch         tmp;
@@ -367,7 +366,6 @@ template <int D>
 void measure(int64_t n, const float* positions, const int* labels, const unsigned char* core, int64_t nc, fi_cluster_row* rows, int memory,
              hipStream_t st)
 {
-	const bool    host   = memory == FI_HOST;
 	const int     bits   = bits_for(nc + 1);
 	const int64_t chunks = n / kChunk + nc + 1;  // at most n / kChunk full chunks and a partial one per cluster
 	MeasureWork   w{};
@@ -382,19 +380,14 @@ void measure(int64_t n, const float* positions, const int* labels, const unsigne
 		w.first       = a.take<uint32_t>(nc + 1);
 		w.nchunks     = a.take<uint32_t>(nc + 1);
 		w.chunk_first = a.take<uint32_t>(nc + 1);
-		w.pos         = host ? a.take<float>(n * D) : const_cast<float*>(positions);
-		w.labels      = host ? a.take<int>(n) : const_cast<int*>(labels);
-		w.core        = !core ? nullptr : host ? a.take<unsigned char>(n) : const_cast<unsigned char*>(core);
+		w.pos         = stage::in(a, positions, n * D, memory, st);
+		w.labels      = stage::in(a, labels, n, memory, st);
+		w.core        = stage::in(a, core, n, memory, st);
 		w.partial     = a.take<ChunkPartial>(chunks);
 		w.rows        = a.take<fi_cluster_row>(nc + 1);
 		w.tmp.p       = a.take<char>(static_cast<int64_t>(w.tmp.bytes));
 	});
 	FI_HIP_TRY(hipMemsetAsync(w.info, 0, sizeof(uint32_t), st));
-	if (host) {
-		FI_HIP_TRY(hipMemcpyAsync(w.pos, positions, sizeof(float) * D * n, hipMemcpyHostToDevice, st));
-		FI_HIP_TRY(hipMemcpyAsync(w.labels, labels, sizeof(int) * n, hipMemcpyHostToDevice, st));
-		if (core) { FI_HIP_TRY(hipMemcpyAsync(w.core, core, n, hipMemcpyHostToDevice, st)); }
-	}
 	hipLaunchKernelGGL(k_cluster_keys, grid(n), dim3(kThreads), 0, st, n, nc, w.labels, w.key, w.val, w.info);
 	FI_HIP_TRY(hipGetLastError());
 	sort_u64(w.key, w.key2, w.val, w.order, n, 0, bits, w.tmp, st);
@@ -423,14 +416,14 @@ void cluster_labels(const NearestIndex& t, float eps, int min_points, int* label
 {
 	if (stats) { *stats = fi_cluster_stats{0, 0, 0, 0, static_cast<long>(t.n - t.nf)}; }
 	if (t.n == 0) { return; }
-	const int64_t         n = t.n;
-	AllocStream           alloc_on(st);
-	Staged<int>           lb(labels, n, memory);
-	Staged<unsigned char> cr(core, n, memory);
-	ClusterArgs           a{};
-	uint32_t*             flag   = nullptr;
-	uint32_t*             number = nullptr;
-	prim::Scratch         tmp;
+	const int64_t             n = t.n;
+	AllocStream               alloc_on(st);
+	stage::Out<int>           lb(labels, n, memory);
+	stage::Out<unsigned char> cr(core, n, memory);
+	ClusterArgs               a{};
+	uint32_t*                 flag   = nullptr;
+	uint32_t*                 number = nullptr;
+	prim::Scratch             tmp;
 	tmp.bytes = prim::scan_bytes(n + 1);
 	DevBuf block;
 	prim::arena_alloc(block, [&](prim::Arena& ar) {

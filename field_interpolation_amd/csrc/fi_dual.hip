@@ -12,6 +12,7 @@
 // Only the first two read the whole field; the fit and the primitives touch the active cells and their neighbourhoods.
 // Scratch: 8 bytes per active cell (the first primitives) plus the workgroup totals; nothing per lattice point.
 #include "fi_solver_internal.h"
+#include "fi_stage.h"
 #include "fi_prim.h"
 #include "fi_dual.h"
 
@@ -442,16 +443,11 @@ void dual_contour_ctx(fi_ctx* c, const float* field, const float* gradients, flo
 	           "dual contouring of a slab context: a slab's vertices need field planes hi .. hi + 2, one more than the ghost "
 	           "planes the iso path exchanges (a vertex exchange is not implemented)");
 	FI_REQUIRE(field || c->vectors_ready, FI_ERR_STATE, "no solution yet");
-	FI_REQUIRE((!field && !gradients) || memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	if (field || gradients) { check_memory(memory); }
 	AllocStream alloc_on(c->stream);
-	DevBuf buf, gbuf;
+	DevBuf buf;
 	const float* f = field_f32(c, field, memory, buf);
-	const float* gr = gradients;
-	if (gradients && memory == FI_HOST) {
-		gbuf.alloc(sizeof(float) * g.ndim * g.nown);
-		FI_HIP_TRY(hipMemcpyAsync(gbuf.p, gradients, sizeof(float) * g.ndim * g.nown, hipMemcpyHostToDevice, c->stream));
-		gr = gbuf.as<float>();
-	}
+	stage::In<float> gr(gradients, static_cast<int64_t>(g.ndim) * g.nown, memory, c->stream);
 	dual_contour_whole(f, gr, g.ndim, g.gn, iso, c->stream, out);
 }
 

@@ -349,10 +349,9 @@ void points_describe(const NearestIndex& t, const float* normals, int k, float m
 	const int64_t n = t.n, nf = t.nf;
 	if (n == 0) { return; }
 	AllocStream alloc_on(st);
-	const bool  host = memory == FI_HOST;
 	FeatArgs    a{};
 	DevBuf      block;
-	float *     pos = nullptr, *queries = nullptr, *dist = nullptr, *nrm = nullptr, *feat = nullptr;
+	float *     pos = nullptr, *queries = nullptr, *dist = nullptr, *feat = nullptr;
 	uint32_t*   who = nullptr;
 	long long*  idx = nullptr;
 	unsigned char* val = nullptr;
@@ -364,12 +363,11 @@ void points_describe(const NearestIndex& t, const float* normals, int k, float m
 		queries  = ar.take<float>(nf * 3);
 		dist     = ar.take<float>(nf * k);
 		who      = ar.take<uint32_t>(nf);
-		nrm      = host ? ar.take<float>(n * 3) : const_cast<float*>(normals);
-		feat     = host ? ar.take<float>(n * kWidth) : features;
+		a.normals = stage::in(ar, normals, n * 3, memory, st);
+		feat     = stage::out(ar, features, n * kWidth, memory);
 		a.live   = ar.take<unsigned char>(n);
-		val      = !valid ? nullptr : host ? ar.take<unsigned char>(n) : valid;
+		val      = stage::out(ar, valid, n, memory);
 	});
-	if (host) { FI_HIP_TRY(hipMemcpyAsync(nrm, normals, sizeof(float) * 3 * n, hipMemcpyHostToDevice, st)); }
 	FI_HIP_TRY(hipMemsetAsync(pos, 0xFF, sizeof(float) * 3 * n, st));  // NaN
 	FI_HIP_TRY(hipMemsetAsync(a.packed, 0, sizeof(unsigned long long) * 4 * n, st));
 	FI_HIP_TRY(hipMemsetAsync(feat, 0, sizeof(float) * kWidth * n, st));
@@ -380,7 +378,6 @@ void points_describe(const NearestIndex& t, const float* normals, int k, float m
 	a.who      = who;
 	a.idx      = idx;
 	a.pos      = pos;
-	a.normals  = nrm;
 	a.features = feat;
 	a.valid    = val;
 	const dim3 block_dim(kThreads);
@@ -395,10 +392,8 @@ void points_describe(const NearestIndex& t, const float* normals, int k, float m
 		hipLaunchKernelGGL(k_feat_fpfh, dim3(blocks_for(nf)), block_dim, 0, st, a);
 	}
 	FI_HIP_TRY(hipGetLastError());
-	if (host) {
-		FI_HIP_TRY(hipMemcpyAsync(features, feat, sizeof(float) * kWidth * n, hipMemcpyDeviceToHost, st));
-		if (valid) { FI_HIP_TRY(hipMemcpyAsync(valid, val, n, hipMemcpyDeviceToHost, st)); }
-	}
+	stage::back(features, feat, n * kWidth, memory, st);
+	stage::back(valid, val, n, memory, st);
 	FI_HIP_TRY(hipStreamSynchronize(st));  // the temporaries die here
 }
 
@@ -407,35 +402,23 @@ void feature_match(int dim, int64_t n_a, const float* a, const unsigned char* va
 {
 	if (n_a == 0) { return; }
 	hipStream_t st   = nullptr;
-	const bool  host = memory == FI_HOST;
 	MatchArgs   g{};
 	DevBuf      block;
-	float *     da = nullptr, *db = nullptr, *dd = nullptr;
-	unsigned char *dva = nullptr, *dvb = nullptr;
+	float*      dd = nullptr;
 	long long*  di = nullptr;
-	arena_alloc(block, [&](Arena& ar) {
+	arena_alloc(block, [&](Arena& ar) {  // (an empty b is not uploaded)
 		g.best = ar.take<unsigned long long>(n_a);
-		di     = host ? ar.take<long long>(n_a) : indices;
-		da     = host ? ar.take<float>(n_a * dim) : const_cast<float*>(a);
-		db     = host ? ar.take<float>(n_b * dim) : const_cast<float*>(b);
-		dd     = !distances ? nullptr : host ? ar.take<float>(n_a) : distances;
-		dva    = !valid_a ? nullptr : host ? ar.take<unsigned char>(n_a) : const_cast<unsigned char*>(valid_a);
-		dvb    = !valid_b ? nullptr : host ? ar.take<unsigned char>(n_b) : const_cast<unsigned char*>(valid_b);
+		di     = stage::out(ar, indices, n_a, memory);
+		g.a    = stage::in(ar, a, n_a * dim, memory, st);
+		g.b    = stage::in(ar, b, n_b * dim, memory, st);
+		dd     = stage::out(ar, distances, n_a, memory);
+		g.va   = stage::in(ar, valid_a, n_a, memory, st);
+		g.vb   = stage::in(ar, valid_b, n_b, memory, st);
 	});
-	if (host) {
-		FI_HIP_TRY(hipMemcpyAsync(da, a, sizeof(float) * dim * n_a, hipMemcpyHostToDevice, st));
-		if (n_b > 0) { FI_HIP_TRY(hipMemcpyAsync(db, b, sizeof(float) * dim * n_b, hipMemcpyHostToDevice, st)); }
-		if (valid_a) { FI_HIP_TRY(hipMemcpyAsync(dva, valid_a, n_a, hipMemcpyHostToDevice, st)); }
-		if (valid_b && n_b > 0) { FI_HIP_TRY(hipMemcpyAsync(dvb, valid_b, n_b, hipMemcpyHostToDevice, st)); }
-	}
 	FI_HIP_TRY(hipMemsetAsync(g.best, 0xFF, sizeof(unsigned long long) * n_a, st));  // kNoMatch
 	g.dim = dim;
 	g.na  = n_a;
 	g.nb  = n_b;
-	g.a   = da;
-	g.b   = db;
-	g.va  = dva;
-	g.vb  = dvb;
 	if (n_b > 0) {
 		// about 2048 workgroups: the rows of a first, then as many chunks of b as that leaves room for
 		const int64_t rows = blocks_for(n_a), tiles = (n_b + kTile - 1) / kTile;
@@ -454,10 +437,8 @@ void feature_match(int dim, int64_t n_a, const float* a, const unsigned char* va
 	}
 	hipLaunchKernelGGL(k_feat_match_out, dim3(blocks_for(n_a)), dim3(kThreads), 0, st, g, di, dd);
 	FI_HIP_TRY(hipGetLastError());
-	if (host) {
-		FI_HIP_TRY(hipMemcpyAsync(indices, di, sizeof(long long) * n_a, hipMemcpyDeviceToHost, st));
-		if (distances) { FI_HIP_TRY(hipMemcpyAsync(distances, dd, sizeof(float) * n_a, hipMemcpyDeviceToHost, st)); }
-	}
+	stage::back(indices, di, n_a, memory, st);
+	stage::back(distances, dd, n_a, memory, st);
 	FI_HIP_TRY(hipStreamSynchronize(st));
 }
 

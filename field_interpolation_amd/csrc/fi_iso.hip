@@ -11,6 +11,7 @@
 //   k_iso_prims     the cell's primitives at its scanned offset, vertex indices gathered from the bases of its corners
 // Scratch: 4 bytes per point (the bases) plus the workgroup totals.
 #include "fi_solver_internal.h"
+#include "fi_stage.h"
 #include "fi_prim.h"
 #include "fi_iso.h"
 #include "fi_iso_tables.h"
@@ -411,7 +412,7 @@ void iso_extract_ctx(fi_ctx* c, const float* field, float iso, int memory, fi_me
 	const int   L = g.ndim - 1;
 	check_dims(g.ndim, g.gn);
 	FI_REQUIRE(field || c->vectors_ready, FI_ERR_STATE, "no solution yet");
-	FI_REQUIRE(!field || memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	if (field) { check_memory(memory); }
 	if (c->nranks > 1) {
 		RankSet R{c};
 		slab_pieces(R, &field, memory, iso, out);

@@ -22,7 +22,7 @@ namespace fi {
 namespace {
 
 using namespace bvh;
-using namespace knn;  // the list of the k best pairs, capacity_for, Staged (fi_knn_list.h)
+using namespace knn;  // the list of the k best pairs, capacity_for (fi_knn_list.h)
 
 struct KnnArgs {
 	Tree         t;
@@ -236,18 +236,18 @@ void knn_query(const NearestIndex& t, int64_t n, const float* queries, int k, fl
                int memory, hipStream_t st)
 {
 	if (n == 0) { return; }
-	AllocStream       alloc_on(st);
-	Staged<float>     d(distances, n * k, memory);
-	Staged<long long> ix(indices, n * k, memory);
-	DevBuf            bq;
-	KnnArgs           a{};
+	AllocStream           alloc_on(st);
+	stage::Out<float>     d(distances, n * k, memory);
+	stage::Out<long long> ix(indices, n * k, memory);
+	stage::In<float>      q(queries, n * t.D, memory, st);
+	KnnArgs               a{};
 	a.t    = tree_of(t);
 	a.n    = n;
-	a.q    = stage_queries(queries, n, t.D, memory, bq, st);
+	a.q    = q;
 	a.k    = k;
 	a.lim  = limit_for(max_distance);
-	a.dist = d.dev;
-	a.idx  = ix.dev;
+	a.dist = d;
+	a.idx  = ix;
 	const dim3 grid(blocks_for(n));
 	switch (t.D) {
 	case 1: launch_query<1>(capacity_for(k), grid, a, st); break;
@@ -264,19 +264,19 @@ void estimate_normals(const NearestIndex& t, int k, float max_distance, int orie
                       float* normals, float* variation, int memory, hipStream_t st)
 {
 	if (t.n == 0) { return; }
-	AllocStream   alloc_on(st);
-	Staged<float> nr(normals, t.n * t.D, memory);
-	Staged<float> va(variation, t.n, memory);
-	DevBuf        bg;
-	NormalArgs    a{};
+	AllocStream       alloc_on(st);
+	stage::Out<float> nr(normals, t.n * t.D, memory);
+	stage::Out<float> va(variation, t.n, memory);
+	stage::In<float>  g(orient == kOrientNone ? nullptr : guides, num_guides * t.D, memory, st);
+	NormalArgs        a{};
 	a.t          = tree_of(t);
 	a.k          = k;
 	a.lim        = limit_for(max_distance);
 	a.orient     = orient;
-	a.guides     = orient == kOrientNone ? nullptr : stage_queries(guides, num_guides, t.D, memory, bg, st);
+	a.guides     = g;
 	a.num_guides = num_guides;
-	a.normals    = nr.dev;
-	a.variation  = va.dev;
+	a.normals    = nr;
+	a.variation  = va;
 	if (t.nf < t.n) {
 		hipLaunchKernelGGL(k_knn_blank, dim3(blocks_for(t.n)), dim3(kThreads), 0, st, t.n, t.D, a.normals, a.variation);
 	}

@@ -1,6 +1,6 @@
 // fi_knn_list.h -- the register-resident list of the k best pairs that the units walking fi_nearest.h's tree for more than one
-// neighbour share (fi_knn.hip: queries and normals; fi_cloud.hip: the neighbour distances of a set's own points), and the
-// staging of their outputs.  The list code is fi_knn.hip's, moved here as it was.
+// neighbour share (fi_knn.hip: queries and normals; fi_cloud.hip: the neighbour distances of a set's own points).  The list
+// code is fi_knn.hip's, moved here as it was.
 #pragma once
 
 #include "fi_solver_internal.h"
@@ -80,27 +80,6 @@ __device__ inline bool found(float s, uint32_t j, float lim) { return s >= 0.0f 
 
 // the list's capacity class of a k
 inline int capacity_for(int k) { return k <= 8 ? 8 : k <= 16 ? 16 : 32; }
-
-// a caller's output of `count` elements on the device: the buffer itself (FI_DEVICE) or a staged one, copied back by back()
-template <typename T>
-struct Staged {
-	T*     host;
-	T*     dev;
-	size_t bytes;
-	int    memory;
-	DevBuf buf;
-	Staged(T* out, int64_t count, int mem) : host(out), dev(out), bytes(sizeof(T) * count), memory(mem)
-	{
-		if (out && memory == FI_HOST) {
-			buf.alloc(bytes);
-			dev = buf.as<T>();
-		}
-	}
-	void back(hipStream_t st)
-	{
-		if (host && memory == FI_HOST) { FI_HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st)); }
-	}
-};
 
 }  // namespace knn
 }  // namespace fi

@@ -21,6 +21,7 @@
 //              the query's number inverted below: the first of equal maxima wins); one thread adds the block sums in order.
 // No floating-point atomics, no atomics at all; one device allocation for every temporary of a call (fi_arena.h).
 #include "fi_solver_internal.h"
+#include "fi_stage.h"
 #include "fi_meshpts.h"
 #include "fi_prim.h"
 #include "fi_uniform.h"
@@ -494,7 +495,7 @@ void mesh_sample(const fi_mesh* m, long n, unsigned long long seed, int normals_
 	FI_REQUIRE(n == 0 || positions != nullptr, FI_ERR_INVALID, "positions is null");
 	FI_REQUIRE(normals_mode == FI_SAMPLE_NORMALS_FACE || normals_mode == FI_SAMPLE_NORMALS_VERTEX, FI_ERR_INVALID, "bad normals mode %d",
 	           normals_mode);
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	check_memory(memory);
 	FI_REQUIRE(!(normals && normals_mode == FI_SAMPLE_NORMALS_VERTEX) || m->has_normals, FI_ERR_INVALID, "the mesh has no vertex normals");
 	FI_REQUIRE(m->ndim == 2 || m->ndim == 3, FI_ERR_INVALID, "a mesh of %d-vertex primitives", m->ndim);
 	// (one thread per sample, (double)i exact)
@@ -504,20 +505,17 @@ void mesh_sample(const fi_mesh* m, long n, unsigned long long seed, int normals_
 	FI_HIP_TRY(hipSetDevice(m->device));
 	hipStream_t   st   = nullptr;
 	const int64_t D    = m->ndim;
-	const bool    host = memory == FI_HOST;
 	Weights       w{};
 	Scratch       tmp{};
-	float *       dpos = positions, *dnrm = normals;
-	long long*    dprim = primitives;
+	float *       dpos = nullptr, *dnrm = nullptr;
+	long long*    dprim = nullptr;
 	const size_t  tmp_bytes = scan_u64_bytes(m->np + 1);
 	DevBuf        block;
 	arena_alloc(block, [&](Arena& a) {
 		take_weights(a, m->np, w);
-		if (host) {
-			dpos  = a.take<float>(n * D);
-			dnrm  = normals ? a.take<float>(n * D) : nullptr;
-			dprim = primitives ? a.take<long long>(n) : nullptr;
-		}
+		dpos      = stage::out(a, positions, n * D, memory);
+		dnrm      = stage::out(a, normals, n * D, memory);
+		dprim     = stage::out(a, primitives, n, memory);
 		tmp.p     = a.take<char>(static_cast<int64_t>(tmp_bytes));
 		tmp.bytes = tmp_bytes;
 	});
@@ -525,11 +523,9 @@ void mesh_sample(const fi_mesh* m, long n, unsigned long long seed, int normals_
 	FI_REQUIRE(total > 0, FI_ERR_INVALID, "no primitive of the mesh has a positive finite measure");
 	const int mode = !normals ? kNoNormals : normals_mode == FI_SAMPLE_NORMALS_FACE ? kFace : kVertex;
 	draw(m, n, seed, mode, total, w, dpos, dnrm, dprim, st);
-	if (host) {
-		FI_HIP_TRY(hipMemcpyAsync(positions, dpos, sizeof(float) * D * n, hipMemcpyDeviceToHost, st));
-		if (normals) { FI_HIP_TRY(hipMemcpyAsync(normals, dnrm, sizeof(float) * D * n, hipMemcpyDeviceToHost, st)); }
-		if (primitives) { FI_HIP_TRY(hipMemcpyAsync(primitives, dprim, sizeof(long long) * n, hipMemcpyDeviceToHost, st)); }
-	}
+	stage::back(positions, dpos, n * D, memory, st);
+	stage::back(normals, dnrm, n * D, memory, st);
+	stage::back(primitives, dprim, n, memory, st);
 	FI_HIP_TRY(hipStreamSynchronize(st));  // (the arena goes back behind the kernels that use it)
 }
 
@@ -543,7 +539,7 @@ void mesh_deviation(const fi_mesh* a, fi_surface* b, long samples, unsigned long
 	FI_REQUIRE(a->device == b->device, FI_ERR_INVALID, "the mesh is on device %d, the surface on device %d", a->device, b->device);
 	FI_REQUIRE(samples >= 0, FI_ERR_INVALID, "samples = %ld", samples);
 	FI_REQUIRE(max_distance >= 0.0f, FI_ERR_INVALID, "max_distance must be >= 0 (got %g)", static_cast<double>(max_distance));  // (NaN fails)
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	check_memory(memory);
 	FI_REQUIRE(samples < (1L << 31), FI_ERR_UNSUPPORTED, "%ld samples in one call", samples);
 	FI_HIP_TRY(hipSetDevice(a->device));
 	hipStream_t   st = nullptr;
@@ -551,7 +547,6 @@ void mesh_deviation(const fi_mesh* a, fi_surface* b, long samples, unsigned long
 	const int64_t nv = a->nv, np = a->np, ns = samples;
 	const bool    sampled = ns > 0 && of_samples && np > 0;
 	const bool    walked  = (of_vertices || vertex_distances) && nv > 0;
-	const bool    staged  = vertex_distances && memory == FI_HOST && nv > 0;
 
 	Weights       w{};
 	Partials      p{};
@@ -576,7 +571,7 @@ void mesh_deviation(const fi_mesh* a, fi_surface* b, long samples, unsigned long
 			number = ar.take<uint32_t>(nv + 1);
 			vpos   = ar.take<float>(nv * D);
 			vdist  = ar.take<float>(nv);
-			if (staged) { vout = ar.take<float>(nv); }
+			vout   = stage::out(ar, vertex_distances, nv, memory);
 		}
 		tmp.p     = ar.take<char>(static_cast<int64_t>(tmp_bytes));
 		tmp.bytes = tmp_bytes;
@@ -615,7 +610,7 @@ void mesh_deviation(const fi_mesh* a, fi_surface* b, long samples, unsigned long
 		if (vertex_distances) {
 			hipLaunchKernelGGL(k_mpts_scatter, grid(nv), dim3(kThreads), 0, st, nv, used, number, vdist, vout);
 			FI_HIP_TRY(hipGetLastError());
-			if (staged) { FI_HIP_TRY(hipMemcpyAsync(vertex_distances, vout, sizeof(float) * nv, hipMemcpyDeviceToHost, st)); }
+			stage::back(vertex_distances, vout, nv, memory, st);
 		}
 	}
 	for (int k = 0; k < 2; ++k) {

@@ -188,11 +188,11 @@ void nearest_query(const NearestIndex& t, int64_t n, const float* queries, float
 	if (n == 0) { return; }
 	AllocStream alloc_on(st);
 	Outputs o(n, t.D, distances, indices, nullptr, memory);
-	DevBuf  bq;
+	stage::In<float> q(queries, n * t.D, memory, st);
 	QueryArgs a{};
 	a.t    = tree_of(t);
 	a.n    = n;
-	a.q    = stage_queries(queries, n, t.D, memory, bq, st);
+	a.q    = q;
 	a.lim  = limit_for(max_distance);
 	a.dist = o.dist;
 	a.idx  = o.idx;

@@ -429,30 +429,17 @@ void orient_normals(const NearestIndex& t, int k, float max_distance, int anchor
 	AllocStream alloc_on(st);
 	OrientStats mine;
 	if (!stats && test_switch("FI_ORIENT_STATS")) { stats = &mine; }
-	// the caller's buffers on the device: its own (FI_DEVICE) or staged
-	DevBuf       bn, bc, bg;
-	float*       nrm  = normals;
-	long long*   comp = components;
-	const size_t nb = sizeof(float) * t.D * t.n, cb = sizeof(long long) * t.n;
-	if (memory == FI_HOST) {
-		bn.alloc(nb);
-		nrm = bn.as<float>();
-		FI_HIP_TRY(hipMemcpyAsync(nrm, normals, nb, hipMemcpyHostToDevice, st));
-		if (components) {
-			bc.alloc(cb);
-			comp = bc.as<long long>();
-		}
-	}
-	const float* g = anchor == kAnchorNone ? nullptr : stage_queries(guides, num_guides, t.D, memory, bg, st);
+	stage::Out<float> nrm(normals, t.D * t.n, memory);  // in and out: a stand-in starts as the caller's normals
+	if (nrm.host) { stage::upload(nrm.dev, normals, nrm.count, st); }
+	stage::Out<long long> comp(components, t.n, memory);
+	stage::In<float>      g(anchor == kAnchorNone ? nullptr : guides, num_guides * t.D, memory, st);
 	if (t.D == 2) {
 		run<2>(t, k, max_distance, anchor, g, num_guides, nrm, comp, st, stats);
 	} else {
 		run<3>(t, k, max_distance, anchor, g, num_guides, nrm, comp, st, stats);
 	}
-	if (memory == FI_HOST) {
-		FI_HIP_TRY(hipMemcpyAsync(normals, nrm, nb, hipMemcpyDeviceToHost, st));
-		if (components) { FI_HIP_TRY(hipMemcpyAsync(components, comp, cb, hipMemcpyDeviceToHost, st)); }
-	}
+	nrm.back(st);
+	comp.back(st);
 	FI_HIP_TRY(hipStreamSynchronize(st));
 	if (stats == &mine) {
 		std::fprintf(stderr, "fi_orient_normals: n %lld k %d rounds %d launches/round %d table_ms %.3f propagate_ms %.3f\n",

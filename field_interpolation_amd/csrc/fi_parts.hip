@@ -21,6 +21,7 @@
 //             its chunks' partials in ascending order.  No floating-point atomics.
 //   select    keep flags per vertex and primitive, exclusive scans, a gather with remapped indices.
 #include "fi_solver_internal.h"
+#include "fi_stage.h"
 #include "fi_parts.h"
 #include "fi_prim.h"
 #include "fi_treesum.h"
@@ -637,7 +638,7 @@ void mesh_create(fi_mesh** out, int ndim, long num_vertices, const float* vertic
 {
 	FI_REQUIRE(out != nullptr, FI_ERR_INVALID, "out is null");
 	*out = nullptr;
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	check_memory(memory);
 	FI_REQUIRE(ndim == 2 || ndim == 3, FI_ERR_UNSUPPORTED, "a mesh has 2 or 3 dimensions (got %d)", ndim);
 	FI_REQUIRE(num_vertices >= 0 && num_primitives >= 0, FI_ERR_INVALID, "negative count");
 	FI_REQUIRE(num_vertices < (1LL << 31) && num_primitives < (1LL << 31), FI_ERR_UNSUPPORTED,
@@ -686,7 +687,7 @@ void mesh_create(fi_mesh** out, int ndim, long num_vertices, const float* vertic
 void mesh_parts(const fi_mesh* m, long* num_parts, int* vertex_labels, int* primitive_labels, int memory)
 {
 	check_mesh(m);
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	check_memory(memory);
 	std::lock_guard<std::mutex> hold(m->parts_lock);
 	const MeshParts*            P = ensure_labels(m);
 	if (num_parts) { *num_parts = static_cast<long>(P->count); }

@@ -21,6 +21,7 @@
 //              refit loop never returns to the host: a `done` word on the device turns the remaining rounds into no-ops.
 // One device allocation (fi_arena.h) a call; per plane one read-back a batch and one for the model.
 #include "fi_solver_internal.h"
+#include "fi_stage.h"
 #include "fi_plane.h"
 #include "fi_consensus.h"
 #include "fi_jacobi.h"
@@ -384,13 +385,10 @@ struct PlaneWork {
 };
 
 template <int D>
-void lay_out(PlaneWork& w, DevBuf& block, int64_t n, const float* positions, const unsigned char* mask, unsigned char* flag_dev, int memory,
+void lay_out(PlaneWork& w, DevBuf& block, int64_t n, const float* positions, const unsigned char* mask, unsigned char* flag, int memory,
              hipStream_t st)
 {
-	const bool    host   = memory == FI_HOST;
 	const int64_t chunks = (n + kChunk - 1) / kChunk;
-	float*         pos = nullptr;
-	unsigned char* msk = nullptr;
 	w.tmp.bytes = select_bytes(n);
 	arena_alloc(block, [&](Arena& ar) {
 		w.a.state   = ar.take<PlaneState>(1);
@@ -399,24 +397,18 @@ void lay_out(PlaneWork& w, DevBuf& block, int64_t n, const float* positions, con
 		w.a.counts  = ar.take<uint32_t>(kBatch);
 		w.a.partial = ar.take<double>(chunks * kMaxK);
 		w.cflag     = ar.take<unsigned char>(n);
-		w.a.flag    = flag_dev ? flag_dev : ar.take<unsigned char>(n);
+		w.a.flag    = stage::work(ar, flag, n, memory);
 		w.cand      = ar.take<uint32_t>(n);
 		w.member    = ar.take<uint32_t>(n);
-		pos         = host ? ar.take<float>(n * D) : const_cast<float*>(positions);
-		msk         = !mask ? nullptr : host ? ar.take<unsigned char>(n) : const_cast<unsigned char*>(mask);
+		w.a.pos     = stage::in(ar, positions, n * D, memory, st);
+		w.mask      = stage::in(ar, mask, n, memory, st);
 		w.tmp.p     = ar.take<char>(static_cast<int64_t>(w.tmp.bytes));
 	});
-	if (host) {
-		FI_HIP_TRY(hipMemcpyAsync(pos, positions, sizeof(float) * D * n, hipMemcpyHostToDevice, st));
-		if (mask) { FI_HIP_TRY(hipMemcpyAsync(msk, mask, n, hipMemcpyHostToDevice, st)); }
-	}
 	FI_HIP_TRY(hipMemsetAsync(w.a.counts, 0, sizeof(uint32_t) * kBatch, st));
 	w.a.n      = n;
-	w.a.pos    = pos;
 	w.a.cflag  = w.cflag;
 	w.a.cand   = w.cand;
 	w.a.member = w.member;
-	w.mask     = msk;
 }
 
 void constrain(PlaneArgs& a, int D, const fi_plane_options& opt)
@@ -484,13 +476,12 @@ template <int D>
 void fit(int64_t n, const float* positions, const unsigned char* mask, const fi_plane_options& opt, fi_plane_model* model,
          unsigned char* inliers, int memory, hipStream_t st)
 {
-	const bool to_host = inliers && memory == FI_HOST;
 	PlaneWork  w{};
 	DevBuf     block;
-	lay_out<D>(w, block, n, positions, mask, to_host ? nullptr : inliers, memory, st);
+	lay_out<D>(w, block, n, positions, mask, inliers, memory, st);
 	constrain(w.a, D, opt);
 	fit_one<D>(w, opt, opt.seed, nullptr, model, st);
-	if (to_host) { FI_HIP_TRY(hipMemcpyAsync(inliers, w.a.flag, n, hipMemcpyDeviceToHost, st)); }
+	stage::back(inliers, w.a.flag, n, memory, st);
 	FI_HIP_TRY(hipStreamSynchronize(st));
 }
 
@@ -498,16 +489,11 @@ template <int D>
 void segment(int64_t n, const float* positions, const unsigned char* mask, const fi_plane_options& opt, int max_planes, int64_t min_inliers,
              int* labels, fi_plane_model* rows, int* num_planes, int memory, hipStream_t st)
 {
-	const bool host = memory == FI_HOST;
 	PlaneWork  w{};
-	DevBuf     block, staged;
+	DevBuf     block;
 	lay_out<D>(w, block, n, positions, mask, nullptr, memory, st);
 	constrain(w.a, D, opt);
-	int* lab = labels;
-	if (host) {
-		staged.alloc(sizeof(int) * n);
-		lab = staged.as<int>();
-	}
+	stage::Out<int> lab(labels, n, memory);
 	FI_HIP_TRY(hipMemsetAsync(lab, 0xFF, sizeof(int) * n, st));  // -1
 	for (int p = 0; p < max_planes; ++p) {
 		fi_plane_model got{};
@@ -518,7 +504,7 @@ void segment(int64_t n, const float* positions, const unsigned char* mask, const
 		rows[p]     = got;
 		*num_planes = p + 1;
 	}
-	if (host) { FI_HIP_TRY(hipMemcpyAsync(labels, lab, sizeof(int) * n, hipMemcpyDeviceToHost, st)); }
+	lab.back(st);
 	FI_HIP_TRY(hipStreamSynchronize(st));
 }
 

@@ -347,12 +347,12 @@ void ray_cast(const SurfaceIndex& t, int64_t n, const float* origins, const floa
 	if (n == 0) { return; }
 	AllocStream alloc_on(st);
 	Outputs     o(n, t.D - 1, hit_t, primitives, bary, memory);  // (its `closest`: D - 1 barycentrics per ray)
-	DevBuf      bo, bd;
+	stage::In<float> org(origins, n * t.D, memory, st), dir(directions, n * t.D, memory, st);
 	RayArgs     a{};
 	a.t     = tree_of(t);
 	a.n     = n;
-	a.o     = stage_queries(origins, n, t.D, memory, bo, st);
-	a.d     = stage_queries(directions, n, t.D, memory, bd, st);
+	a.o     = org;
+	a.d     = dir;
 	a.t_min = t_min;
 	a.t_max = t_max;
 	a.hit_t = o.dist;
@@ -372,22 +372,19 @@ void ray_count(const SurfaceIndex& t, int64_t n, const float* origins, const flo
 {
 	if (n == 0) { return; }
 	AllocStream alloc_on(st);
-	DevBuf      bo, bd, bc;
+	stage::In<float> org(origins, n * t.D, memory, st), dir(directions, n * t.D, memory, st);
+	stage::Out<int>  c(counts, n, memory);
 	RayArgs     a{};
 	a.t      = tree_of(t);
 	a.n      = n;
-	a.o      = stage_queries(origins, n, t.D, memory, bo, st);
-	a.d      = stage_queries(directions, n, t.D, memory, bd, st);
+	a.o      = org;
+	a.d      = dir;
 	a.t_min  = t_min;
 	a.t_max  = t_max;
 	a.limit  = limit;
-	a.counts = counts;
-	if (memory == FI_HOST) {
-		bc.alloc(sizeof(int) * n);
-		a.counts = bc.as<int>();
-	}
+	a.counts = c;
 	launch_count<kCounts>(t.D, dim3(blocks_for(n)), a, st);
-	if (memory == FI_HOST) { FI_HIP_TRY(hipMemcpyAsync(counts, a.counts, sizeof(int) * n, hipMemcpyDeviceToHost, st)); }
+	c.back(st);
 	FI_HIP_TRY(hipStreamSynchronize(st));
 }
 
@@ -396,18 +393,15 @@ void ray_contains(const SurfaceIndex& t, int64_t n, const float* points, const f
 {
 	if (n == 0) { return; }
 	AllocStream alloc_on(st);
-	DevBuf      bo, bi;
+	stage::In<float>           org(points, n * t.D, memory, st);
+	stage::Out<unsigned char>  in(inside, n, memory);
 	RayArgs     a{};
 	parity_rays(a, t, direction);
 	a.n      = n;
-	a.o      = stage_queries(points, n, t.D, memory, bo, st);
-	a.inside = inside;
-	if (memory == FI_HOST) {
-		bi.alloc(static_cast<size_t>(n));
-		a.inside = bi.as<unsigned char>();
-	}
+	a.o      = org;
+	a.inside = in;
 	launch_count<kInside>(t.D, dim3(blocks_for(n)), a, st);
-	if (memory == FI_HOST) { FI_HIP_TRY(hipMemcpyAsync(inside, a.inside, static_cast<size_t>(n), hipMemcpyDeviceToHost, st)); }
+	in.back(st);
 	FI_HIP_TRY(hipStreamSynchronize(st));
 }
 
@@ -417,11 +411,11 @@ void ray_signed_query(const SurfaceIndex& t, int64_t n, const float* queries, fl
 	if (n == 0) { return; }
 	AllocStream alloc_on(st);
 	Outputs     o(n, t.D, distances, primitives, closest, memory);
-	DevBuf      bq;
+	stage::In<float> q(queries, n * t.D, memory, st);
 	RayArgs     a{};
 	parity_rays(a, t, nullptr);
 	a.n    = n;
-	a.o    = stage_queries(queries, n, t.D, memory, bq, st);
+	a.o    = q;
 	a.dist = o.dist;
 	surface_query(t, n, a.o, max_distance, o.dist, o.idx, o.cl, FI_DEVICE, st);  // the unchanged kernels, on the device
 	launch_count<kSign>(t.D, dim3(blocks_for(n)), a, st);

@@ -21,6 +21,7 @@
 //              writes the state -- or, for the last evaluation, the result.  The host reads the state once per step.
 // No atomics of any kind; one device allocation for every temporary of a call (fi_arena.h); nothing is kept with a handle.
 #include "fi_solver_internal.h"
+#include "fi_stage.h"
 #include "fi_register.h"
 #include "fi_prim.h"
 
@@ -628,7 +629,7 @@ void check_common(long n, const float* source, const fi_register_options* opt, c
 		FI_REQUIRE(opt->scale > 0.0f, FI_ERR_INVALID, "a loss needs scale > 0 (got %g)", static_cast<double>(opt->scale));
 		FI_REQUIRE(opt->tuning >= 0.0f, FI_ERR_INVALID, "tuning must be >= 0 (got %g)", static_cast<double>(opt->tuning));
 	}
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	check_memory(memory);
 	if (initial) {
 		for (int a = 0; a < D; ++a) {
 			for (int b = 0; b <= D; ++b) {
@@ -678,14 +679,13 @@ void run(const Target& tg, int64_t n, const float* source, const fi_register_opt
 	}
 	FI_HIP_TRY(hipSetDevice(tg.device));
 	hipStream_t   st    = nullptr;
-	const bool    host  = memory == FI_HOST;
 	const bool    plane = opt->mode == FI_REGISTER_PLANE;
 	const int64_t nb    = blocks_of(n), bounds_blocks = std::min<int64_t>(nb, kBoundsBlocks), nw = bounds_blocks * (kThreads / 64);
 	const int64_t m     = tg.kind == kSet ? tg.set->n : 0;
 	constexpr int K     = sums_of(D);
 
-	const float*     src  = source;
-	float *          p = transformed, *dist = distances, *closest = nullptr, *tpos = nullptr, *part = nullptr;
+	const float*     src  = nullptr;
+	float *          p = nullptr, *dist = nullptr, *closest = nullptr, *tpos = nullptr, *part = nullptr;
 	const float*     tnrm = tg.normals;
 	long long*       prim = nullptr;
 	double*          partial = nullptr;
@@ -700,22 +700,16 @@ void run(const Target& tg, int64_t n, const float* source, const fi_register_opt
 		partial = ar.take<double>(nb * K);
 		count   = ar.take<uint64_t>(nb);
 		prim    = ar.take<long long>(n);
-		if (host) { src = ar.take<float>(n * D); }
-		if (host || !transformed) { p = ar.take<float>(n * D); }
-		if (host || !distances) { dist = ar.take<float>(n); }
+		src     = stage::in(ar, source, n * D, memory, st);
+		p       = stage::work(ar, transformed, n * D, memory);
+		dist    = stage::work(ar, distances, n, memory);
 		if (tg.kind == kMesh) {
 			closest = ar.take<float>(n * D);
 		} else {
 			tpos = ar.take<float>(m * D);
-			if (plane && host) { tnrm = ar.take<float>(m * D); }
+			if (plane) { tnrm = stage::in(ar, tg.normals, m * D, memory, st); }  // (read by the plane mode only)
 		}
 	});
-	if (host) {
-		FI_HIP_TRY(hipMemcpyAsync(const_cast<float*>(src), source, sizeof(float) * D * n, hipMemcpyHostToDevice, st));
-		if (tg.kind == kSet && plane && m > 0) {
-			FI_HIP_TRY(hipMemcpyAsync(const_cast<float*>(tnrm), tg.normals, sizeof(float) * D * m, hipMemcpyHostToDevice, st));
-		}
-	}
 	if (tg.kind == kSet && tg.set->nf > 0) {
 		hipLaunchKernelGGL(k_reg_unsort<D>, grid(tg.set->nf), dim3(kThreads), 0, st, tg.set->nf, m, tg.set->items.as<float4>(), tpos);
 	}
@@ -765,10 +759,8 @@ void run(const Target& tg, int64_t n, const float* source, const fi_register_opt
 	evaluate(1);
 	fi_registration got;
 	FI_HIP_TRY(hipMemcpyAsync(&got, res, sizeof(got), hipMemcpyDeviceToHost, st));
-	if (host) {
-		if (transformed) { FI_HIP_TRY(hipMemcpyAsync(transformed, p, sizeof(float) * D * n, hipMemcpyDeviceToHost, st)); }
-		if (distances) { FI_HIP_TRY(hipMemcpyAsync(distances, dist, sizeof(float) * n, hipMemcpyDeviceToHost, st)); }
-	}
+	stage::back(transformed, p, n * D, memory, st);
+	stage::back(distances, dist, n, memory, st);
 	FI_HIP_TRY(hipStreamSynchronize(st));  // (the arena goes back behind the kernels that use it)
 	*out = got;
 }

@@ -12,6 +12,7 @@
 // linear, 2 for cubic), samples the points whose slowest cell index lies in its slab and writes -0.0 for every other point;
 // the sum over the slabs is then exact, sign of zero included, and points outside the lattice get `fill` after it.
 #include "fi_solver_internal.h"
+#include "fi_stage.h"
 #include "fi_sample.h"
 
 namespace fi {
@@ -283,7 +284,7 @@ void check_query(int ndim, const int* sizes, int64_t n, const float* positions, 
 	FI_REQUIRE(n >= 0, FI_ERR_INVALID, "n = %lld", static_cast<long long>(n));
 	FI_REQUIRE(positions != nullptr && values != nullptr, FI_ERR_INVALID, "null positions or values");
 	FI_REQUIRE(mode == FI_SAMPLE_LINEAR || mode == FI_SAMPLE_CUBIC, FI_ERR_INVALID, "bad sampling mode %d", mode);
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	check_memory(memory);
 	FI_REQUIRE(sizes != nullptr, FI_ERR_INVALID, "sizes is null");
 	FI_REQUIRE(ndim >= 1 && ndim <= 3, FI_ERR_INVALID, "ndim must be 1, 2 or 3 (got %d)", ndim);
 	for (int d = 0; d < ndim; ++d) { FI_REQUIRE(sizes[d] >= 2, FI_ERR_INVALID, "sampling needs sizes >= 2 (sizes[%d] = %d)", d, sizes[d]); }
@@ -291,35 +292,15 @@ void check_query(int ndim, const int* sizes, int64_t n, const float* positions, 
 	FI_REQUIRE(n < (int64_t(1) << 31), FI_ERR_UNSUPPORTED, "%lld points in one call", static_cast<long long>(n));
 }
 
-// the call's buffers on the device: the caller's (FI_DEVICE) or staged copies (FI_HOST), copied back by finish()
+// the call's buffers on the device (fi_stage.h), its kernel arguments, and finish(), which copies back and ends the call
 struct Query {
-	int64_t      n;
-	int          D;
-	int          memory;
-	const float* pos  = nullptr;
-	float*       val  = nullptr;
-	float*       grad = nullptr;
-	float*       host_val;
-	float*       host_grad;
-	DevBuf       bpos, bval, bgrad;
-	Query(int ndim, int64_t npts, const float* positions, float* values, float* gradients, int mem, hipStream_t st)
-	    : n(npts), D(ndim), memory(mem), host_val(values), host_grad(gradients)
+	int64_t           n;
+	int               D;
+	stage::In<float>  pos;
+	stage::Out<float> val, grad;
+	Query(int ndim, int64_t npts, const float* positions, float* values, float* gradients, int memory, hipStream_t st)
+	    : n(npts), D(ndim), pos(positions, D * n, memory, st), val(values, n, memory), grad(gradients, D * n, memory)
 	{
-		if (memory == FI_DEVICE) {
-			pos  = positions;
-			val  = values;
-			grad = gradients;
-			return;
-		}
-		bpos.alloc(sizeof(float) * D * n);
-		bval.alloc(sizeof(float) * n);
-		FI_HIP_TRY(hipMemcpyAsync(bpos.p, positions, sizeof(float) * D * n, hipMemcpyHostToDevice, st));
-		pos = bpos.as<float>();
-		val = bval.as<float>();
-		if (gradients) {
-			bgrad.alloc(sizeof(float) * D * n);
-			grad = bgrad.as<float>();
-		}
 	}
 	template <typename T>
 	SampleArgs<T> args(const T* f, const int* sizes, float fill) const
@@ -340,10 +321,8 @@ struct Query {
 	}
 	void finish(hipStream_t st)
 	{
-		if (memory == FI_HOST) {
-			FI_HIP_TRY(hipMemcpyAsync(host_val, val, sizeof(float) * n, hipMemcpyDeviceToHost, st));
-			if (grad) { FI_HIP_TRY(hipMemcpyAsync(host_grad, grad, sizeof(float) * D * n, hipMemcpyDeviceToHost, st)); }
-		}
+		val.back(st);
+		grad.back(st);
 		FI_HIP_TRY(hipStreamSynchronize(st));
 	}
 };
@@ -445,15 +424,9 @@ void sample_field(const float* field, int ndim, const int* sizes, int64_t n, con
 	if (n == 0) { return; }
 	hipStream_t st = nullptr;
 	Query q(ndim, n, positions, values, gradients, memory, st);
-	DevBuf buf;
-	const float* f = field;
-	if (memory == FI_HOST) {
-		int64_t total = 1;
-		for (int d = 0; d < ndim; ++d) { total *= sizes[d]; }
-		buf.alloc(sizeof(float) * total);
-		FI_HIP_TRY(hipMemcpyAsync(buf.p, field, sizeof(float) * total, hipMemcpyHostToDevice, st));
-		f = buf.as<float>();
-	}
+	int64_t total = 1;
+	for (int d = 0; d < ndim; ++d) { total *= sizes[d]; }
+	stage::In<float> f(field, total, memory, st);
 	launch(ndim, mode, q.args<float>(f, sizes, fill), st);
 	q.finish(st);
 }

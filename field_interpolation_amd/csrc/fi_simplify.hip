@@ -21,6 +21,7 @@
 // No floating-point atomics, no atomics writing an output, one read-back per size the host needs, one device allocation for
 // every temporary of a call (fi_arena.h; the host helpers around the sorts and scans are fi_prim.h's).
 #include "fi_solver_internal.h"
+#include "fi_stage.h"
 #include "fi_simplify.h"
 #include "fi_prim.h"
 #include "fi_jacobi.h"
@@ -568,7 +569,7 @@ void mesh_simplify(const fi_mesh* m, float cell, const float* origin, int placem
 	*out = nullptr;
 	FI_REQUIRE(m != nullptr, FI_ERR_INVALID, "null mesh");
 	FI_REQUIRE(m->ndim == 2 || m->ndim == 3, FI_ERR_INVALID, "a mesh of %d-vertex primitives", m->ndim);
-	FI_REQUIRE(memory == FI_HOST || memory == FI_DEVICE, FI_ERR_INVALID, "bad memory kind %d", memory);
+	check_memory(memory);
 	FI_REQUIRE(cell > 0.0f, FI_ERR_INVALID, "cell must be > 0 (got %g)", static_cast<double>(cell));  // (false for a NaN)
 	FI_REQUIRE(placement == FI_SIMPLIFY_QUADRIC || placement == FI_SIMPLIFY_MEAN, FI_ERR_INVALID, "bad placement %d", placement);
 	FI_HIP_TRY(hipSetDevice(m->device));
@@ -580,23 +581,21 @@ void mesh_simplify(const fi_mesh* m, float cell, const float* origin, int placem
 	o->ndim        = m->ndim;
 	o->has_normals = m->has_normals;
 	hipStream_t st   = nullptr;
-	DevBuf      staged;
-	int*        dmap = vertex_map;
-	if (vertex_map && memory == FI_HOST && m->nv > 0) {
-		staged.alloc(sizeof(int) * m->nv);
-		dmap = staged.as<int>();
-	}
+	stage::Out<int> dmap(m->nv > 0 ? vertex_map : nullptr, m->nv, memory);
 	if (m->nv > 0 && m->np > 0) {
 		if (m->ndim == 2) {
 			simplify<2>(m, g, placement == FI_SIMPLIFY_QUADRIC, dmap, o.get(), st);
 		} else {
 			simplify<3>(m, g, placement == FI_SIMPLIFY_QUADRIC, dmap, o.get(), st);
 		}
-	} else if (dmap && m->nv > 0) {
+	} else if (dmap) {
 		FI_HIP_TRY(hipMemsetAsync(dmap, 0xff, sizeof(int) * m->nv, st));
 		FI_HIP_TRY(hipStreamSynchronize(st));
 	}
-	if (staged.p) { FI_HIP_TRY(hipMemcpy(vertex_map, staged.p, sizeof(int) * m->nv, hipMemcpyDeviceToHost)); }
+	if (dmap.host) {  // (the work above has ended; this copy has its own wait)
+		dmap.back(st);
+		FI_HIP_TRY(hipStreamSynchronize(st));
+	}
 	*out = o.release();
 }
 

@@ -355,11 +355,11 @@ void surface_query(const SurfaceIndex& t, int64_t n, const float* queries, float
 	if (n == 0) { return; }
 	AllocStream alloc_on(st);
 	Outputs o(n, t.D, distances, primitives, closest, memory);
-	DevBuf  bq;
+	stage::In<float> q(queries, n * t.D, memory, st);
 	QueryArgs a{};
 	a.t       = tree_of(t);
 	a.n       = n;
-	a.q       = stage_queries(queries, n, t.D, memory, bq, st);
+	a.q       = q;
 	a.lim     = limit_for(max_distance);
 	a.dist    = o.dist;
 	a.idx     = o.idx;

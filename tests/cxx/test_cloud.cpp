@@ -150,6 +150,31 @@ int main(int argc, char** argv)
 	        "fi_cloud_thin");
 	tp2.resize(3 * cells), tn2.resize(3 * cells), tc2.resize(cells), ti2.resize(cells);
 	require(cells > 0 && cells < n && same(tp, tp2) && same(tn, tn2) && same(tc, tc2) && same(ti, ti2) && same(map, map2), "... the same bytes");
+	{
+		// host memory, 65 points (one 64-lane wave and one more) in fewer cells than points: only num_out rows of the five
+		// per-cell outputs are the call's to write, the rows behind them keep what the caller had there
+		const int          few = 65;
+		const float        mark = -12345.0f;
+		std::vector<float> val(few, 2.0f), sp(3 * few, mark), sn(3 * few, mark), sv(few, mark);
+		std::vector<int>   sc(few, -7), smap(few, -7);
+		std::vector<long long> si(few, -7);
+		long               got = 0;
+		require(n >= few && fi_cloud_thin(3, few, pos.data(), nrm.data(), val.data(), 16.0f, origin.data(), FI_THIN_MEAN, sp.data(), sn.data(),
+		                                  sv.data(), sc.data(), si.data(), smap.data(), &got, FI_HOST) == FI_OK &&
+		            got > 0 && got < few,
+		        "fi_cloud_thin, 65 points in fewer cells");
+		bool written = true, kept_mark = true;
+		for (int c = 0; c < few; ++c) {
+			const bool mine = c < got;
+			const bool marked = sp[3 * c] == mark && sp[3 * c + 1] == mark && sp[3 * c + 2] == mark && sn[3 * c] == mark &&
+			                    sn[3 * c + 1] == mark && sn[3 * c + 2] == mark && sv[c] == mark && sc[c] == -7 && si[c] == -7;
+			if (mine) { written = written && sc[c] > 0 && si[c] >= 0 && sv[c] == 2.0f && sp[3 * c] != mark; }
+			if (!mine) { kept_mark = kept_mark && marked; }
+			written = written && smap[c] >= 0 && smap[c] < got;
+		}
+		require(written, "... num_out rows and the whole cell map are written");
+		require(kept_mark, "... the rows from num_out on keep the caller's bytes");
+	}
 	float* dp  = on_device(pos);
 	float* dn  = on_device(nrm);
 	float* dtp = on_device(pos);

@@ -112,6 +112,19 @@ int main(int argc, char** argv)
 		        "context, host field = in place");
 		fi_ctx_destroy(c);
 	}
+	{
+		// fi_upscale_field: the same bytes from host and from device buffers
+		const std::vector<int> large = {45, 37, 33};
+		const size_t           nl    = 45 * 37 * 33;
+		std::vector<float>     up(nl);
+		float*                 du = nullptr;
+		require(hipMalloc(reinterpret_cast<void**>(&du), nl * sizeof(float)) == hipSuccess, "hipMalloc upscaled");
+		require(fi_upscale_field(x.data(), 3, sizes.data(), large.data(), up.data(), FI_HOST) == FI_OK &&
+		            fi_upscale_field(dx, 3, sizes.data(), large.data(), du, FI_DEVICE) == FI_OK && same_bits(from_device(du, nl), up) &&
+		            up[0] == x[0],
+		        "fi_upscale_field, host = device buffers");
+		hipFree(du);
+	}
 	hipFree(dx);
 	hipFree(dp);
 	hipFree(dv);
