@@ -31,6 +31,7 @@ SYMBOLS = [
     "fi_orient_normals", "fi_points_orient_normals",
     "fi_radius_count", "fi_points_radius_count", "fi_neighbour_distances", "fi_points_neighbour_distances",
     "fi_outliers_statistical", "fi_points_outliers_statistical", "fi_outliers_radius", "fi_points_outliers_radius", "fi_cloud_thin",
+    "fi_mls_project", "fi_points_mls_project",
     "fi_cluster", "fi_points_cluster", "fi_cluster_measure", "fi_plane_fit", "fi_planes_segment",
     "fi_points_describe", "fi_feature_match", "fi_align_correspondences",
     "fi_surface_create", "fi_surface_from_mesh", "fi_surface_distance", "fi_surface_distance_field", "fi_surface_destroy",
@@ -254,6 +255,8 @@ def lib():
     L.fi_points_outliers_radius.argtypes = [vp, C.c_float, C.c_int, vp, C.POINTER(C.c_long), C.c_int]
     L.fi_cloud_thin.argtypes = [C.c_int, C.c_long, fp, fp, fp, C.c_float, C.POINTER(C.c_float), C.c_int, fp, fp, fp, vp, vp, vp,
                                 C.POINTER(C.c_long), C.c_int]
+    L.fi_mls_project.argtypes = [vp, C.c_long, fp, C.c_int, C.c_float, C.c_int, C.c_float, fp, fp, fp, fp, vp, C.c_int]
+    L.fi_points_mls_project.argtypes = [vp, C.c_long, fp, C.c_int, C.c_float, C.c_int, C.c_float, fp, fp, fp, fp, vp, C.c_int]
     L.fi_cluster.argtypes = [vp, C.c_float, C.c_int, vp, vp, C.POINTER(FiClusterStats), C.c_int]
     L.fi_points_cluster.argtypes = [vp, C.c_float, C.c_int, vp, vp, C.POINTER(FiClusterStats), C.c_int]
     L.fi_cluster_measure.argtypes = [C.c_int, C.c_long, fp, vp, vp, C.c_long, C.POINTER(FiClusterRow), C.c_int]

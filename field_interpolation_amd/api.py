@@ -635,6 +635,61 @@ def _propagated(index, call, ndim, n, k, max_distance, viewpoints, directions, v
     return (nrm, var) if variation else nrm
 
 
+_MLS_DOC = """(positions (n, ndim), normals (n, ndim)) float32 -- with curvature=True also the curvature (n,) float32, with
+        order=True also the order (n,) uint8, in that order -- of %s, each projected onto the surface fitted to its k nearest
+        points of the set within `radius` (moving least squares, weights (1 - d^2 / radius^2)^3): degree=1 a plane, degree=2 a
+        quadric over the plane's frame, in fp64 on the device.  The normal is the fitted surface's at the projected point, with
+        the sign that makes its largest component positive -- or, with normals= (n, ndim) given, the sign that agrees with
+        them, which is how normals oriented by orient_normals come back oriented; the curvature is the mean curvature (2-D:
+        the curve's) in 1 / length, positive where the surface bends towards the normal.  order says what was fitted: 2 the
+        quadric, 1 the plane (asked for, or because the neighbours do not determine a quadric), 0 nothing -- fewer than ndim
+        neighbours with a positive weight, or a non-finite point: such a point stays where it is with a zero normal and a NaN
+        curvature.  max_move limits how far a point may go.  The plane shrinks curved surfaces; the quadric does not, but it
+        needs neighbours: with k = 16 on a noisy surface it amplifies the noise, so keep k = 32 for degree 2, and a radius
+        that holds that many.  1 <= k <= 32.  The set itself is not changed: to go on with the smoothed cloud build a new
+        PointIndex from the positions.  numpy arrays, or torch tensors on the GPU %s (include/fi_hip.h
+        fi_mls_project)."""
+
+
+def _mls_project(call, ndim, n_own, queries, k, radius, degree, max_move, normals, curvature, order, device):
+    """Shared body of the moving-least-squares projection: call(n, queries, k, radius, degree, max_move, guides, positions,
+    normals, curvature, order, memory) is the C entry point; queries None: the set's own n_own points."""
+    k = _check_k(k)
+    if degree not in (1, 2):
+        raise ValueError("degree must be 1 or 2 (got %r)" % (degree,))
+    q, qmem, qkeep = _buf(queries)
+    if queries is None:
+        n = n_own
+    else:
+        count = qkeep.numel() if hasattr(qkeep, "numel") else qkeep.size
+        if count % ndim:
+            raise ValueError("queries: %d values, not a multiple of ndim = %d (x fastest)" % (count, ndim))
+        n = count // ndim
+    g, gmem, gkeep = _buf(normals)
+    if normals is not None:
+        count = gkeep.numel() if hasattr(gkeep, "numel") else gkeep.size
+        if count != n * ndim:
+            raise ValueError("normals: %d values for %d points of %d dimensions" % (count, n, ndim))
+    on_device = bool(device) or qmem == FI_DEVICE or gmem == FI_DEVICE
+    dev = None
+    if on_device:
+        import torch
+        dev = qkeep.device if qmem == FI_DEVICE else (gkeep.device if gmem == FI_DEVICE else "cuda")
+        if queries is not None and qmem != FI_DEVICE:
+            qkeep = torch.as_tensor(qkeep).to(dev)
+            q = C.c_void_p(qkeep.data_ptr())
+        if normals is not None and gmem != FI_DEVICE:
+            gkeep = torch.as_tensor(gkeep).to(dev)
+            g = C.c_void_p(gkeep.data_ptr())
+    pos, pp = _cloud_out(dev, (n, ndim), np.float32)
+    nrm, pn = _cloud_out(dev, (n, ndim), np.float32)
+    cur, pc = _cloud_out(dev, (n,), np.float32) if curvature else (None, None)
+    odr, po = _cloud_out(dev, (n,), np.uint8) if order else (None, None)
+    if n:
+        check(call(n, q, k, float(radius), int(degree), float(max_move), g, pp, pn, pc, po, FI_DEVICE if on_device else FI_HOST))
+    return (pos, nrm) + tuple(a for a in (cur, odr) if a is not None)
+
+
 def _distance_field(call, total, indices, device):
     """Shared body of the distance fields: call(distances, indices, memory); numpy arrays of `total` values (x fastest), or
     torch tensors on the current GPU with device=True."""
@@ -738,6 +793,26 @@ class PointIndex:
         def call(kk, md, m, kt, c, mem):
             return _capi.lib().fi_points_neighbour_distances(self._h, kk, md, m, kt, c, mem)
         return _neighbour_distances(call, self.num_points, k, max_distance, device)
+
+    def _mls_call(self, n, q, kk, r, deg, mm, g, pos, nrm, cur, odr, mem):
+        return _capi.lib().fi_points_mls_project(self._h, n, q, kk, r, deg, mm, g, pos, nrm, cur, odr, mem)
+
+    def smooth(self, k=32, radius=None, degree=2, max_move=math.inf, normals=None, curvature=False, order=False, device=False):
+        if radius is None:
+            raise ValueError("smooth needs a radius")
+        return _mls_project(self._mls_call, self.ndim, self.num_points, None, k, radius, degree, max_move, normals, curvature,
+                            order, device)
+    smooth.__doc__ = _MLS_DOC % ("the set's own points (num_points of them, a point being its own neighbour)",
+                                 "when `normals` is a device tensor or with device=True")
+
+    def project(self, queries, k=32, radius=None, degree=2, max_move=math.inf, normals=None, curvature=False, order=False,
+                device=False):
+        if radius is None:
+            raise ValueError("project needs a radius")
+        return _mls_project(self._mls_call, self.ndim, self.num_points, queries, k, radius, degree, max_move, normals, curvature,
+                            order, device)
+    project.__doc__ = _MLS_DOC % ("`queries` (n x ndim: any points -- a grid to resample a scan on, or more points than it has)",
+                                  "when `queries` or `normals` is a device tensor or with device=True")
 
     def describe(self, normals, k=32, max_distance=math.inf, device=False):
         """(features (num_points, 33) float32, valid (num_points,) bool): what every point's neighbourhood looks like as a
@@ -1444,8 +1519,17 @@ def register_global(source, source_normals, target, target_normals, threshold, k
     return alignment, register_points(source, target_index, target_normals=target_normals, initial=alignment["transform"], **keywords)
 
 
+def smooth_points(positions, radius, k=32, degree=2, max_move=math.inf, normals=None, curvature=False, order=False):
+    """PointIndex(positions).smooth(...): the cloud's points moved onto the local surface of their neighbours, with its normals
+    -- what reduces the measurement noise of a scan before estimate_normals / sdf_from_points.  numpy arrays, or torch CUDA
+    tensors that stay on the device."""
+    return PointIndex(positions).smooth(k=k, radius=radius, degree=degree, max_move=max_move, normals=normals, curvature=curvature,
+                                        order=order, device=bool(getattr(positions, "is_cuda", False)))
+
+
 def clean_points(positions, normals=None, values=None, cell=None, k=None, std_ratio=2.0, radius=None, min_neighbours=2,
-                 max_distance=math.inf, cluster_eps=None, cluster_min_points=1, largest=None, min_cluster=0, remove_planes=None):
+                 max_distance=math.inf, cluster_eps=None, cluster_min_points=1, largest=None, min_cluster=0, remove_planes=None,
+                 smooth=None):
     """A scan made fit for estimate_normals / sdf_from_points on the device, in this order and each step only if asked for:
     thin_points(cell) (mean mode), PointIndex.radius_outliers(radius, min_neighbours), PointIndex.statistical_outliers(k,
     std_ratio, max_distance).  Each filter builds its PointIndex over what the step before left.  numpy arrays, or torch
@@ -1457,7 +1541,10 @@ def clean_points(positions, normals=None, values=None, cell=None, k=None, std_ra
     step removed, and `clusters`, its stats.  remove_planes, a dict of segment_planes' arguments (threshold and max_planes at
     least), takes the floor or table a scan stands on out after the outlier rules and BEFORE the cluster step -- an object
     touches what it stands on, so clustering alone cannot part them: the points segment_planes labels go, and the report
-    gains `planes`, what the step removed, and `plane_models`, the models."""
+    gains `planes`, what the step removed, and `plane_models`, the models.  smooth, a dict of smooth_points' arguments (radius
+    at least), runs as the very last step on the points that are kept: their positions become smooth_points(positions,
+    normals=the kept normals, **smooth)'s, the normals (if any were given) the fitted surface's with the given normals' sign,
+    and the report gains `smoothed`, how many points were fitted (order >= 1), and `smooth_order`, each point's order."""
     as_array = lambda a: a if a is None or hasattr(a, "data_ptr") else np.ascontiguousarray(a, np.float32)  # noqa: E731
     pos, nrm, val = as_array(positions), as_array(normals), as_array(values)
     on_device = bool(getattr(pos, "is_cuda", False))
@@ -1500,6 +1587,15 @@ def clean_points(positions, normals=None, values=None, cell=None, k=None, std_ra
         report["cluster"] = _rows(pos) - int(keep.sum())
         report["clusters"] = stats
         pos, nrm, val = select(keep)
+    if smooth is not None:
+        args = dict(smooth)
+        args.pop("order", None)
+        args.pop("normals", None)
+        got = smooth_points(pos, normals=nrm, order=True, **args)
+        pos = got[0]
+        nrm = got[1] if nrm is not None else None
+        report["smooth_order"] = got[-1]
+        report["smoothed"] = int((got[-1] > 0).sum())
     report["output"] = _rows(pos)
     return pos, nrm, val, report
 
@@ -1949,6 +2045,26 @@ class LatticeField:
         def call(kk, md, m, kt, c, mem):
             return _capi.lib().fi_neighbour_distances(self._h, kk, md, m, kt, c, mem)
         return _neighbour_distances(call, self._point_count(), k, max_distance, device)
+
+    def _mls_call(self, n, q, kk, r, deg, mm, g, pos, nrm, cur, odr, mem):
+        return _capi.lib().fi_mls_project(self._h, n, q, kk, r, deg, mm, g, pos, nrm, cur, odr, mem)
+
+    def smooth(self, k=32, radius=None, degree=2, max_move=math.inf, normals=None, curvature=False, order=False, device=False):
+        """PointIndex.smooth of the data points of this context, in the order they were added (include/fi_hip.h
+        fi_mls_project).  The context's points stay as they are."""
+        if radius is None:
+            raise ValueError("smooth needs a radius")
+        return _mls_project(self._mls_call, len(self.sizes), self._point_count(), None, k, radius, degree, max_move, normals,
+                            curvature, order, device)
+
+    def project(self, queries, k=32, radius=None, degree=2, max_move=math.inf, normals=None, curvature=False, order=False,
+                device=False):
+        """PointIndex.project over the data points of this context (include/fi_hip.h fi_mls_project): the set and the search
+        structure are nearest()'s."""
+        if radius is None:
+            raise ValueError("project needs a radius")
+        return _mls_project(self._mls_call, len(self.sizes), self._point_count(), queries, k, radius, degree, max_move, normals,
+                            curvature, order, device)
 
     def statistical_outliers(self, k=8, std_ratio=2.0, max_distance=math.inf, device=False):
         """PointIndex.statistical_outliers of the data points of this context, in the order they were added

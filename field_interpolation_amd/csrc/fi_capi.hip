@@ -21,6 +21,7 @@
 #include "fi_cluster.h"
 #include "fi_plane.h"
 #include "fi_align.h"
+#include "fi_mls.h"
 #include "fi_feature.h"
 
 #include <memory>
@@ -1522,6 +1523,48 @@ int fi_points_estimate_normals(fi_points* h, int k, float max_distance, int orie
 	check_points(h);
 	check_normals(&h->t, h->t.D, k, max_distance, orient, guides, num_guides, normals, memory);
 	fi::estimate_normals(h->t, k, max_distance, orient, guides, num_guides, normals, variation, memory, nullptr);
+	FI_API_END
+}
+
+
+// ---- a point cloud made smooth: moving-least-squares projection (fi_mls.hip) ----------------------
+namespace {
+void check_mls(int ndim, long n, const float* queries, int k, float radius, int degree, float max_move, bool any_output, int memory)
+{
+	FI_REQUIRE(ndim >= 2, FI_ERR_INVALID, "a local surface needs 2 or 3 dimensions (got %d)", ndim);
+	check_k(k);
+	// (every comparison is false for a NaN)
+	FI_REQUIRE(radius > 0.0f && std::isfinite(radius), FI_ERR_INVALID, "radius must be > 0 and finite (got %g)", static_cast<double>(radius));
+	FI_REQUIRE(degree == 1 || degree == 2, FI_ERR_INVALID, "degree must be 1 or 2 (got %d)", degree);
+	FI_REQUIRE(max_move >= 0.0f, FI_ERR_INVALID, "max_move must be >= 0 (got %g)", static_cast<double>(max_move));
+	fi::check_memory(memory);
+	FI_REQUIRE(any_output, FI_ERR_INVALID, "every output is null");
+	if (!queries) { return; }
+	FI_REQUIRE(n >= 0, FI_ERR_INVALID, "n = %ld", n);
+	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld queries in one call", n);  // (one thread per query)
+}
+}  // namespace
+
+int fi_mls_project(fi_ctx* c, long n, const float* queries, int k, float radius, int degree, float max_move, const float* guide_normals,
+                   float* positions, float* normals, float* curvature, unsigned char* order, int memory)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	check_mls(c->g.ndim, n, queries, k, radius, degree, max_move, positions || normals || curvature || order, memory);
+	check_undivided(c);
+	fi::mls_project(fi::nearest_of(c), n, queries, k, radius, degree, max_move, guide_normals, positions, normals, curvature, order, memory,
+	                c->stream);
+	FI_API_END
+}
+
+int fi_points_mls_project(fi_points* h, long n, const float* queries, int k, float radius, int degree, float max_move,
+                          const float* guide_normals, float* positions, float* normals, float* curvature, unsigned char* order, int memory)
+{
+	FI_API_BEGIN
+	check_points(h);
+	check_mls(h->t.D, n, queries, k, radius, degree, max_move, positions || normals || curvature || order, memory);
+	fi::mls_project(h->t, n, queries, k, radius, degree, max_move, guide_normals, positions, normals, curvature, order, memory, nullptr);
 	FI_API_END
 }
 

@@ -11,6 +11,8 @@ namespace fi {
 struct NearestIndex : BvhIndex {
 	int     D = 0;
 	int64_t n = 0;   // points of the set (finite or not)
+	DevBuf  rest;    // the n - nf points left out of the tree, in no order: float4 each (x, y, z, the index as bits) -- what a
+	                 // unit that hands a set's own points back (fi_mls.hip) returns for them
 };
 
 // what the units that walk this tree share (fi_nearest.hip, fi_knn.hip): the points of a leaf ...

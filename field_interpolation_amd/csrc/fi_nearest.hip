@@ -52,6 +52,24 @@ struct PointItems {
 	}
 };
 
+// the points the tree leaves out (the non-finite ones), appended in whatever order the integer counter hands out: `room` of
+// them at the most
+__global__ __launch_bounds__(kThreads) void k_points_rest(int64_t n, int D, const float* __restrict__ pos, int64_t room, uint32_t* count,
+                                                            float4* __restrict__ rest)
+{
+	const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+	if (i >= n) { return; }
+	float p[3]   = {0.0f, 0.0f, 0.0f};
+	bool  finite = true;
+	for (int d = 0; d < D; ++d) {
+		p[d]   = pos[i * D + d];
+		finite = finite && isfinite(p[d]);
+	}
+	if (finite) { return; }
+	const uint32_t at = atomicAdd(count, 1u);
+	if (at < room) { rest[at] = make_float4(p[0], p[1], p[2], __uint_as_float(static_cast<uint32_t>(i))); }
+}
+
 // where the queries come from
 enum { kFromBuffer = 0, kFromLattice = 1, kFromList = 2 };
 
@@ -149,6 +167,16 @@ void nearest_build(NearestIndex& t, int D, int64_t n, const float* const* seg_po
 	case 1: build(t, PointItems<1>{pos}, n, st); break;
 	case 2: build(t, PointItems<2>{pos}, n, st); break;
 	default: build(t, PointItems<3>{pos}, n, st); break;
+	}
+	if (t.nf < n) {  // (a clean set never comes here)
+		DevBuf count;
+		count.alloc(sizeof(uint32_t));
+		t.rest.alloc(sizeof(float4) * (n - t.nf));
+		FI_HIP_TRY(hipMemsetAsync(count.p, 0, sizeof(uint32_t), st));
+		hipLaunchKernelGGL(k_points_rest, dim3(blocks_for(n)), dim3(kThreads), 0, st, n, D, pos, n - t.nf, count.as<uint32_t>(),
+		                   t.rest.as<float4>());
+		FI_HIP_TRY(hipGetLastError());
+		FI_HIP_TRY(hipStreamSynchronize(st));  // (`all` and the counter die here)
 	}
 }
 

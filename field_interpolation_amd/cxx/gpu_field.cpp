@@ -676,6 +676,65 @@ bool GpuLatticeField::cluster_points(float eps, int min_points, std::vector<int>
 	return true;
 }
 
+namespace {
+// the outputs of a moving-least-squares call sized for n points of D dimensions
+void size_mls(size_t n, size_t D, std::vector<float>* positions, std::vector<float>* normals, std::vector<float>* curvature,
+              std::vector<unsigned char>* order)
+{
+	if (positions) { positions->resize(D * n); }
+	if (normals) { normals->resize(D * n); }
+	if (curvature) { curvature->resize(n); }
+	if (order) { order->resize(n); }
+}
+}  // namespace
+
+bool GpuLatticeField::smooth_points(float radius, std::vector<float>* positions, std::vector<float>* normals, int k, int degree,
+                                    float max_move, const std::vector<float>& guide_normals, std::vector<float>* curvature,
+                                    std::vector<unsigned char>* order) const
+{
+	const size_t D = sizes_.size();
+	long         n = 0;
+	if ((!positions && !normals && !curvature && !order) || fi_point_count(ctx_, &n) != FI_OK ||
+	    (!guide_normals.empty() && guide_normals.size() != D * n)) {
+		warn("smooth_points");
+		return false;
+	}
+	size_mls(n, D, positions, normals, curvature, order);
+	if (n == 0) { return true; }  // (data() of an empty vector may be null: the library would take every output for missing)
+	if (fi_mls_project(ctx_, n, nullptr, k, radius, degree, max_move, guide_normals.empty() ? nullptr : guide_normals.data(),
+	                   positions ? positions->data() : nullptr, normals ? normals->data() : nullptr,
+	                   curvature ? curvature->data() : nullptr, order ? order->data() : nullptr, FI_HOST) != FI_OK) {
+		warn("smooth_points");
+		return false;
+	}
+	return true;
+}
+
+bool smooth_points(int ndim, const std::vector<float>& positions, float radius, std::vector<float>* out_positions,
+                   std::vector<float>* out_normals, int k, int degree, float max_move, const std::vector<float>& guide_normals,
+                   std::vector<float>* curvature, std::vector<unsigned char>* order)
+{
+	const auto refuse = [] {
+		std::fprintf(stderr, "field_interpolation: smooth_points: %s\n", fi_last_error());
+		return false;
+	};
+	if (ndim < 2 || ndim > 3 || positions.size() % ndim != 0 || (!out_positions && !out_normals && !curvature && !order) ||
+	    (!guide_normals.empty() && guide_normals.size() != positions.size())) {
+		return refuse();
+	}
+	const size_t n = positions.size() / ndim;
+	size_mls(n, ndim, out_positions, out_normals, curvature, order);
+	if (n == 0) { return true; }
+	fi_points* set = nullptr;
+	if (fi_points_create(&set, ndim, static_cast<long>(n), positions.data(), FI_HOST) != FI_OK) { return refuse(); }
+	const int rc = fi_points_mls_project(set, static_cast<long>(n), nullptr, k, radius, degree, max_move,
+	                                     guide_normals.empty() ? nullptr : guide_normals.data(),
+	                                     out_positions ? out_positions->data() : nullptr, out_normals ? out_normals->data() : nullptr,
+	                                     curvature ? curvature->data() : nullptr, order ? order->data() : nullptr, FI_HOST);
+	fi_points_destroy(set);
+	return rc == FI_OK ? true : refuse();
+}
+
 bool thin_points(int ndim, const std::vector<float>& positions, float cell, std::vector<float>* out_positions,
                  const std::vector<float>& normals, std::vector<float>* out_normals, const std::vector<float>& values,
                  std::vector<float>* out_values, const std::vector<float>& origin, bool first, std::vector<int>* out_counts,

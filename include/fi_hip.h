@@ -1017,8 +1017,8 @@ int fi_points_orient_normals(fi_points* points, int k, float max_distance, int a
  * num_out, out_normals without normals or out_values without values, a NaN or non-positive cell, a bad mode or memory kind, a
  * finite point with |c_a| >= 2^20.  n >= 2^31: FI_ERR_UNSUPPORTED.  A cell that holds the whole cloud is one thread's work:
  * slow and correct.
- * Not offered: lists of the neighbours within a radius, k > 32, a median / MAD threshold, moving-least-squares smoothing of
- * positions, slab contexts, approximate search. */
+ * Not offered: lists of the neighbours within a radius, k > 32, a median / MAD threshold, slab contexts, approximate search
+ * (smoothing of positions: fi_mls_project below). */
 #define FI_THIN_MEAN  0
 #define FI_THIN_FIRST 1
 typedef struct fi_outlier_stats {
@@ -1038,6 +1038,63 @@ int fi_points_outliers_radius(fi_points* points, float radius, int min_neighbour
 int fi_cloud_thin(int ndim, long n, const float* positions, const float* normals, const float* values, float cell,
                   const float* origin, int mode, float* out_positions, float* out_normals, float* out_values, int* out_counts,
                   long long* out_indices, int* cell_map, long* num_out, int memory);
+
+/* ---- a point cloud made smooth: moving-least-squares projection -------------------------------------
+ * The contract (tests/mls_reference.py is its definition in numpy).  Every query is projected onto a plane
+ * (degree 1) or a quadric (degree 2) fitted to its weighted neighbours, and gets that surface's normal and curvature.  The
+ * point set, s(p, q), finiteness and the search structure are fi_nearest's; ndim = 2 or 3 (D below).  The queries are
+ * `queries` (float[n * ndim]), or with queries == NULL the set's own points in point order (n is then not read: it is the
+ * set's count).  Everything but s is fp64, one rounding per operation over + - * / sqrt on fp32 inputs converted exactly;
+ * "the sum" of terms is 0.0 + the first + the second ..., in the order given.  h = (double)radius.  For a finite query q:
+ *   1. neighbours: the first k pairs (s, j) of fi_knn's order (s ascending in fp32, equal s by ascending index) with
+ *      sqrtf(s) <= radius, m of them, in that order -- "list order".  One of the set's own points finds itself (or a duplicate)
+ *      first: it is a neighbour, as in fi_estimate_normals;
+ *   2. weights: t = 1 - (double)s / (h h); t < 0 gives 0; w = (t t) t;
+ *   3. W = the sum of w; the centroid c_a = (the sum of w x_a) / W; with e = x - c the covariance sums a_xy = the sum of
+ *      (w e_x) e_y for x <= y, the other triangle copied, not divided by W; fi_estimate_normals' Jacobi iteration (step 3
+ *      there) on it as it stands;
+ *   4. the frame: n is the column of V whose diagonal entry of A is smallest (the lowest column on a tie), its component of
+ *      largest magnitude (the first such axis) made positive; the tangents t1 (, t2) are the remaining columns in ascending
+ *      column order, as they are.  Local coordinates of a point x: u = (the sum over ascending axes of e_a t1_a) / h, v
+ *      likewise with t2 (3-D only), z likewise with n;
+ *   5. refusal: m < D, or fewer than D weights > 0, or not W > 0: the point stays where it is -- order 0, position = q's bits,
+ *      normal all zeros, curvature NaN;
+ *   6. degree 2 and m >= NB, the basis b = (1, u, v, u u, u v, v v) in 3-D (NB = 6), (1, u, u u) in 2-D (NB = 3): the normal
+ *      equations m_rs = the sum of (w b_r) b_s for r <= s, f_r = the sum of (w b_r) z.  Unpivoted Cholesky, columns j
+ *      ascending: pivot d_j = m_jj - l_j0 l_j0 - ... - l_j,j-1 l_j,j-1, l_jj = sqrt(d_j), l_ij = (m_ji - l_i0 l_j0 - ... -
+ *      l_i,j-1 l_j,j-1) / l_jj for i > j ascending; y_i = (f_i - l_i0 y_0 - ... - l_i,i-1 y_i-1) / l_ii ascending;
+ *      x_i = (y_i - l_i+1,i x_i+1 - ... - l_NB-1,i x_NB-1) / l_ii descending.  If every d_j > 1e-15 W the coefficients are x
+ *      and order = 2; else, and for degree 1 or m < NB, they are all 0.0 and order = 1 (the plane);
+ *   7. projection, (u0, v0) the local coordinates of q.  3-D: p = ((((x0 + x1 u0) + x2 v0) + x3 (u0 u0)) + x4 (u0 v0)) +
+ *      x5 (v0 v0); pu = (x1 + (2 x3) u0) + x4 v0; pv = (x2 + x4 u0) + (2 x5) v0; x'_a = c_a + h ((u0 t1_a + v0 t2_a) + p n_a);
+ *      g_a = (n_a - pu t1_a) - pv t2_a; A = 1 + pu pu, B = 1 + pv pv, G = A + pv pv; curvature = ((B (2 x3) - ((2 pu) pv) x4) +
+ *      A (2 x5)) / ((2 h) (G sqrt(G))): the mean curvature of the graph, in 1 / length, positive where the surface bends
+ *      towards the normal.  2-D: p = (x0 + x1 u0) + x2 (u0 u0); pu = x1 + (2 x2) u0; x'_a = c_a + h (u0 t1_a + p n_a);
+ *      g_a = n_a - pu t1_a; G = 1 + pu pu; curvature = (2 x2) / (h (G sqrt(G))).  order 1: curvature = 0.0.  The normal is
+ *      g / sqrt(g_0 g_0 + g_1 g_1 (+ g_2 g_2));
+ *   8. guide_normals (float[n * ndim], one per query, or NULL): d = the sum over ascending axes of normal_a (double)guide_a; d
+ *      finite and < 0 negates the normal and the curvature: normals oriented by fi_orient_normals come back oriented;
+ *   9. max_move (>= 0; +inf: no limit), fi_mesh_smooth's rule: dl = x' - q, s2 = dl_0 dl_0 + dl_1 dl_1 (+ dl_2 dl_2); if
+ *      s2 > max_move max_move then x' = q + dl (max_move / sqrt(s2));
+ *  10. a non-finite x', normal or curvature: the outputs of step 5.  Otherwise positions, normals and curvature are the fp64
+ *      figures rounded to fp32.
+ * A non-finite query: position all NaN, order 0, normal zeros, curvature NaN.  A non-finite point of the set (queries ==
+ * NULL): its position's bits as they were given, order 0, normal zeros, curvature NaN.
+ * positions float[n * ndim], normals float[n * ndim], curvature float[n], order unsigned char[n]: any of them may be NULL,
+ * not all four.  Results depend neither on the launch shape nor on timing.  The plane shrinks a curved surface (a sphere of
+ * radius R by about the squared neighbourhood size over R); the quadric does not, but with few neighbours for its six
+ * coefficients (k = 16 on a noisy surface) it amplifies noise: keep k = 32 for degree 2.  The set's points are not moved: to go
+ * on with the smoothed cloud, build a new point set from `positions`.
+ * FI_ERR_INVALID: ndim = 1, k outside 1..32, a radius that is not > 0 and finite, a degree other than 1 or 2, a NaN or negative
+ * max_move, four NULL outputs, a bad memory kind, n < 0.  n >= 2^31: FI_ERR_UNSUPPORTED.  A slab context: FI_ERR_UNSUPPORTED,
+ * as for fi_nearest.  `memory` applies to every buffer of the call.
+ * Not offered: Gaussian weights, degree above 2, k > 32, iterated projection (call again on a new set), upsampling beyond
+ * caller-supplied queries, slab contexts. */
+int fi_mls_project(fi_ctx* ctx, long n, const float* queries, int k, float radius, int degree, float max_move,
+                   const float* guide_normals, float* positions, float* normals, float* curvature, unsigned char* order, int memory);
+int fi_points_mls_project(fi_points* points, long n, const float* queries, int k, float radius, int degree, float max_move,
+                          const float* guide_normals, float* positions, float* normals, float* curvature, unsigned char* order,
+                          int memory);
 
 /* ---- the clusters of a point cloud: Euclidean clusters and DBSCAN ------------------------------------
  * The contract (tests/cluster_reference.py is its definition in numpy).  The point set, s(p, q), finiteness

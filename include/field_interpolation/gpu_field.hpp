@@ -230,6 +230,17 @@ public:
 	// keep[i] = 1 where point i is finite and has at least min_neighbours other points within radius.  The contract is
 	// include/fi_hip.h fi_outliers_radius.
 	bool radius_outliers(float radius, int min_neighbours, std::vector<unsigned char>* keep, long* num_kept = nullptr) const;
+	// The data points, in the order they were added, each projected onto the plane (degree 1) or quadric (degree 2) fitted
+	// to its k nearest points within `radius` on the device (moving least squares): what takes the measurement noise off a
+	// scan.  positions, normals: ndim floats per point; curvature: the fitted surface's mean curvature, in 1 / length; order:
+	// 2 the quadric, 1 the plane, 0 nothing fitted (the point stays); any of the four may be null, not all.  guide_normals
+	// (ndim floats per point, or empty): the sign the normals come back with.  max_move limits how far a point may go.  The
+	// field's own points stay as they are.  With k = 16 on a noisy surface the quadric amplifies noise: keep k = 32 for
+	// degree 2.  The contract is include/fi_hip.h fi_mls_project.  false: the library refused the call.
+	bool smooth_points(float radius, std::vector<float>* positions, std::vector<float>* normals = nullptr, int k = 32, int degree = 2,
+	                   float max_move = std::numeric_limits<float>::infinity(),
+	                   const std::vector<float>& guide_normals = std::vector<float>(), std::vector<float>* curvature = nullptr,
+	                   std::vector<unsigned char>* order = nullptr) const;
 	// The clusters of the data points, in the order the points were added: labels[i] is point i's cluster, -1 for noise and
 	// for a non-finite point.  A point is core when min_points points, itself included, lie within eps of it (min_points = 1:
 	// plain Euclidean clustering); core points within eps of each other share a cluster, numbered by their lowest core point;
@@ -294,6 +305,14 @@ bool thin_points(int ndim, const std::vector<float>& positions, float cell, std:
                  const std::vector<float>& values = std::vector<float>(), std::vector<float>* out_values = nullptr,
                  const std::vector<float>& origin = std::vector<float>(), bool first = false, std::vector<int>* out_counts = nullptr,
                  std::vector<long long>* out_indices = nullptr, std::vector<int>* cell_map = nullptr);
+
+// GpuLatticeField::smooth_points of a point cloud of its own, no lattice needed (ndim = 2 or 3; positions: ndim floats per
+// point): every point projected onto the local surface of its neighbours.  The contract is include/fi_hip.h fi_mls_project.
+bool smooth_points(int ndim, const std::vector<float>& positions, float radius, std::vector<float>* out_positions,
+                   std::vector<float>* out_normals = nullptr, int k = 32, int degree = 2,
+                   float max_move = std::numeric_limits<float>::infinity(),
+                   const std::vector<float>& guide_normals = std::vector<float>(), std::vector<float>* curvature = nullptr,
+                   std::vector<unsigned char>* order = nullptr);
 
 // The dominant plane (ndim = 3) or line (ndim = 2) of a point cloud on the device, no lattice needed: RANSAC with an exact
 // inlier count (a point within `threshold` of the plane, inclusive, is an inlier), then `refine` least-squares refits.
