@@ -7,7 +7,7 @@ GPU; importing the API without the built library raises ImportError (no CPU fall
 from .api import (GradientKernel, IsoMesh, LatticeField, LatticeGroup, MeshParts, PointIndex, SolveOptions, SurfaceIndex,  # noqa: F401
                   ValueKernel, Weights, dual_contour, generate_error_map, iso_surface, jacobi_iterations, keep_parts, merge_meshes, mesh_parts, mesh_to_sdf, redistance, sample_field, select_parts,
                   simplify_mesh, smooth_mesh, mesh_normals, sample_mesh, mesh_deviation, register_points, apply_transform, thin_points, clean_points, smooth_points,
-                  cluster_points, cluster_measure, keep_clusters, segment_plane, segment_planes,
+                  cluster_points, cluster_measure, keep_clusters, segment_plane, segment_planes, segment_sphere, segment_cylinder, segment_shapes,
                   match_features, align_correspondences, register_global,
                   sdf_from_points, sdf_from_unoriented_points, solve_sparse_linear_exact, solve_sparse_linear_with_guess, solve_tiled_with_guess, upscale_field)
 from ._capi import FiError, memory_pool  # noqa: F401

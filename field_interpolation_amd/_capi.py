@@ -33,6 +33,7 @@ SYMBOLS = [
     "fi_outliers_statistical", "fi_points_outliers_statistical", "fi_outliers_radius", "fi_points_outliers_radius", "fi_cloud_thin",
     "fi_mls_project", "fi_points_mls_project",
     "fi_cluster", "fi_points_cluster", "fi_cluster_measure", "fi_plane_fit", "fi_planes_segment",
+    "fi_shape_fit", "fi_shapes_segment",
     "fi_points_describe", "fi_feature_match", "fi_align_correspondences",
     "fi_surface_create", "fi_surface_from_mesh", "fi_surface_distance", "fi_surface_distance_field", "fi_surface_destroy",
     "fi_surface_raycast", "fi_surface_count_hits", "fi_surface_contains", "fi_surface_signed_distance",
@@ -44,6 +45,7 @@ FI_LOSS = {"huber": 0, "cauchy": 1, "tukey": 2}
 FI_LOSS_NONE = -1
 FI_REGISTER = {"plane": 0, "point": 1}
 FI_THIN = {"mean": 0, "first": 1}
+FI_SHAPE = {"sphere": 0, "cylinder": 1}
 
 
 class FiWeights(C.Structure):
@@ -133,6 +135,17 @@ class FiPlaneOptions(C.Structure):
 class FiPlaneModel(C.Structure):
     _fields_ = [("found", C.c_int), ("refits", C.c_int), ("inliers", C.c_long), ("candidates", C.c_long), ("trials", C.c_long),
                 ("normal", C.c_double * 3), ("offset", C.c_double), ("rms", C.c_double)]
+
+
+class FiShapeOptions(C.Structure):
+    _fields_ = [("kind", C.c_int), ("threshold", C.c_float), ("r_min", C.c_float), ("r_max", C.c_float), ("normal_cos", C.c_float),
+                ("max_trials", C.c_long), ("confidence", C.c_double), ("refine", C.c_int), ("seed", C.c_ulonglong)]
+
+
+class FiShapeModel(C.Structure):
+    _fields_ = [("found", C.c_int), ("kind", C.c_int), ("refits", C.c_int), ("inliers", C.c_long), ("candidates", C.c_long),
+                ("trials", C.c_long), ("center", C.c_double * 3), ("axis", C.c_double * 3), ("radius", C.c_double),
+                ("extent", C.c_double * 2), ("rms", C.c_double)]
 
 
 class FiAlignOptions(C.Structure):
@@ -263,6 +276,9 @@ def lib():
     L.fi_plane_fit.argtypes = [C.c_int, C.c_long, fp, vp, C.POINTER(FiPlaneOptions), C.POINTER(FiPlaneModel), vp, C.c_int]
     L.fi_planes_segment.argtypes = [C.c_int, C.c_long, fp, vp, C.POINTER(FiPlaneOptions), C.c_int, C.c_long, vp,
                                     C.POINTER(FiPlaneModel), ip, C.c_int]
+    L.fi_shape_fit.argtypes = [C.c_int, C.c_long, fp, fp, vp, C.POINTER(FiShapeOptions), C.POINTER(FiShapeModel), vp, C.c_int]
+    L.fi_shapes_segment.argtypes = [C.c_int, C.c_long, fp, fp, vp, C.POINTER(FiShapeOptions), C.c_int, C.c_long, vp,
+                                    C.POINTER(FiShapeModel), ip, C.c_int]
     L.fi_points_describe.argtypes = [vp, fp, C.c_int, C.c_float, fp, vp, C.c_int]
     L.fi_feature_match.argtypes = [C.c_int, C.c_long, fp, vp, C.c_long, fp, vp, vp, fp, C.c_int]
     L.fi_align_correspondences.argtypes = [C.c_long, fp, C.c_long, fp, C.c_long, vp, vp, C.POINTER(FiAlignOptions),

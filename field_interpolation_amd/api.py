@@ -1410,6 +1410,90 @@ def segment_planes(positions, threshold, max_planes, min_inliers=0, max_trials=1
     return labels, [_plane_dict(rows[i], ndim) for i in range(found.value)]
 
 
+def _shape_options(kind, threshold, r_min, r_max, has_normals, max_angle, max_trials, confidence, refine, seed):
+    if kind not in _capi.FI_SHAPE:
+        raise ValueError("kind is 'sphere' or 'cylinder', not %r" % (kind,))
+    normal_cos = 0.0
+    if max_angle is not None:
+        if not has_normals:
+            raise ValueError("max_angle needs normals")
+        if not 0.0 <= float(max_angle) < 90.0:
+            raise ValueError("max_angle is in degrees, 0 .. 90 (90 excluded: leave it out)")
+        normal_cos = float(np.float32(math.cos(math.radians(float(max_angle)))))   # no trigonometry on the device
+    return _capi.FiShapeOptions(_capi.FI_SHAPE[kind], float(threshold), float(r_min), float(r_max), normal_cos, int(max_trials),
+                                float(confidence), int(refine), int(seed) & (2 ** 64 - 1))
+
+
+def _shape_dict(m, ndim, kind):
+    out = {"found": bool(m.found), "kind": kind,
+           "center": np.array(m.center[:ndim], np.float64), "radius": float(m.radius), "inliers": int(m.inliers),
+           "candidates": int(m.candidates), "trials": int(m.trials), "refits": int(m.refits), "rms": float(m.rms)}
+    if kind == "cylinder":
+        out["axis"] = np.array(m.axis[:], np.float64)
+        out["extent"] = np.array(m.extent[:], np.float64)
+    return out
+
+
+def _shape_cloud(positions, normals, mask):
+    p, mk, n, ndim, mem, keep = _plane_cloud(positions, mask)
+    nr, nmem, nkeep = _buf(normals)
+    if normals is not None and tuple(nkeep.shape) != (n, ndim):
+        raise ValueError("normals is (%d, %d), one per point" % (n, ndim))
+    return p, nr, mk, n, ndim, _same_memory(mem, nmem), keep + (nkeep,)
+
+
+def _segment_shape(kind, positions, normals, threshold, r_min, r_max, max_angle, max_trials, confidence, refine, seed, mask):
+    p, nr, mk, n, ndim, mem, keep = _shape_cloud(positions, normals, mask)
+    opt = _shape_options(kind, threshold, r_min, r_max, normals is not None, max_angle, max_trials, confidence, refine, seed)
+    model = _capi.FiShapeModel()
+    out, ptr = _cloud_out(keep[0].device if mem == FI_DEVICE else None, (n,), np.uint8)
+    check(_capi.lib().fi_shape_fit(ndim, n, p if n else None, nr if n else None, mk if n else None, C.byref(opt), C.byref(model), ptr, mem))
+    return _shape_dict(model, ndim, kind), _as_mask(out)
+
+
+def segment_sphere(positions, threshold, r_min=0.0, r_max=math.inf, normals=None, max_angle=None, max_trials=1024, confidence=0.999,
+                   refine=2, seed=0, mask=None):
+    """The dominant sphere (3-D) or circle (2-D) of a point cloud on the device: RANSAC with an exact inlier count, then
+    `refine` algebraic least-squares refits.  positions (n, ndim), a numpy array or a torch CUDA tensor that stays on the device;
+    a point whose distance from the sphere is within `threshold` (inclusive) is an inlier.  Only radii in [r_min, r_max] are
+    considered.  normals (n, ndim), optional: points without a usable normal take no part, and with max_angle (degrees) an
+    inlier's normal must also lie within that angle of the sphere's, either way round.  At most max_trials hypotheses, fewer
+    once the best one would have been drawn with probability `confidence` (0: never stop early); mask (n,): the points that
+    take part.  -> (model, inliers): a dict with `found`, `kind`, `center` (float64 (ndim,)), `radius`, `inliers`, `candidates`,
+    `trials`, `refits` and `rms`, and a boolean mask (n,) where `positions` lives.  Every figure is defined bit for bit
+    (include/fi_hip.h fi_shape_fit)."""
+    return _segment_shape("sphere", positions, normals, threshold, r_min, r_max, max_angle, max_trials, confidence, refine, seed, mask)
+
+
+def segment_cylinder(positions, normals, threshold, r_min=0.0, r_max=math.inf, max_angle=None, max_trials=1024, confidence=0.999,
+                     refine=2, seed=0, mask=None):
+    """The dominant cylinder of a 3-D point cloud with normals on the device: two points and their normals make a hypothesis
+    (the axis across both normals, through the point the two normal lines come closest at), scored and refitted as
+    segment_sphere's.  -> (model, inliers): segment_sphere's dict with `kind` 'cylinder', `center` a point of the axis, and two
+    more entries: `axis` (float64 (3,), its largest component positive) and `extent`, the least and the greatest
+    (x - center) . axis over the inliers (include/fi_hip.h fi_shape_fit)."""
+    if normals is None:
+        raise ValueError("a cylinder needs normals")
+    return _segment_shape("cylinder", positions, normals, threshold, r_min, r_max, max_angle, max_trials, confidence, refine, seed, mask)
+
+
+def segment_shapes(positions, kind, threshold, max_shapes, min_inliers=0, normals=None, r_min=0.0, r_max=math.inf, max_angle=None,
+                   max_trials=1024, confidence=0.999, refine=2, seed=0, mask=None):
+    """Up to max_shapes shapes of one `kind` ('sphere' or 'cylinder') peeled off a point cloud on the device, one after the
+    other: shape p is segment_sphere / segment_cylinder with seed + p over the points no earlier shape took; the loop ends at
+    the first shape with fewer than min_inliers inliers, which is not recorded.  -> (labels, models): labels (n,) int32 where
+    `positions` lives, the shape that took each point or -1, and the list of model dicts (include/fi_hip.h
+    fi_shapes_segment)."""
+    p, nr, mk, n, ndim, mem, keep = _shape_cloud(positions, normals, mask)
+    opt = _shape_options(kind, threshold, r_min, r_max, normals is not None, max_angle, max_trials, confidence, refine, seed)
+    rows = (_capi.FiShapeModel * max(int(max_shapes), 1))()
+    found = C.c_int(0)
+    labels, ptr = _cloud_out(keep[0].device if mem == FI_DEVICE else None, (n,), np.int32)
+    check(_capi.lib().fi_shapes_segment(ndim, n, p if n else None, nr if n else None, mk if n else None, C.byref(opt), int(max_shapes),
+                                        int(min_inliers), ptr, rows, C.byref(found), mem))
+    return labels, [_shape_dict(rows[i], ndim, kind) for i in range(found.value)]
+
+
 def _match(a, b, valid_a, valid_b, distances):
     pa, amem, akeep = _buf(a)
     pb, bmem, bkeep = _buf(b)

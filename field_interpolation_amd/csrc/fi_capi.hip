@@ -20,6 +20,7 @@
 #include "fi_cloud.h"
 #include "fi_cluster.h"
 #include "fi_plane.h"
+#include "fi_shape.h"
 #include "fi_align.h"
 #include "fi_mls.h"
 #include "fi_feature.h"
@@ -1804,6 +1805,59 @@ int fi_planes_segment(int ndim, long n, const float* positions, const unsigned c
 	FI_REQUIRE(rows != nullptr && (n == 0 || labels != nullptr), FI_ERR_INVALID, "null labels or rows");
 	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld points in one call", n);
 	fi::planes_segment(ndim, n, positions, mask, *opt, max_planes, min_inliers, labels, rows, num_planes, memory);
+	FI_API_END
+}
+
+
+// ---- the spheres and cylinders of a point cloud (fi_shape.hip) ------------------------------------
+namespace {
+void check_shape(int ndim, long n, const float* positions, const float* normals, const fi_shape_options* opt, int memory)
+{
+	FI_REQUIRE(2 <= ndim && ndim <= FI_MAX_DIM, FI_ERR_INVALID, "ndim must be 2..%d (got %d)", FI_MAX_DIM, ndim);
+	FI_REQUIRE(n >= 0, FI_ERR_INVALID, "n = %ld", n);
+	FI_REQUIRE(n == 0 || positions != nullptr, FI_ERR_INVALID, "positions is null");
+	FI_REQUIRE(opt != nullptr, FI_ERR_INVALID, "opt is null");
+	FI_REQUIRE(opt->kind == FI_SHAPE_SPHERE || opt->kind == FI_SHAPE_CYLINDER, FI_ERR_INVALID, "unknown shape kind %d", opt->kind);
+	FI_REQUIRE(opt->kind != FI_SHAPE_CYLINDER || ndim == 3, FI_ERR_UNSUPPORTED, "a cylinder needs ndim = 3 (got %d)", ndim);
+	FI_REQUIRE(opt->kind != FI_SHAPE_CYLINDER || n == 0 || normals != nullptr, FI_ERR_INVALID, "a cylinder needs normals");
+	FI_REQUIRE(opt->threshold >= 0.0f && !std::isinf(opt->threshold), FI_ERR_INVALID, "threshold must be finite and >= 0 (got %g)",
+	           static_cast<double>(opt->threshold));  // (NaN fails)
+	FI_REQUIRE(opt->r_min >= 0.0f && opt->r_max >= opt->r_min, FI_ERR_INVALID, "the radius limits must be 0 <= r_min <= r_max (got %g, %g)",
+	           static_cast<double>(opt->r_min), static_cast<double>(opt->r_max));  // (a NaN fails)
+	FI_REQUIRE(opt->normal_cos >= 0.0f && opt->normal_cos <= 1.0f, FI_ERR_INVALID, "normal_cos must be in [0, 1] (got %g)",
+	           static_cast<double>(opt->normal_cos));
+	FI_REQUIRE(!(opt->normal_cos > 0.0f) || n == 0 || normals != nullptr, FI_ERR_INVALID, "normal_cos > 0 needs normals");
+	FI_REQUIRE(1 <= opt->max_trials && opt->max_trials <= (1L << 20), FI_ERR_INVALID, "max_trials must be 1..2^20 (got %ld)", opt->max_trials);
+	FI_REQUIRE(opt->confidence >= 0.0 && opt->confidence < 1.0, FI_ERR_INVALID, "confidence must be in [0, 1) (got %g)", opt->confidence);
+	FI_REQUIRE(0 <= opt->refine && opt->refine <= 16, FI_ERR_INVALID, "refine must be 0..16 (got %d)", opt->refine);
+	fi::check_memory(memory);
+}
+}  // namespace
+
+int fi_shape_fit(int ndim, long n, const float* positions, const float* normals, const unsigned char* mask, const fi_shape_options* opt,
+                 fi_shape_model* model, unsigned char* inliers, int memory)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(model != nullptr, FI_ERR_INVALID, "model is null");
+	*model = fi_shape_model{};
+	check_shape(ndim, n, positions, normals, opt, memory);
+	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld points in one call", n);
+	fi::shape_fit(ndim, n, positions, normals, mask, *opt, model, inliers, memory);
+	FI_API_END
+}
+
+int fi_shapes_segment(int ndim, long n, const float* positions, const float* normals, const unsigned char* mask, const fi_shape_options* opt,
+                      int max_shapes, long min_inliers, int* labels, fi_shape_model* rows, int* num_shapes, int memory)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(num_shapes != nullptr, FI_ERR_INVALID, "num_shapes is null");
+	*num_shapes = 0;
+	check_shape(ndim, n, positions, normals, opt, memory);
+	FI_REQUIRE(max_shapes >= 1, FI_ERR_INVALID, "max_shapes must be >= 1 (got %d)", max_shapes);
+	FI_REQUIRE(min_inliers >= 0, FI_ERR_INVALID, "min_inliers must be >= 0 (got %ld)", min_inliers);
+	FI_REQUIRE(rows != nullptr && (n == 0 || labels != nullptr), FI_ERR_INVALID, "null labels or rows");
+	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld points in one call", n);
+	fi::shapes_segment(ndim, n, positions, normals, mask, *opt, max_shapes, min_inliers, labels, rows, num_shapes, memory);
 	FI_API_END
 }
 

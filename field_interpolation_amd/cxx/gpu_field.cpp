@@ -838,6 +838,78 @@ bool segment_planes(int ndim, const std::vector<float>& positions, float thresho
 	return true;
 }
 
+namespace {
+static_assert(sizeof(ShapeModel) == sizeof(fi_shape_model), "ShapeModel mirrors fi_shape_model");
+
+bool shape_options(int ndim, Shape kind, size_t floats, size_t normal_floats, float threshold, float r_min, float r_max, float normal_cos,
+                   long max_trials, double confidence, int refine, unsigned long long seed, const std::vector<unsigned char>& mask,
+                   fi_shape_options* opt)
+{
+	if (ndim < 2 || ndim > 3 || floats % ndim != 0) { return false; }
+	if ((!mask.empty() && mask.size() != floats / ndim) || (normal_floats != 0 && normal_floats != floats)) { return false; }
+	*opt            = fi_shape_options{};
+	opt->kind       = static_cast<int>(kind);
+	opt->threshold  = threshold;
+	opt->r_min      = r_min;
+	opt->r_max      = r_max;
+	opt->normal_cos = normal_cos;
+	opt->max_trials = max_trials;
+	opt->confidence = confidence;
+	opt->refine     = refine;
+	opt->seed       = seed;
+	return true;
+}
+}  // namespace
+
+bool segment_shape(int ndim, Shape kind, const std::vector<float>& positions, const std::vector<float>& normals, float threshold,
+                   ShapeModel* model, std::vector<unsigned char>* inliers, float r_min, float r_max, float normal_cos, long max_trials,
+                   double confidence, int refine, unsigned long long seed, const std::vector<unsigned char>& mask)
+{
+	fi_shape_options opt;
+	fi_shape_model   m;
+	if (!model || !shape_options(ndim, kind, positions.size(), normals.size(), threshold, r_min, r_max, normal_cos, max_trials, confidence,
+	                             refine, seed, mask, &opt)) {
+		std::fprintf(stderr, "field_interpolation: segment_shape: bad arguments\n");
+		return false;
+	}
+	const size_t n = positions.size() / ndim;
+	if (inliers) { inliers->resize(n); }
+	if (fi_shape_fit(ndim, static_cast<long>(n), positions.data(), normals.empty() ? nullptr : normals.data(),
+	                 mask.empty() ? nullptr : mask.data(), &opt, &m, inliers && n ? inliers->data() : nullptr, FI_HOST) != FI_OK) {
+		std::fprintf(stderr, "field_interpolation: segment_shape: %s\n", fi_last_error());
+		return false;
+	}
+	std::memcpy(model, &m, sizeof(m));
+	return true;
+}
+
+bool segment_shapes(int ndim, Shape kind, const std::vector<float>& positions, const std::vector<float>& normals, float threshold,
+                    int max_shapes, std::vector<int>* labels, std::vector<ShapeModel>* models, long min_inliers, float r_min, float r_max,
+                    float normal_cos, long max_trials, double confidence, int refine, unsigned long long seed,
+                    const std::vector<unsigned char>& mask)
+{
+	fi_shape_options opt;
+	if (!labels || !models || max_shapes < 1 ||
+	    !shape_options(ndim, kind, positions.size(), normals.size(), threshold, r_min, r_max, normal_cos, max_trials, confidence, refine, seed,
+	                   mask, &opt)) {
+		std::fprintf(stderr, "field_interpolation: segment_shapes: bad arguments\n");
+		return false;
+	}
+	const size_t n = positions.size() / ndim;
+	labels->resize(n);
+	std::vector<fi_shape_model> rows(static_cast<size_t>(max_shapes));
+	int                         found = 0;
+	if (fi_shapes_segment(ndim, static_cast<long>(n), positions.data(), normals.empty() ? nullptr : normals.data(),
+	                      mask.empty() ? nullptr : mask.data(), &opt, max_shapes, min_inliers, n ? labels->data() : nullptr, rows.data(), &found,
+	                      FI_HOST) != FI_OK) {
+		std::fprintf(stderr, "field_interpolation: segment_shapes: %s\n", fi_last_error());
+		return false;
+	}
+	models->resize(static_cast<size_t>(found));
+	if (found > 0) { std::memcpy(models->data(), rows.data(), sizeof(fi_shape_model) * found); }
+	return true;
+}
+
 static_assert(sizeof(Alignment) == sizeof(fi_alignment), "Alignment mirrors fi_alignment");
 
 bool describe_points(const std::vector<float>& positions, const std::vector<float>& normals, std::vector<float>* features,

@@ -1189,8 +1189,8 @@ int fi_cluster_measure(int ndim, long n, const float* positions, const int* labe
  * outside [0, 1); refine outside 0 .. 16; min_cos outside [0, 1]; min_cos > 0 with a zero or non-finite axis; a bad memory
  * kind; NULL required pointers (opt, model / labels, rows, num_planes; positions with n > 0); max_planes < 1;
  * min_inliers < 0.  n >= 2^31: FI_ERR_UNSUPPORTED.
- * Not offered: spheres, cylinders and other models; MSAC / MLESAC scores; per-point normals in the inlier test; region
- * growing by normals; slab contexts. */
+ * Spheres, cylinders and per-point normals in the inlier test: fi_shape_fit / fi_shapes_segment below.
+ * Not offered: cones, tori and other models; MSAC / MLESAC scores; region growing by normals; slab contexts. */
 #define FI_PLANE_BATCH 1024
 typedef struct fi_plane_options {
 	float              threshold;
@@ -1210,6 +1210,88 @@ int fi_plane_fit(int ndim, long n, const float* positions, const unsigned char* 
                  fi_plane_model* model, unsigned char* inliers, int memory);
 int fi_planes_segment(int ndim, long n, const float* positions, const unsigned char* mask, const fi_plane_options* opt,
                       int max_planes, long min_inliers, int* labels, fi_plane_model* rows, int* num_planes, int memory);
+
+/* ---- the spheres and cylinders of a point cloud: RANSAC with refits ------------------------------
+ * The contract (tests/shape_reference.py is its definition in numpy) is this project's own.  fi_shape_fit
+ * fits one shape of opt->kind to positions float[n * ndim]: FI_SHAPE_SPHERE a sphere |x - c| = r (a circle with ndim = 2),
+ * FI_SHAPE_CYLINDER a cylinder |(x - q) - ((x - q) . a) a| = r (ndim = 3 only); fi_shapes_segment peels several off, one after
+ * the other.  normals float[n * ndim] may be NULL for a sphere; a cylinder's hypotheses and refits are made of them.
+ * positions, normals, mask, inliers and labels lie in `memory`, the models on the HOST; the calls run on the current device.
+ * Everything is fp64 computed from the fp32 inputs, one rounding per operation (no FMA contraction), over + - * / sqrt, fabs
+ * and compares; there are no float atomics, and every output is defined bit for bit, whatever the launch shape and the
+ * timing.  a . b is the sum of the products over ascending axes.
+ *   - candidates: point i is one iff all its coordinates are finite, mask is NULL or mask[i] != 0 and, where normals are
+ *     passed, every component of its normal is finite and len = sqrt(n . n) is finite and > 0 (fi_points_describe's length);
+ *     its unit normal is u = n / len per component.  In ascending index they form the list cand[0 .. m).  With S = 4 (sphere,
+ *     3-D), 3 (circle) or 2 (cylinder) the points a hypothesis draws: m < S gives found = 0, trials = 0;
+ *   - hypothesis h = 0 .. max_trials - 1 draws S list positions j_k = min(floor(u(seed, h S + k) m), m - 1) by fi_plane_fit's
+ *     counter hash; p_k and u_k are the drawn points and their unit normals.
+ *     Sphere: q_k = p_k - p_0 and h_k = 0.5 (q_k . q_k) for k = 1 .. D; c' solves M c' = h, M's rows being the q_k, by
+ *     Cramer's rule: 2-D det = M00 M11 - M01 M10, x_0 = (M11 h_0 - M01 h_1) / det, x_1 = (M00 h_1 - M10 h_0) / det; 3-D the
+ *     cofactors C_ij = M_i'j' M_i"j" - M_i'j" M_i"j' with i' = (i + 1) mod 3, i" = (i + 2) mod 3 (and so j), det =
+ *     (M00 C00 + M01 C01) + M02 C02, x_j = ((C0j h_0 + C1j h_1) + C2j h_2) / det.  Invalid when det is not finite or is 0.
+ *     c = p_0 + c', r = sqrt(c' . c').
+ *     Cylinder: a = u_0 x u_1, each component the difference of two products (u0_1 u1_2 - u0_2 u1_1, u0_2 u1_0 - u0_0 u1_2,
+ *     u0_0 u1_1 - u0_1 u1_0); len = sqrt(a . a), invalid unless finite and > 0; a = a / len.  d = p_1 - p_0, g00 = u_0 . u_0,
+ *     g01 = u_0 . u_1, g11 = u_1 . u_1, b0 = u_0 . d, b1 = u_1 . d, det = g00 g11 - g01 g01, invalid unless finite and != 0;
+ *     s = (b0 g11 - g01 b1) / det; the axis point q = p_0 + s u_0 per component; r = fabs(s).
+ *     Both: invalid when two of the j_k are equal, and unless r is finite and (double)r_min <= r <= (double)r_max (r_max =
+ *     +inf: no upper limit).  An invalid hypothesis scores -1;
+ *   - band, once a model: lo = r - (double)threshold, 0 where that is not > 0; lo2 = lo lo; hi = r + threshold; hi2 = hi hi;
+ *   - score, no square root: sphere g = x - c; cylinder v = x - q, t = v . a, g = v - t a; s_i = g . g.  Candidate i is an
+ *     inlier iff lo2 <= s_i <= hi2 -- a point exactly on either edge is in -- and, with normal_cos > 0, also s_i > 0 and
+ *     (u_i . g)^2 >= (mc mc) s_i, mc = (double)normal_cos: the point's normal lies within that angle of the shape's, either
+ *     way round.  The score is the exact count; ties, the batches of FI_SHAPE_BATCH, the stop rule (with this S as the
+ *     exponent: p = w multiplied by w S - 1 times), trials and candidates are fi_plane_fit's;
+ *   - refits, `refine` times, over the current inliers in ascending index, every sum fi_plane_fit's tree_sum:
+ *     m_a = tree_sum(x_a) / count, y = x - m.  Sphere (Kasa), in F = D dimensions: w = y . y; the sums A_ab = tree_sum(y_a y_b)
+ *     (a <= b, mirrored), B_a = tree_sum(y_a w), W = tree_sum(w); c' solves A c' = 0.5 B by the Cramer routine above;
+ *     c = m + c'; r = sqrt(c' . c' + W / count).  Cylinder: N_ab = tree_sum(u_a u_b) of the members' unit normals (a <= b,
+ *     mirrored, not centred); fi_estimate_normals' Jacobi iteration (6 sweeps) of N; the new axis is the column with the
+ *     smallest diagonal entry, the lowest column on a tie, NOT renormalised; e_1, e_2 are the other two columns in ascending
+ *     column order; then the same Kasa sums in F = 2 dimensions over f = (y . e_1, y . e_2), their solution (c_u, c_v),
+ *     q = (m + c_u e_1) + c_v e_2 per component, r = sqrt((c_u c_u + c_v c_v) + W / count).  The inliers are then counted
+ *     again over all candidates.  A refit is skipped, and the refits end, when count < S + 1, the determinant is not finite
+ *     or is 0, a figure of the new model or of the frame is not finite, or the new r leaves [r_min, r_max].  A refit is not
+ *     conditional on the count going up.  refits reports how many ran;
+ *   - result: center is c (sphere; unused axes 0) or q (cylinder); radius is r; axis is a with fi_estimate_normals' canonical
+ *     sign (the component of largest magnitude, the first such axis, is positive), zeros for a sphere; extent is the least
+ *     and the greatest (x - q) . axis over the final inliers (zeros for a sphere or with none); rms =
+ *     sqrt(tree_sum((sqrt(s_i) - r)^2) / inliers), 0 with none; inliers (unsigned char[n] or NULL) is one byte per input
+ *     point from the final model; kind repeats opt->kind.  found = 0 leaves every figure but candidates and trials 0.
+ * fi_shapes_segment: shape p is fi_shape_fit with seed + p (wrapping) over the candidates no earlier shape took; the loop ends
+ * at max_shapes, at found = 0, or at the first shape with fewer than min_inliers inliers, which is not recorded.  labels[i]
+ * (int[n]) is the shape that took point i, or -1; rows (host, max_shapes) receive the recorded models and *num_shapes their
+ * number.  n = 0: found = 0, no shapes, FI_OK.
+ * FI_ERR_INVALID: ndim outside 2..3; n < 0; an unknown kind; a cylinder without normals; a negative, NaN or infinite
+ * threshold; r_min < 0; r_max < r_min; a NaN limit; normal_cos outside [0, 1]; normal_cos > 0 without normals; max_trials
+ * outside 1 .. 2^20; confidence outside [0, 1); refine outside 0 .. 16; a bad memory kind; NULL required pointers (opt,
+ * model / labels, rows, num_shapes; positions with n > 0); max_shapes < 1; min_inliers < 0.  FI_ERR_UNSUPPORTED: a cylinder
+ * with ndim = 2; n >= 2^31.
+ * Not offered: cones and tori; a radius-weighted or geometric (non-algebraic) refit; MSAC / MLESAC scores; slab contexts. */
+#define FI_SHAPE_SPHERE   0      /* a circle when ndim = 2 */
+#define FI_SHAPE_CYLINDER 1      /* 3-D only */
+#define FI_SHAPE_BATCH    1024
+typedef struct fi_shape_options {
+	int                kind;
+	float              threshold;
+	float              r_min, r_max;
+	float              normal_cos;
+	long               max_trials;
+	double             confidence;
+	int                refine;
+	unsigned long long seed;
+} fi_shape_options;
+typedef struct fi_shape_model {
+	int    found, kind, refits;
+	long   inliers, candidates, trials;
+	double center[3], axis[3], radius, extent[2], rms;
+} fi_shape_model;
+int fi_shape_fit(int ndim, long n, const float* positions, const float* normals, const unsigned char* mask,
+                 const fi_shape_options* opt, fi_shape_model* model, unsigned char* inliers, int memory);
+int fi_shapes_segment(int ndim, long n, const float* positions, const float* normals, const unsigned char* mask,
+                      const fi_shape_options* opt, int max_shapes, long min_inliers, int* labels, fi_shape_model* rows,
+                      int* num_shapes, int memory);
 
 /* ---- descriptors of a point's neighbourhood that survive a rigid motion, and their matching -----
  * The contract (tests/feature_reference.py is its definition in numpy) is this project's own: Rusu's fast

@@ -80,6 +80,15 @@ struct PlaneModel
 	double normal[3], offset, rms;
 };
 
+// A sphere (circle) or cylinder found by segment_shape / segment_shapes (include/fi_hip.h fi_shape_model), field for field.
+struct ShapeModel
+{
+	int    found, kind, refits;
+	long   inliers, candidates, trials;
+	double center[3], axis[3], radius, extent[2], rms;
+};
+enum class Shape { kSphere = 0, kCylinder = 1 };
+
 class GpuLatticeField
 {
 public:
@@ -332,6 +341,26 @@ bool segment_planes(int ndim, const std::vector<float>& positions, float thresho
                     std::vector<PlaneModel>* models, long min_inliers = 0, long max_trials = 1024, double confidence = 0.999,
                     int refine = 2, unsigned long long seed = 0, const std::vector<unsigned char>& mask = std::vector<unsigned char>(),
                     const std::vector<float>& axis = std::vector<float>(), float min_cos = 0.0f);
+
+// The dominant sphere (a circle with ndim = 2) or cylinder (ndim = 3, needs normals) of a point cloud on the device: RANSAC with
+// an exact inlier count (a point whose distance from the shape is within `threshold`, inclusive, is an inlier), then `refine`
+// algebraic least-squares refits.  positions and normals: ndim floats per point; normals may be empty for a sphere.  Only radii
+// in [r_min, r_max] are considered.  normal_cos > 0: an inlier's normal also lies within that angle of the shape's, either way
+// round.  max_trials, confidence, mask and inliers as segment_plane's.  Every figure is defined bit for bit: the contract is
+// include/fi_hip.h fi_shape_fit.  false: the library refused the call.
+bool segment_shape(int ndim, Shape kind, const std::vector<float>& positions, const std::vector<float>& normals, float threshold,
+                   ShapeModel* model, std::vector<unsigned char>* inliers = nullptr, float r_min = 0.0f,
+                   float r_max = std::numeric_limits<float>::infinity(), float normal_cos = 0.0f, long max_trials = 1024,
+                   double confidence = 0.999, int refine = 2, unsigned long long seed = 0,
+                   const std::vector<unsigned char>& mask = std::vector<unsigned char>());
+// Up to max_shapes shapes of one kind peeled off one after the other: shape p is segment_shape with seed + p over the points no
+// earlier shape took; the first shape with fewer than min_inliers inliers ends the loop and is not recorded.  labels[i]: the
+// shape that took point i, or -1.  The contract is include/fi_hip.h fi_shapes_segment.
+bool segment_shapes(int ndim, Shape kind, const std::vector<float>& positions, const std::vector<float>& normals, float threshold,
+                    int max_shapes, std::vector<int>* labels, std::vector<ShapeModel>* models, long min_inliers = 0, float r_min = 0.0f,
+                    float r_max = std::numeric_limits<float>::infinity(), float normal_cos = 0.0f, long max_trials = 1024,
+                    double confidence = 0.999, int refine = 2, unsigned long long seed = 0,
+                    const std::vector<unsigned char>& mask = std::vector<unsigned char>());
 
 // What every point's neighbourhood looks like, as 33 floats that survive a turn and a shift of the cloud (fast point feature
 // histograms over the k nearest points and the normals; 3 floats per point each), on the device.  valid (optional): one byte
