@@ -40,12 +40,16 @@ SYMBOLS = [
     "fi_surface_signed_distance_field",
     "fi_redistance", "fi_redistance_field",
     "fi_point_count", "fi_point_residuals", "fi_robust_reweight", "fi_reset_point_weights", "fi_solve_robust",
+    "fi_depth_unproject", "fi_volume_create", "fi_volume_destroy", "fi_volume_load", "fi_volume_copy", "fi_volume_integrate",
+    "fi_volume_constraints", "fi_add_volume",
 ]
 FI_LOSS = {"huber": 0, "cauchy": 1, "tukey": 2}
 FI_LOSS_NONE = -1
 FI_REGISTER = {"plane": 0, "point": 1}
 FI_THIN = {"mean": 0, "first": 1}
 FI_SHAPE = {"sphere": 0, "cylinder": 1}
+FI_DEPTH = {"z": 0, "range": 1}
+FI_DEPTH_CAMERAS = 8
 
 
 class FiWeights(C.Structure):
@@ -156,6 +160,11 @@ class FiAlignOptions(C.Structure):
 class FiAlignment(C.Structure):
     _fields_ = [("found", C.c_int), ("pairs", C.c_long), ("live", C.c_long), ("trials", C.c_long), ("valid", C.c_long),
                 ("inliers", C.c_long), ("transform", C.c_double * 16), ("rms", C.c_double)]
+
+
+class FiCamera(C.Structure):
+    _fields_ = [("pose", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("width", C.c_int), ("height", C.c_int), ("kind", C.c_int)]
 
 
 class FiError(RuntimeError):
@@ -300,6 +309,14 @@ def lib():
     L.fi_robust_reweight.argtypes = [vp, fp, C.POINTER(FiRobustOptions), fp, C.POINTER(C.c_float), C.c_int]
     L.fi_reset_point_weights.argtypes = [vp]
     L.fi_solve_robust.argtypes = [vp, fp, C.POINTER(FiRobustOptions), C.c_int, C.c_float, fp, fp, C.POINTER(FiRobustStats), C.c_int]
+    L.fi_depth_unproject.argtypes = [C.POINTER(FiCamera), fp, C.c_float, fp, fp, fp, vp, C.c_int]
+    L.fi_volume_create.argtypes = [C.POINTER(vp), C.c_int, ip, C.c_float, C.c_float]
+    L.fi_volume_destroy.argtypes = [vp]
+    L.fi_volume_load.argtypes = [vp, fp, fp, C.c_int]
+    L.fi_volume_copy.argtypes = [vp, fp, fp, C.c_int]
+    L.fi_volume_integrate.argtypes = [vp, C.c_long, C.POINTER(FiCamera), fp, fp, fp, C.c_float, C.c_int]
+    L.fi_volume_constraints.argtypes = [vp, C.c_float, C.POINTER(C.c_long), fp, fp, fp, C.c_int]
+    L.fi_add_volume.argtypes = [vp, vp, C.c_float, C.c_int, C.c_float]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError if the .so lacks a declared symbol
     _LIB = L

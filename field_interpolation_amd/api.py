@@ -1886,6 +1886,13 @@ class LatticeField:
                                         float(gradient_weight), int(gradient_kernel), mem))
         self._dirty = True
 
+    def add_volume(self, volume, value_weight, value_kernel=ValueKernel.kNearestNeighbor, min_weight=0.0):
+        """The band of a DepthVolume over this lattice as data points (include/fi_hip.h fi_add_volume): its voxels with
+        weight >= min_weight and |tsdf| < 1, each a value constraint tsdf * truncation with point weight W / max_weight,
+        formed on the device and added as add_points adds device arrays.  No gradient rows."""
+        check(_capi.lib().fi_add_volume(self._h, volume._h, float(value_weight), int(value_kernel), float(min_weight)))
+        self._dirty = True
+
     def add_rows_coo(self, rows, cols, values, rhs):
         """Arbitrary rows of a `LinearEquation` (sparse_linear.hpp:18-22): triplets (row, col, value) with rows
         numbered from 0 within this call, and one rhs per row.  Duplicate (row, col) entries are summed in input order in
@@ -2512,6 +2519,180 @@ def sdf_from_unoriented_points(sizes, weights, positions, k=16, viewpoints=None,
                                                                       device=hasattr(positions, "is_cuda") and positions.is_cuda,
                                                                       propagate=propagate)
     return sdf_from_points(sizes, weights, positions, normals, **kw)
+
+
+# ---- depth images (include/fi_hip.h fi_depth_unproject, fi_volume_integrate) ------------------------------
+
+class Camera:
+    """A pinhole camera for depth images (include/fi_hip.h fi_camera): pose (3, 4) float32 = [R | t], world (lattice
+    coordinates) to camera; it looks along +z, image x goes right, y down; pixel (row, col) has its centre at (col + 0.5,
+    row + 0.5).  kind: "range" (distance along the pixel's ray, what SurfaceIndex.render_depth writes) or "z" (depth along
+    the optical axis)."""
+
+    def __init__(self, pose, fx, fy, cx, cy, width, height, kind="range"):
+        self.pose = np.ascontiguousarray(np.asarray(pose, np.float32).reshape(3, 4))
+        self.fx, self.fy, self.cx, self.cy = (float(np.float32(v)) for v in (fx, fy, cx, cy))
+        self.width, self.height = int(width), int(height)
+        if kind not in _capi.FI_DEPTH:
+            raise ValueError("kind must be 'range' or 'z' (got %r)" % (kind,))
+        self.kind = kind
+
+    def _c(self):
+        return _capi.FiCamera((C.c_float * 12)(*self.pose.reshape(-1).tolist()), self.fx, self.fy, self.cx, self.cy, self.width,
+                              self.height, _capi.FI_DEPTH[self.kind])
+
+
+def camera_look_at(eye, target, up, fov_y, width, height, kind="range"):
+    """The Camera whose pixel-centre rays are those of SurfaceIndex.render_depth(eye, target, up, fov_y, width, height): the
+    rows of R are that function's right, -top and fwd, t = -R eye, fx = fy = height / (2 tan(fov_y / 2)), cx = width / 2,
+    cy = height / 2; computed in float64 and rounded to float32 once."""
+    eye = np.asarray(eye, np.float64).reshape(3)
+    fwd = np.asarray(target, np.float64).reshape(3) - eye
+    fwd /= np.linalg.norm(fwd)
+    right = np.cross(fwd, np.asarray(up, np.float64).reshape(3))
+    right /= np.linalg.norm(right)
+    top = np.cross(right, fwd)
+    R = np.stack([right, -top, fwd])
+    f = height / (2.0 * math.tan(0.5 * fov_y))
+    return Camera(np.concatenate([R, -(R @ eye)[:, None]], axis=1), f, f, 0.5 * width, 0.5 * height, width, height, kind)
+
+
+def _count(keep):
+    return keep.numel() if hasattr(keep, "numel") else keep.size
+
+
+def depth_to_points(camera, depth, max_jump=math.inf, positions=True, normals=True, incidence=True, valid=True, compact=False):
+    """A depth image (height, width) as oriented points on the device (include/fi_hip.h fi_depth_unproject): the tuple of
+    those asked for among positions (h w, 3), normals (h w, 3), incidence (h w,) float32 and valid (h w,) bool, in pixel
+    order.  A pixel is valid when its depth is finite and > 0; its normal is the cross product of the image's own
+    differences (central where both neighbours are valid and within max_jump in depth, else one-sided), turned towards the
+    eye; incidence is the cosine between the normal and the ray back to the eye, in (0, 1].  An invalid pixel has a NaN
+    position, a pixel without a normal a zero normal and a zero incidence.  compact=True drops the invalid pixels.  numpy
+    in, numpy out; a torch tensor on the GPU in, tensors on that GPU out."""
+    d, mem, keep = _buf(depth)
+    n = camera.width * camera.height
+    if _count(keep) != n:
+        raise ValueError("depth: %d values for a %d x %d image" % (_count(keep), camera.height, camera.width))
+    dev = keep.device if mem == FI_DEVICE else None
+    pos, pp = _cloud_out(dev, (n, 3), np.float32) if positions else (None, None)
+    nrm, pn = _cloud_out(dev, (n, 3), np.float32) if normals else (None, None)
+    inc, pi = _cloud_out(dev, (n,), np.float32) if incidence else (None, None)
+    val, pv = _cloud_out(dev, (n,), np.uint8) if (valid or compact) else (None, None)
+    cam = camera._c()
+    check(_capi.lib().fi_depth_unproject(C.byref(cam), d, float(max_jump), pp, pn, pi, pv, mem))
+    mask = _as_mask(val) if val is not None else None
+    out = [a for a in (pos, nrm, inc) if a is not None]
+    if compact:
+        out = [a[mask] for a in out]
+        mask = mask[mask]
+    return tuple(out) + ((mask,) if valid else ())
+
+
+def _flat_images(images):
+    """a list of images (or one array of them back to back) as one flat float32 array / tensor"""
+    if images is None or not isinstance(images, (list, tuple)):
+        return images
+    if any(hasattr(a, "data_ptr") for a in images):
+        import torch
+        return torch.cat([torch.as_tensor(a).reshape(-1).float() for a in images])
+    return np.concatenate([np.asarray(a, np.float32).reshape(-1) for a in images]) if images else np.zeros(0, np.float32)
+
+
+class DepthVolume:
+    """A truncated signed distance volume over a 3-D lattice on the device (include/fi_hip.h fi_volume_integrate): for every
+    lattice point tsdf (fp32, 1 at first: free space, in units of `truncation`) and weight (fp32, 0 at first: never seen).
+    integrate() fuses depth images into it; constraints() / LatticeField.add_volume hand its band to the solve."""
+
+    def __init__(self, sizes, truncation, max_weight=64.0):
+        self.sizes = [int(s) for s in sizes]
+        self.truncation, self.max_weight = float(truncation), float(max_weight)
+        self._h = C.c_void_p()
+        sz = (C.c_int * len(self.sizes))(*self.sizes)
+        check(_capi.lib().fi_volume_create(C.byref(self._h), len(self.sizes), sz, self.truncation, self.max_weight))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _capi._LIB is not None:
+            _capi._LIB.fi_volume_destroy(h)
+        self._h = None
+
+    @property
+    def num_voxels(self):
+        return int(np.prod(self.sizes))
+
+    def integrate(self, cameras, depths, incidences=None, image_weights=None, min_incidence=0.5):
+        """Fuses the depth images `depths` (a list of (height, width) arrays, or one array with the images back to back) seen
+        by `cameras` into the volume, in that order.  incidences (optional, same layout; depth_to_points gives them) scale
+        each sample's distance along the ray into one along the normal and weigh it; samples below min_incidence are left
+        out.  image_weights (optional): one factor per image.  numpy arrays, or torch tensors on the GPU."""
+        cameras = [cameras] if isinstance(cameras, Camera) else list(cameras)
+        m = len(cameras)
+        total = sum(c.width * c.height for c in cameras)
+        d, dm, dk = _buf(_flat_images(depths))
+        q, qm, qk = _buf(_flat_images(incidences))
+        w, wm, wk = _buf(image_weights)
+        for name, keep, want in (("depths", dk, total), ("incidences", qk, total), ("image_weights", wk, m)):
+            if (keep is not None or name == "depths") and (0 if keep is None else _count(keep)) != want:
+                raise ValueError("%s: %d values, %d expected" % (name, 0 if keep is None else _count(keep), want))
+        if dm == FI_DEVICE and wk is not None and wm != FI_DEVICE:       # a short host list beside device images
+            import torch
+            wk = torch.as_tensor(wk).to(dk.device)
+            w, wm = C.c_void_p(wk.data_ptr()), FI_DEVICE
+        mem = _same_memory(dm, qm, wm)
+        cams = (_capi.FiCamera * max(m, 1))(*[c._c() for c in cameras])
+        check(_capi.lib().fi_volume_integrate(self._h, m, cams, d if total else None, q if total else None, w if m else None,
+                                              float(min_incidence), mem))
+        return self
+
+    def _read(self, which, device):
+        a, p = _cloud_out("cuda" if device else None, (self.num_voxels,), np.float32)
+        check(_capi.lib().fi_volume_copy(self._h, p if which == 0 else None, p if which == 1 else None,
+                                         FI_DEVICE if device else FI_HOST))
+        return a
+
+    def tsdf(self, device=False):
+        """the truncated signed distances in units of `truncation`, (num_voxels,) float32, x fastest"""
+        return self._read(0, device)
+
+    def weight(self, device=False):
+        """the weights, (num_voxels,) float32, x fastest"""
+        return self._read(1, device)
+
+    def load(self, tsdf, weight):
+        """sets both arrays (num_voxels values each): resumes a fusion"""
+        t, tm, tk = _buf(tsdf)
+        w, wm, wk = _buf(weight)
+        if _count(tk) != self.num_voxels or _count(wk) != self.num_voxels:
+            raise ValueError("tsdf and weight must hold %d values each" % self.num_voxels)
+        check(_capi.lib().fi_volume_load(self._h, t, w, _same_memory(tm, wm)))
+        return self
+
+    def constraints(self, min_weight=0.0, device=False):
+        """(positions (n, 3), values (n,), weights (n,)) float32 of the band: the voxels with weight >= min_weight, weight > 0
+        and |tsdf| < 1 in ascending index; values are tsdf * truncation, weights W / max_weight."""
+        n = C.c_long(0)
+        check(_capi.lib().fi_volume_constraints(self._h, float(min_weight), C.byref(n), None, None, None, FI_HOST))
+        dev = "cuda" if device else None
+        pos, pp = _cloud_out(dev, (n.value, 3), np.float32)
+        val, pv = _cloud_out(dev, (n.value,), np.float32)
+        wgt, pw = _cloud_out(dev, (n.value,), np.float32)
+        if n.value:
+            check(_capi.lib().fi_volume_constraints(self._h, float(min_weight), C.byref(n), pp, pv, pw, FI_DEVICE if device else FI_HOST))
+        return pos, val, wgt
+
+
+def sdf_from_depth(sizes, weights, cameras, depths, truncation, incidences=None, min_incidence=0.5, max_weight=64.0, dtype="f32"):
+    """A signed distance problem from depth images: a DepthVolume over `sizes` fuses them, the model rows of `weights` and the
+    volume's band (value rows of weight weights.data_pos) make the field -> (field, volume), ready for field.solve_cg().
+    The rows' point weights are W / max_weight: choose max_weight near the number of views that see a surface point at
+    min_incidence or better (about 4 of 14 views all around an object), or raise weights.data_pos -- with weights of a few
+    hundredths the smoothness rows win and the surface moves by cells."""
+    volume = DepthVolume(sizes, truncation, max_weight)
+    volume.integrate(cameras, depths, incidences, min_incidence=min_incidence)
+    field = LatticeField(sizes, dtype=dtype)
+    field.add_field_constraints(weights)
+    field.add_volume(volume, weights.data_pos)
+    return field, volume
 
 
 def solve_sparse_linear_with_guess(field, guess, max_iterations=0, error_tolerance=0.0):

@@ -24,6 +24,7 @@
 #include "fi_align.h"
 #include "fi_mls.h"
 #include "fi_feature.h"
+#include "fi_depth.h"
 
 #include <memory>
 
@@ -2124,5 +2125,150 @@ int fi_redistance_field(const float* field, int ndim, const int* sizes, float is
 	FI_API_END
 }
 
+// ---- depth images: oriented points, and a truncated signed distance volume (fi_depth.hip) -----------
+namespace {
+void check_volume(const fi_volume* v)
+{
+	FI_REQUIRE(v != nullptr, FI_ERR_INVALID, "volume is null");
+	FI_HIP_TRY(hipSetDevice(v->device));
+}
+
+// the cameras of a call and the pixels of their images together
+int64_t check_cameras(long m, const fi_camera* cameras)
+{
+	FI_REQUIRE(m >= 0, FI_ERR_INVALID, "m = %ld", m);
+	FI_REQUIRE(m == 0 || cameras != nullptr, FI_ERR_INVALID, "cameras is null");
+	int64_t pixels = 0;
+	for (long s = 0; s < m; ++s) {
+		fi::check_camera(cameras[s]);
+		pixels += fi::camera_pixels(cameras[s]);
+		FI_REQUIRE(pixels < (int64_t(1) << 31), FI_ERR_UNSUPPORTED, "more than 2^31 - 1 pixels in one call");
+	}
+	return pixels;
+}
+}  // namespace
+
+int fi_depth_unproject(const fi_camera* camera, const float* depth, float max_jump, float* positions, float* normals, float* incidence,
+                       unsigned char* valid, int memory)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(camera != nullptr && depth != nullptr, FI_ERR_INVALID, "null camera or depth");
+	FI_REQUIRE(max_jump >= 0.0f, FI_ERR_INVALID, "max_jump must be >= 0 (got %g)", static_cast<double>(max_jump));  // (NaN fails)
+	FI_REQUIRE(positions || normals || incidence || valid, FI_ERR_INVALID, "every output is null");
+	fi::check_memory(memory);
+	check_cameras(1, camera);
+	fi::depth_unproject(*camera, depth, max_jump, positions, normals, incidence, valid, memory, nullptr);
+	FI_API_END
+}
+
+int fi_volume_create(fi_volume** out, int ndim, const int* sizes, float truncation, float max_weight)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(out != nullptr, FI_ERR_INVALID, "out is null");
+	*out = nullptr;
+	FI_REQUIRE(1 <= ndim && ndim <= FI_MAX_DIM && sizes != nullptr, FI_ERR_INVALID, "ndim must be 1..%d with sizes (got %d)", FI_MAX_DIM, ndim);
+	const int64_t n = fi::lattice_points(ndim, sizes);
+	FI_REQUIRE(truncation > 0.0f && std::isfinite(truncation), FI_ERR_INVALID, "truncation must be > 0 and finite (got %g)",
+	           static_cast<double>(truncation));
+	FI_REQUIRE(max_weight > 0.0f, FI_ERR_INVALID, "max_weight must be > 0 (got %g)", static_cast<double>(max_weight));  // (NaN fails)
+	FI_REQUIRE(ndim == 3, FI_ERR_UNSUPPORTED, "a volume over a %d-D lattice is not supported", ndim);
+	FI_REQUIRE(n < (int64_t(1) << 31), FI_ERR_UNSUPPORTED, "a volume of %lld voxels", static_cast<long long>(n));
+	std::unique_ptr<fi_volume> v(new fi_volume());
+	FI_HIP_TRY(hipGetDevice(&v->device));
+	for (int d = 0; d < 3; ++d) { v->n[d] = sizes[d]; }
+	v->nvox       = n;
+	v->truncation = truncation;
+	v->max_weight = max_weight;
+	v->tsdf.alloc(sizeof(float) * n);
+	v->weight.alloc(sizeof(float) * n);
+	fi::volume_reset(v.get(), nullptr);
+	*out = v.release();
+	FI_API_END
+}
+
+int fi_volume_destroy(fi_volume* v) { return fi::destroy_handle(v); }
+
+int fi_volume_load(fi_volume* v, const float* tsdf, const float* weight, int memory)
+{
+	FI_API_BEGIN
+	check_volume(v);
+	FI_REQUIRE(tsdf != nullptr && weight != nullptr, FI_ERR_INVALID, "null tsdf or weight");
+	fi::check_memory(memory);
+	const hipMemcpyKind kind = memory == FI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+	FI_HIP_TRY(hipMemcpyAsync(v->tsdf.p, tsdf, sizeof(float) * v->nvox, kind, nullptr));
+	FI_HIP_TRY(hipMemcpyAsync(v->weight.p, weight, sizeof(float) * v->nvox, kind, nullptr));
+	FI_HIP_TRY(hipStreamSynchronize(nullptr));
+	FI_API_END
+}
+
+int fi_volume_copy(const fi_volume* v, float* tsdf, float* weight, int memory)
+{
+	FI_API_BEGIN
+	check_volume(v);
+	FI_REQUIRE(tsdf != nullptr || weight != nullptr, FI_ERR_INVALID, "null tsdf and weight");
+	fi::check_memory(memory);
+	const hipMemcpyKind kind = memory == FI_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+	if (tsdf) { FI_HIP_TRY(hipMemcpyAsync(tsdf, v->tsdf.p, sizeof(float) * v->nvox, kind, nullptr)); }
+	if (weight) { FI_HIP_TRY(hipMemcpyAsync(weight, v->weight.p, sizeof(float) * v->nvox, kind, nullptr)); }
+	FI_HIP_TRY(hipStreamSynchronize(nullptr));
+	FI_API_END
+}
+
+int fi_volume_integrate(fi_volume* v, long m, const fi_camera* cameras, const float* depths, const float* incidences,
+                        const float* image_weights, float min_incidence, int memory)
+{
+	FI_API_BEGIN
+	check_volume(v);
+	FI_REQUIRE(min_incidence == min_incidence, FI_ERR_INVALID, "min_incidence is NaN");
+	fi::check_memory(memory);
+	check_cameras(m, cameras);
+	FI_REQUIRE(m == 0 || depths != nullptr, FI_ERR_INVALID, "depths is null");
+	fi::volume_integrate(v, m, cameras, depths, incidences, image_weights, min_incidence, memory, nullptr);
+	FI_API_END
+}
+
+int fi_volume_constraints(const fi_volume* v, float min_weight, long* n, float* positions, float* values, float* weights, int memory)
+{
+	FI_API_BEGIN
+	check_volume(v);
+	FI_REQUIRE(n != nullptr, FI_ERR_INVALID, "n is null");
+	FI_REQUIRE(min_weight == min_weight, FI_ERR_INVALID, "min_weight is NaN");
+	fi::check_memory(memory);
+	const bool fill = positions || values || weights;
+	FI_REQUIRE(!fill || *n >= 0, FI_ERR_INVALID, "room for %ld points", *n);
+	*n = static_cast<long>(fi::volume_constraints(v, min_weight, fill ? *n : 0, positions, values, weights, memory, nullptr));
+	FI_API_END
+}
+
+int fi_add_volume(fi_ctx* c, const fi_volume* v, float value_weight, int value_kernel, float min_weight)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	FI_REQUIRE(v != nullptr, FI_ERR_INVALID, "volume is null");
+	FI_REQUIRE(value_kernel == FI_VALUE_NEAREST_NEIGHBOR || value_kernel == FI_VALUE_LINEAR_INTERPOLATION, FI_ERR_INVALID,
+	           "Unknown value kernel: %d", value_kernel);
+	FI_REQUIRE(min_weight == min_weight, FI_ERR_INVALID, "min_weight is NaN");
+	FI_REQUIRE(c->g.ndim == 3, FI_ERR_UNSUPPORTED, "a volume into a %d-D lattice is not supported", c->g.ndim);
+	FI_REQUIRE(c->nranks == 1, FI_ERR_UNSUPPORTED, "fi_add_volume on a slab context: the volume covers the whole lattice");
+	FI_REQUIRE(c->g.gn[0] == v->n[0] && c->g.gn[1] == v->n[1] && c->g.gn[2] == v->n[2], FI_ERR_INVALID,
+	           "the volume is %d x %d x %d, the lattice %d x %d x %d", v->n[0], v->n[1], v->n[2], c->g.gn[0], c->g.gn[1], c->g.gn[2]);
+	FI_REQUIRE(c->device == v->device, FI_ERR_INVALID, "the volume lives on device %d, the context on %d", v->device, c->device);
+	fi::DevBuf    pos, val, wgt, zero;
+	const int64_t n = fi::volume_constraints_device(v, min_weight, pos, val, wgt, c->stream);
+	if (n == 0) { return FI_OK; }
+	const float* nrm = nullptr;
+	if (value_kernel == FI_VALUE_NEAREST_NEIGHBOR) {
+		// that kernel's row reads the point's gradient for the step to its lattice point: zero here, as the step is
+		zero.alloc(sizeof(float) * 3 * n);
+		FI_HIP_TRY(hipMemsetAsync(zero.p, 0, sizeof(float) * 3 * n, c->stream));
+		nrm = zero.as<float>();
+	}
+	fi::nearest_release(c);  // (a new point set)
+	fi::add_points_device(c, static_cast<long>(n), pos.as<float>(), nrm, wgt.as<float>(), val.as<float>(), value_weight, value_kernel, 0.0f,
+	                      FI_GRADIENT_NEAREST_NEIGHBOR);
+	c->assembled = false;
+	FI_API_END
+}
 
 }  // extern "C"

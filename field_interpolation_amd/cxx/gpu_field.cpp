@@ -676,6 +676,126 @@ bool GpuLatticeField::cluster_points(float eps, int min_points, std::vector<int>
 	return true;
 }
 
+// ---- depth images (include/fi_hip.h fi_depth_unproject, fi_volume_integrate) ----
+namespace {
+fi_camera to_c(const DepthCamera& c)
+{
+	fi_camera out{};
+	std::memcpy(out.pose, c.pose, sizeof(out.pose));
+	out.fx     = c.fx;
+	out.fy     = c.fy;
+	out.cx     = c.cx;
+	out.cy     = c.cy;
+	out.width  = c.width;
+	out.height = c.height;
+	out.kind   = c.range ? FI_DEPTH_RANGE : FI_DEPTH_Z;
+	return out;
+}
+}  // namespace
+
+DepthVolume::DepthVolume(const std::vector<int>& sizes, float truncation, float max_weight)
+{
+	if (fi_volume_create(&volume_, static_cast<int>(sizes.size()), sizes.data(), truncation, max_weight) != FI_OK) {
+		warn("DepthVolume");
+		volume_ = nullptr;
+		return;
+	}
+	voxels_ = 1;
+	for (int s : sizes) { voxels_ *= static_cast<size_t>(s); }
+}
+
+DepthVolume::~DepthVolume() { fi_volume_destroy(volume_); }
+
+bool DepthVolume::integrate(const std::vector<DepthCamera>& cameras, const std::vector<float>& depths, const std::vector<float>& incidences,
+                            const std::vector<float>& image_weights, float min_incidence)
+{
+	std::vector<fi_camera> cams;
+	size_t                 pixels = 0;
+	for (const DepthCamera& c : cameras) {
+		cams.push_back(to_c(c));
+		if (c.width > 0 && c.height > 0) { pixels += static_cast<size_t>(c.width) * static_cast<size_t>(c.height); }
+	}
+	if (!volume_ || depths.size() != pixels || (!incidences.empty() && incidences.size() != pixels) ||
+	    (!image_weights.empty() && image_weights.size() != cameras.size()) ||
+	    fi_volume_integrate(volume_, static_cast<long>(cams.size()), cams.data(), depths.data(), incidences.empty() ? nullptr : incidences.data(),
+	                        image_weights.empty() ? nullptr : image_weights.data(), min_incidence, FI_HOST) != FI_OK) {
+		warn("DepthVolume::integrate");
+		return false;
+	}
+	return true;
+}
+
+bool DepthVolume::copy(std::vector<float>* tsdf, std::vector<float>* weight) const
+{
+	if (tsdf) { tsdf->resize(voxels_); }
+	if (weight) { weight->resize(voxels_); }
+	if (!volume_ || fi_volume_copy(volume_, tsdf ? tsdf->data() : nullptr, weight ? weight->data() : nullptr, FI_HOST) != FI_OK) {
+		warn("DepthVolume::copy");
+		return false;
+	}
+	return true;
+}
+
+bool DepthVolume::load(const std::vector<float>& tsdf, const std::vector<float>& weight)
+{
+	if (!volume_ || tsdf.size() != voxels_ || weight.size() != voxels_ || fi_volume_load(volume_, tsdf.data(), weight.data(), FI_HOST) != FI_OK) {
+		warn("DepthVolume::load");
+		return false;
+	}
+	return true;
+}
+
+bool DepthVolume::constraints(std::vector<float>* positions, std::vector<float>* values, std::vector<float>* weights, float min_weight) const
+{
+	long n = 0;
+	if (!volume_ || fi_volume_constraints(volume_, min_weight, &n, nullptr, nullptr, nullptr, FI_HOST) != FI_OK) {
+		warn("DepthVolume::constraints");
+		return false;
+	}
+	if (positions) { positions->resize(3 * static_cast<size_t>(n)); }
+	if (values) { values->resize(static_cast<size_t>(n)); }
+	if (weights) { weights->resize(static_cast<size_t>(n)); }
+	if (n == 0 || (!positions && !values && !weights)) { return true; }
+	if (fi_volume_constraints(volume_, min_weight, &n, positions ? positions->data() : nullptr, values ? values->data() : nullptr,
+	                          weights ? weights->data() : nullptr, FI_HOST) != FI_OK) {
+		warn("DepthVolume::constraints");
+		return false;
+	}
+	return true;
+}
+
+bool GpuLatticeField::add_volume(const DepthVolume& volume, float value_weight, ValueKernel value_kernel, float min_weight)
+{
+	if (fi_add_volume(ctx_, volume.handle(), value_weight, static_cast<int>(value_kernel), min_weight) != FI_OK) {
+		warn("add_volume");
+		return false;
+	}
+	dirty_ = true;
+	return true;
+}
+
+bool depth_to_points(const DepthCamera& camera, const std::vector<float>& depth, std::vector<float>* positions, std::vector<float>* normals,
+                     std::vector<float>* incidence, std::vector<unsigned char>* valid, float max_jump)
+{
+	const size_t n = camera.width > 0 && camera.height > 0 ? static_cast<size_t>(camera.width) * static_cast<size_t>(camera.height) : 0;
+	const fi_camera c = to_c(camera);
+	if (n == 0 || depth.size() != n || (!positions && !normals && !incidence && !valid)) {
+		std::fprintf(stderr, "field_interpolation: depth_to_points: %zu depths for a %d x %d image, or no output\n", depth.size(), camera.height,
+		             camera.width);
+		return false;
+	}
+	if (positions) { positions->resize(3 * n); }
+	if (normals) { normals->resize(3 * n); }
+	if (incidence) { incidence->resize(n); }
+	if (valid) { valid->resize(n); }
+	if (fi_depth_unproject(&c, depth.data(), max_jump, positions ? positions->data() : nullptr, normals ? normals->data() : nullptr,
+	                       incidence ? incidence->data() : nullptr, valid ? valid->data() : nullptr, FI_HOST) != FI_OK) {
+		warn("depth_to_points");
+		return false;
+	}
+	return true;
+}
+
 namespace {
 // the outputs of a moving-least-squares call sized for n points of D dimensions
 void size_mls(size_t n, size_t D, std::vector<float>* positions, std::vector<float>* normals, std::vector<float>* curvature,

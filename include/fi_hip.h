@@ -1492,6 +1492,85 @@ int fi_redistance(fi_ctx* ctx, const float* field, float iso, int method, float 
 int fi_redistance_field(const float* field, int ndim, const int* sizes, float iso, int method, float max_distance, float* out,
                         long long* primitives, fi_mesh** mesh, int memory);
 
+/* ---- depth images: oriented points, and a truncated signed distance volume ----------------------------
+ * The contract (tests/depth_reference.py is its definition in numpy).  3-D only.  All arithmetic is fp32, one
+ * rounding per operation over + - * / sqrt floor min and compares, in the order written here with the parentheses given;
+ * nothing is summed by atomics, so a repeated call returns the same bytes.  "valid depth": finite and > 0.
+ *
+ * A camera: pose = the rows of [R | t], world (lattice coordinates) to camera: c_a = ((R_a0 x + R_a1 y) + R_a2 z) + t_a with
+ * R_aj = pose[4 a + j], t_a = pose[4 a + 3].  It looks along +z, image x goes right and y down; pixel (row, col) covers
+ * [col, col + 1) x [row, row + 1), its centre is (col + 0.5, row + 0.5); images are row-major, height x width floats.  kind:
+ * FI_DEPTH_Z, depth along the optical axis, or FI_DEPTH_RANGE, distance along the pixel's ray.  R is taken as it is given:
+ * where it is no rotation, "world point" below is still R^T (c - t).  Cameras are always host structures, whatever `memory`.
+ *
+ * fi_depth_unproject, a thread per pixel.  For pixel (row, col) with valid depth d:
+ *   px = ((col + 0.5) - cx) / fx, py = ((row + 0.5) - cy) / fy;  Z: c = (px d, py d, d);  RANGE: l = sqrt((px px + py py) + 1),
+ *   c = ((px / l) d, (py / l) d, (1 / l) d);  e = c - t;  the world point x_j = (R_0j e_0 + R_1j e_1) + R_2j e_2.
+ *   A neighbour qualifies when it is in the image, its depth d' is valid and |d' - d| <= max_jump (>= 0; +inf: any).  a = the
+ *   world point of the right neighbour minus that of the left one where both qualify; else the one that qualifies against the
+ *   pixel's own point (right minus own, or own minus left); b likewise with the lower neighbour minus the upper.  Neither
+ *   qualifies in one of the two directions: no normal.  n = (a_y b_z - a_z b_y, a_z b_x - a_x b_z, a_x b_y - a_y b_x), len =
+ *   sqrt((n_x n_x + n_y n_y) + n_z n_z), n = n / len.  The ray: v_j = (R_0j c_0 + R_1j c_1) + R_2j c_2, lv = sqrt((v_x v_x +
+ *   v_y v_y) + v_z v_z), s = (n_x (v_x / lv) + n_y (v_y / lv)) + n_z (v_z / lv); s > 0: n = -n, s = -s.  incidence = min(-s, 1).
+ *   No normal unless len > 0, len finite and incidence > 0.
+ * positions float[h w 3], normals float[h w 3], incidence float[h w], valid unsigned char[h w], in pixel order; any may be
+ * NULL, not all four.  A pixel without a valid depth: NaN position, zero normal, zero incidence, valid 0 (fi_add_points ignores
+ * non-finite points).  A pixel with a position and no normal: valid 1, zero normal, zero incidence.
+ *
+ * A volume holds tsdf (1 at first) and weight W (0 at first), fp32, for every point of a 3-D lattice, x fastest, on the device
+ * that was current at fi_volume_create.  fi_volume_load sets both arrays (to resume a fusion; the values are taken as they
+ * are), fi_volume_copy reads them (either output may be NULL).  fi_volume_integrate: the m images lie back to back in depths,
+ * image s of height_s x width_s floats; incidences (or NULL) likewise; image_weights (or NULL: all 1) float[m].  Voxel
+ * p = (i, j, k), coordinates (float)i, j, k, is updated for image s = 0 .. m - 1 in that order:
+ *   1. c = the camera point of p; skip unless c_z > 0;
+ *   2. u = fx (c_x / c_z) + cx, v = fy (c_y / c_z) + cy; col = floor(u), row = floor(v); skip if outside the image;
+ *   3. d = depth[row, col]; skip unless valid;
+ *   4. r = c_z (Z) or sqrt((c_x c_x + c_y c_y) + c_z c_z) (RANGE); e = d - r; skip if e < -truncation (the voxel is hidden:
+ *      this cut is on the distance along the ray, before any scaling);
+ *   5. q = 1 without incidences; else q = incidence[row, col]: skip unless q >= min_incidence and q is finite;
+ *   6. f = min((e q) / truncation, 1): the incidence turns the distance along the ray into one along the normal;
+ *   7. w = q image_weight_s; skip unless w > 0;
+ *   8. tsdf = (tsdf W + f w) / (W + w), then W = min(W + w, max_weight).
+ * The kernel applies FI_DEPTH_CAMERAS images per pass over the volume and takes further passes, in image order, for more; no
+ * result depends on that number, nor on the kernel's cull of images a whole run of voxels cannot see.
+ *
+ * fi_volume_constraints: the voxels with W >= min_weight, W > 0 and |tsdf| < 1, in ascending linear index: positions (float)i,
+ * j, k; values tsdf truncation; weights W / max_weight.  Two calls: with all three buffers NULL *n receives the count; else *n
+ * holds the room of each given buffer in points on entry (less than the count: FI_ERR_INVALID) and the count on return.
+ * fi_add_volume forms those arrays on the device and hands them to the code fi_add_points runs for device buffers, as one
+ * batch with values, point weights and no gradient rows: the voxels are data points of the context in every later sense
+ * (residuals, robust reweighting, fi_nearest).  With FI_VALUE_NEAREST_NEIGHBOR, whose row reads a gradient for the step from
+ * the point to its lattice point, the batch carries zero normals (the step is zero: the row is [1] w = value w); with
+ * FI_VALUE_LINEAR_INTERPOLATION it carries none.  The lattice must have the volume's sizes.
+ *
+ * FI_ERR_INVALID: truncation not > 0 and finite, max_weight not > 0, a NaN min_incidence or min_weight, a NaN or negative
+ * max_jump, a kind other than the two, a non-positive image size, a non-finite pose entry, cx or cy, fx or fy not > 0 and
+ * finite, a NULL required pointer, a bad memory kind, m < 0, sizes that differ from the lattice's.  m = 0 is fine.
+ * FI_ERR_UNSUPPORTED: a 1-D or 2-D lattice, more than 2^31 - 1 voxels, or pixels in one call, a slab context.  `memory` applies
+ * to every buffer of a call but the cameras.
+ * Not offered: 2-D lattices, bilinear depth lookup, colour, free-space (tsdf = 1) constraints, space carving, sparse or hashed
+ * volumes, lens distortion, slab groups. */
+#define FI_DEPTH_Z 0
+#define FI_DEPTH_RANGE 1
+#define FI_DEPTH_CAMERAS 8
+typedef struct fi_camera {
+	float pose[12];
+	float fx, fy, cx, cy;
+	int   width, height, kind;
+} fi_camera;
+typedef struct fi_volume fi_volume;
+int fi_depth_unproject(const fi_camera* camera, const float* depth, float max_jump, float* positions, float* normals, float* incidence,
+                       unsigned char* valid, int memory);
+int fi_volume_create(fi_volume** out, int ndim, const int* sizes, float truncation, float max_weight);
+int fi_volume_destroy(fi_volume* volume);
+int fi_volume_load(fi_volume* volume, const float* tsdf, const float* weight, int memory);
+int fi_volume_copy(const fi_volume* volume, float* tsdf, float* weight, int memory);
+int fi_volume_integrate(fi_volume* volume, long m, const fi_camera* cameras, const float* depths, const float* incidences,
+                        const float* image_weights, float min_incidence, int memory);
+int fi_volume_constraints(const fi_volume* volume, float min_weight, long* n, float* positions, float* values, float* weights,
+                          int memory);
+int fi_add_volume(fi_ctx* ctx, const fi_volume* volume, float value_weight, int value_kernel, float min_weight);
+
 #ifdef __cplusplus
 }
 #endif

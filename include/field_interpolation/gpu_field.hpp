@@ -12,6 +12,7 @@
 #include "field_interpolation.hpp"
 
 struct fi_ctx;
+struct fi_volume;
 
 namespace field_interpolation {
 
@@ -88,6 +89,48 @@ struct ShapeModel
 	double center[3], axis[3], radius, extent[2], rms;
 };
 enum class Shape { kSphere = 0, kCylinder = 1 };
+
+// A pinhole camera for depth images (include/fi_hip.h fi_camera): pose = the rows of [R | t], world (lattice coordinates) to
+// camera; it looks along +z, image x goes right, y down; pixel (row, col) has its centre at (col + 0.5, row + 0.5).  range:
+// the depth is the distance along the pixel's ray (false: along the optical axis).
+struct DepthCamera
+{
+	float pose[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+	float fx = 1, fy = 1, cx = 0, cy = 0;
+	int   width = 0, height = 0;
+	bool  range = true;
+};
+
+// A truncated signed distance volume over a 3-D lattice on the device: tsdf (1 at first, in units of `truncation`) and weight
+// (0 at first) for every lattice point, x fastest.  integrate() fuses depth images into it; constraints() and
+// GpuLatticeField::add_volume hand its band to the solve.  The contract is include/fi_hip.h fi_volume_integrate.  Every call
+// returns false where the library refused it; valid() is false when the constructor's arguments were refused.
+class DepthVolume
+{
+public:
+	DepthVolume(const std::vector<int>& sizes, float truncation, float max_weight = 64.0f);
+	~DepthVolume();
+	DepthVolume(const DepthVolume&) = delete;
+	DepthVolume& operator=(const DepthVolume&) = delete;
+
+	bool   valid() const { return volume_ != nullptr; }
+	size_t num_voxels() const { return voxels_; }
+	// depths: the cameras' images back to back, image s of height_s x width_s floats; incidences (empty, or laid out the same
+	// way: depth_to_points gives them); image_weights (empty, or one per image)
+	bool integrate(const std::vector<DepthCamera>& cameras, const std::vector<float>& depths,
+	               const std::vector<float>& incidences = std::vector<float>(),
+	               const std::vector<float>& image_weights = std::vector<float>(), float min_incidence = 0.5f);
+	bool copy(std::vector<float>* tsdf, std::vector<float>* weight) const;              // either may be null
+	bool load(const std::vector<float>& tsdf, const std::vector<float>& weight);        // resumes a fusion
+	// the voxels with weight >= min_weight, weight > 0 and |tsdf| < 1 in ascending index: positions (3 floats each), values
+	// tsdf * truncation, weights W / max_weight; any may be null
+	bool constraints(std::vector<float>* positions, std::vector<float>* values, std::vector<float>* weights, float min_weight = 0) const;
+	const fi_volume* handle() const { return volume_; }
+
+private:
+	fi_volume* volume_ = nullptr;
+	size_t     voxels_ = 0;
+};
 
 class GpuLatticeField
 {
@@ -250,6 +293,11 @@ public:
 	                   float max_move = std::numeric_limits<float>::infinity(),
 	                   const std::vector<float>& guide_normals = std::vector<float>(), std::vector<float>* curvature = nullptr,
 	                   std::vector<unsigned char>* order = nullptr) const;
+	// The band of a DepthVolume over this lattice as data points: every voxel with weight >= min_weight and |tsdf| < 1 a value
+	// constraint tsdf * truncation of point weight W / max_weight, formed on the device; no gradient rows.  The contract is
+	// include/fi_hip.h fi_add_volume.  false: the library refused the call.
+	bool add_volume(const DepthVolume& volume, float value_weight, ValueKernel value_kernel = ValueKernel::kNearestNeighbor,
+	                float min_weight = 0);
 	// The clusters of the data points, in the order the points were added: labels[i] is point i's cluster, -1 for noise and
 	// for a non-finite point.  A point is core when min_points points, itself included, lie within eps of it (min_points = 1:
 	// plain Euclidean clustering); core points within eps of each other share a cluster, numbered by their lowest core point;
@@ -322,6 +370,15 @@ bool smooth_points(int ndim, const std::vector<float>& positions, float radius, 
                    float max_move = std::numeric_limits<float>::infinity(),
                    const std::vector<float>& guide_normals = std::vector<float>(), std::vector<float>* curvature = nullptr,
                    std::vector<unsigned char>* order = nullptr);
+
+// A depth image (camera.height x camera.width floats) as oriented points on the device, in pixel order: positions and normals
+// (3 floats each), incidence (the cosine between the normal and the ray back to the eye) and valid (1: a finite depth > 0);
+// any may be null, not all four.  A neighbour takes part in a pixel's normal when its depth is valid and within max_jump of
+// the pixel's.  An invalid pixel has a NaN position; a pixel without a normal a zero normal and a zero incidence.  The
+// contract is include/fi_hip.h fi_depth_unproject.  false: the library refused the call.
+bool depth_to_points(const DepthCamera& camera, const std::vector<float>& depth, std::vector<float>* positions,
+                     std::vector<float>* normals = nullptr, std::vector<float>* incidence = nullptr,
+                     std::vector<unsigned char>* valid = nullptr, float max_jump = std::numeric_limits<float>::infinity());
 
 // The dominant plane (ndim = 3) or line (ndim = 2) of a point cloud on the device, no lattice needed: RANSAC with an exact
 // inlier count (a point within `threshold` of the plane, inclusive, is an inlier), then `refine` least-squares refits.
