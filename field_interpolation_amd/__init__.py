@@ -9,6 +9,6 @@ from .api import (GradientKernel, IsoMesh, LatticeField, LatticeGroup, MeshParts
                   simplify_mesh, smooth_mesh, mesh_normals, sample_mesh, mesh_deviation, register_points, apply_transform, thin_points, clean_points, smooth_points,
                   cluster_points, cluster_measure, keep_clusters, segment_plane, segment_planes, segment_sphere, segment_cylinder, segment_shapes,
                   match_features, align_correspondences, register_global,
-                  Camera, DepthVolume, camera_look_at, depth_to_points, sdf_from_depth,
+                  Camera, DepthVolume, camera_look_at, depth_to_points, sdf_from_depth, raycast_field, render_field,
                   sdf_from_points, sdf_from_unoriented_points, solve_sparse_linear_exact, solve_sparse_linear_with_guess, solve_tiled_with_guess, upscale_field)
 from ._capi import FiError, memory_pool  # noqa: F401

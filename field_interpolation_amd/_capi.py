@@ -42,6 +42,8 @@ SYMBOLS = [
     "fi_point_count", "fi_point_residuals", "fi_robust_reweight", "fi_reset_point_weights", "fi_solve_robust",
     "fi_depth_unproject", "fi_volume_create", "fi_volume_destroy", "fi_volume_load", "fi_volume_copy", "fi_volume_integrate",
     "fi_volume_constraints", "fi_add_volume",
+    "fi_march_default_options", "fi_field_raycast", "fi_field_render", "fi_raycast_field", "fi_render_field", "fi_volume_raycast",
+    "fi_volume_render",
 ]
 FI_LOSS = {"huber": 0, "cauchy": 1, "tukey": 2}
 FI_LOSS_NONE = -1
@@ -50,6 +52,8 @@ FI_THIN = {"mean": 0, "first": 1}
 FI_SHAPE = {"sphere": 0, "cylinder": 1}
 FI_DEPTH = {"z": 0, "range": 1}
 FI_DEPTH_CAMERAS = 8
+FI_MARCH = {"front": 0, "back": 1, "either": 2}
+FI_MARCH_MAX_SAMPLES = 1 << 20
 
 
 class FiWeights(C.Structure):
@@ -165,6 +169,10 @@ class FiAlignment(C.Structure):
 class FiCamera(C.Structure):
     _fields_ = [("pose", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
                 ("width", C.c_int), ("height", C.c_int), ("kind", C.c_int)]
+
+
+class FiMarchOptions(C.Structure):
+    _fields_ = [("iso", C.c_float), ("step", C.c_float), ("min_weight", C.c_float), ("refine", C.c_int), ("side", C.c_int)]
 
 
 class FiError(RuntimeError):
@@ -317,6 +325,14 @@ def lib():
     L.fi_volume_integrate.argtypes = [vp, C.c_long, C.POINTER(FiCamera), fp, fp, fp, C.c_float, C.c_int]
     L.fi_volume_constraints.argtypes = [vp, C.c_float, C.POINTER(C.c_long), fp, fp, fp, C.c_int]
     L.fi_add_volume.argtypes = [vp, vp, C.c_float, C.c_int, C.c_float]
+    mo, cam = C.POINTER(FiMarchOptions), C.POINTER(FiCamera)
+    L.fi_march_default_options.argtypes = [mo]
+    L.fi_field_raycast.argtypes = [fp, fp, C.c_int, ip, mo, C.c_long, fp, fp, C.c_float, C.c_float, fp, fp, fp, vp, C.c_int]
+    L.fi_field_render.argtypes = [fp, fp, ip, mo, cam, fp, fp, fp, fp, C.c_int]
+    L.fi_raycast_field.argtypes = [vp, fp, mo, C.c_long, fp, fp, C.c_float, C.c_float, fp, fp, fp, vp, C.c_int]
+    L.fi_render_field.argtypes = [vp, fp, mo, cam, fp, fp, fp, fp, C.c_int]
+    L.fi_volume_raycast.argtypes = [vp, mo, C.c_long, fp, fp, C.c_float, C.c_float, fp, fp, fp, vp, C.c_int]
+    L.fi_volume_render.argtypes = [vp, mo, cam, fp, fp, fp, fp, C.c_int]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError if the .so lacks a declared symbol
     _LIB = L

@@ -2078,6 +2078,32 @@ class LatticeField:
             return _capi.lib().fi_sample(self._h, s, n, p, mode, fl, v, g, mem)
         return _sample(call, len(self.sizes), positions, [smem], gradients, cubic, fill)
 
+    def raycast(self, origins, directions, solution=None, iso=0.0, step=1.0, refine=4, side="front", t_min=0.0, t_max=math.inf,
+                positions=False, normals=False):
+        """raycast_field against `solution` (this context's owned values, in the rays' memory) or, with None, against the
+        last solve's solution where it lives on the device (an fp64 one rounded to fp32 once, as iso_surface does): the field
+        itself is marched, no mesh is built.  2-D or 3-D, undivided contexts only (include/fi_hip.h fi_raycast_field)."""
+        opt = _march_options(iso, step, refine, side, 0.0)
+        s, smem, _keep = _buf(solution)
+
+        def call(n, o, d, tp, pp, np_, sp, mem):
+            return _capi.lib().fi_raycast_field(self._h, s, C.byref(opt), n, o, d, float(t_min), float(t_max), tp, pp, np_, sp, mem)
+        return _march_rays(call, len(self.sizes), origins, directions, positions, normals, [smem])
+
+    def render(self, camera, solution=None, iso=0.0, step=1.0, refine=4, side="front", positions=False, normals=False,
+               incidence=False, device=False):
+        """render_field of `solution` (this context's owned values; a device tensor with device=True) or, with None, of the
+        last solve's solution where it lives on the device.  3-D, undivided contexts only; numpy arrays out, or torch
+        tensors with device=True (include/fi_hip.h fi_render_field)."""
+        opt = _march_options(iso, step, refine, side, 0.0)
+        s, smem, _keep = _buf(solution)
+        if smem is not None and (smem == FI_DEVICE) != bool(device):
+            raise ValueError("solution and the outputs live in the same memory: device=True with a device tensor")
+
+        def call(cam, dp, pp, np_, ip, mem):
+            return _capi.lib().fi_render_field(self._h, s, C.byref(opt), cam, dp, pp, np_, ip, mem)
+        return _march_image(call, camera, positions, normals, incidence, device)
+
     def nearest(self, queries, max_distance=math.inf, indices=False):
         """PointIndex.nearest over the data points of this context: every add_points batch in call order, the border prior's
         rows left out (include/fi_hip.h fi_nearest).  The search structure is built at the first query and kept until the
@@ -2679,6 +2705,149 @@ class DepthVolume:
         if n.value:
             check(_capi.lib().fi_volume_constraints(self._h, float(min_weight), C.byref(n), pp, pv, pw, FI_DEVICE if device else FI_HOST))
         return pos, val, wgt
+
+
+    # ---- rays and images of the volume (include/fi_hip.h fi_volume_raycast, fi_volume_render) ----
+    def raycast(self, origins, directions, iso=0.0, step=1.0, refine=4, side="front", min_weight=0.0, t_min=0.0, t_max=math.inf,
+                positions=False, normals=False):
+        """raycast_field against the volume's tsdf under its weights, both read in place: a sample counts only where every
+        corner of its cell has weight > 0 and >= min_weight; iso=0 is the surface (tsdf is in units of `truncation`, the
+        rays' t is not)."""
+        opt = _march_options(iso, step, refine, side, min_weight)
+
+        def call(n, o, d, tp, pp, np_, sp, mem):
+            return _capi.lib().fi_volume_raycast(self._h, C.byref(opt), n, o, d, float(t_min), float(t_max), tp, pp, np_, sp, mem)
+        return _march_rays(call, 3, origins, directions, positions, normals)
+
+    def render(self, camera, step=1.0, refine=4, min_weight=0.0, positions=False, normals=False, incidence=False, device=False):
+        """The depth image (height, width) float32 of the volume's surface (tsdf = 0, front crossings) seen by `camera`, in
+        the camera's own kind; +inf where a pixel's ray meets none.  With positions / normals / incidence also the hit points
+        (h w, 3), the unit gradients (h w, 3) and the incidences (h w,) in depth_to_points' layout and conventions, so that
+        integrate() can take the image and its incidences as they are.  numpy arrays, or torch tensors with device=True."""
+        opt = _march_options(0.0, step, refine, "front", min_weight)
+
+        def call(cam, dp, pp, np_, ip, mem):
+            return _capi.lib().fi_volume_render(self._h, C.byref(opt), cam, dp, pp, np_, ip, mem)
+        return _march_image(call, camera, positions, normals, incidence, device)
+
+    def track(self, camera, depth, rounds=2, max_jump=math.inf, max_distance=None, **register_keywords):
+        """Refines the pose of `camera` from the depth image it took, against the surface the volume holds (frame-to-model
+        tracking): each round renders the volume at the current pose with positions and normals, unprojects `depth` under
+        the same pose (depth_to_points, max_jump), and lays the unprojected points over the rendered ones with
+        register_points(mode="plane", target_normals=the rendered normals, max_distance=the volume's truncation by default,
+        **register_keywords).  With G the guessed pose and T that transform, the new pose is G T^-1, composed in float64 and
+        rounded to float32 once per round.  -> (Camera, dict): the last registration's dict plus "correction" (4, 4)
+        float64, the product of the rounds' transforms, and "rendered" / "unprojected", the points of each round.  Every
+        array stays on the device when `depth` is a device tensor."""
+        device = hasattr(depth, "data_ptr") and depth.is_cuda
+        max_distance = self.truncation if max_distance is None else max_distance
+        total, rendered, unprojected, last = np.eye(4), [], [], {}
+        for _ in range(int(rounds)):
+            _, pos, nrm = self.render(camera, positions=True, normals=True, device=device)
+            hit = pos[:, 0] == pos[:, 0]                 # (a pixel without a hit has a NaN position)
+            src, = depth_to_points(camera, depth, max_jump, normals=False, incidence=False, valid=False, compact=True)
+            last = register_points(src, pos[hit], nrm[hit], mode="plane", max_distance=max_distance, **register_keywords)
+            G = np.eye(4)
+            G[:3] = camera.pose.astype(np.float64)
+            G = G @ np.linalg.inv(last["transform"])
+            total = last["transform"] @ total
+            camera = Camera(G[:3], camera.fx, camera.fy, camera.cx, camera.cy, camera.width, camera.height, camera.kind)
+            rendered.append(int(hit.sum()))
+            unprojected.append(int(src.shape[0]))
+        return camera, dict(last, correction=total, rendered=rendered, unprojected=unprojected)
+
+
+# ---- rays and images of a lattice field (include/fi_hip.h fi_field_raycast, fi_field_render) -----------------
+
+def _march_options(iso, step, refine, side, min_weight):
+    if side not in _capi.FI_MARCH:
+        raise ValueError("side is 'front', 'back' or 'either', not %r" % (side,))
+    return _capi.FiMarchOptions(float(iso), float(step), float(min_weight), int(refine), _capi.FI_MARCH[side])
+
+
+def _march_rays(call, ndim, origins, directions, positions, normals, other_memory=()):
+    """Shared body of the field raycasts: call(n, origins, directions, t, positions, normals, side, memory) -> (t (n,)
+    float32, side (n,) int8[, positions (n, ndim)][, normals (n, ndim)]) where the rays live"""
+    o, omem, okeep = _buf(origins)
+    d, dmem, dkeep = _buf(directions)
+    if _count(okeep) % ndim or _count(okeep) != _count(dkeep):
+        raise ValueError("origins and directions are (n, %d) each (got %d and %d values)" % (ndim, _count(okeep), _count(dkeep)))
+    n = _count(okeep) // ndim
+    mem = _same_memory(omem, dmem, *other_memory)
+    dev = okeep.device if mem == FI_DEVICE else None
+    t, tp = _cloud_out(dev, (n,), np.float32)
+    sd, sp = _cloud_out(dev, (n,), np.int8)
+    pos, pp = _cloud_out(dev, (n, ndim), np.float32) if positions else (None, None)
+    nrm, np_ = _cloud_out(dev, (n, ndim), np.float32) if normals else (None, None)
+    if n:   # (an empty array has no storage to point at)
+        check(call(n, o, d, tp, pp, np_, sp, mem))
+    return tuple(a for a in (t, sd, pos, nrm) if a is not None)
+
+
+def _march_image(call, camera, positions, normals, incidence, device, like=None):
+    """Shared body of the field renders: call(camera, depth, positions, normals, incidence, memory) -> depth (h, w)[,
+    positions (h w, 3)][, normals (h w, 3)][, incidence (h w,)]: numpy, or torch with device=True"""
+    n = camera.width * camera.height
+    dev = ("cuda" if like is None else like.device) if device else None
+    depth, dp = _cloud_out(dev, (n,), np.float32)
+    pos, pp = _cloud_out(dev, (n, 3), np.float32) if positions else (None, None)
+    nrm, np_ = _cloud_out(dev, (n, 3), np.float32) if normals else (None, None)
+    inc, ip = _cloud_out(dev, (n,), np.float32) if incidence else (None, None)
+    cam = camera._c()
+    check(call(C.byref(cam), dp, pp, np_, ip, FI_DEVICE if device else FI_HOST))
+    out = tuple(a for a in (depth.reshape(camera.height, camera.width), pos, nrm, inc) if a is not None)
+    return out if len(out) > 1 else out[0]
+
+
+def raycast_field(field, sizes, origins, directions, iso=0.0, step=1.0, refine=4, side="front", weight=None, min_weight=0.0,
+                  t_min=0.0, t_max=math.inf, positions=False, normals=False):
+    """Rays against the iso-level of a lattice field (flat, fp32, x fastest, 2-D or 3-D), marched on the device through its
+    trilinear interpolant: ray i is origins[i] + t directions[i] (n x ndim each, directions not normalised, t in units of the
+    direction) with t_min <= t <= t_max.  The ray is clipped to the lattice's box and sampled every `step` lattice units; the
+    first two consecutive samples that `iso` separates are refined by `refine` (0 .. 16) bisections and one linear
+    interpolation.  side: "front" takes crossings from outside (f >= iso) to inside (f < iso, as iso_surface decides it),
+    "back" the opposite ones, "either" the first of both.  weight (optional, the field's shape) with min_weight masks the
+    field: a sample counts only where every corner of its cell has weight > 0 and >= min_weight.  -> (t (n,) float32, side
+    (n,) int8: +1 front, -1 back, 0 none), with positions / normals also the hit points (n, ndim) and the field's unit
+    gradients there (towards increasing f).  No crossing: +inf, NaN position, zero normal; a ray with a non-finite origin or
+    direction, or a zero direction: NaN.  Two crossings inside one step, and features thinner than `step`, can be missed.
+    numpy in, numpy out; torch CUDA tensors in (field, rays and weight alike), tensors out (include/fi_hip.h
+    fi_field_raycast)."""
+    sizes = [int(s) for s in sizes]
+    opt = _march_options(iso, step, refine, side, min_weight)
+    f, fmem, fkeep = _buf(field)
+    w, wmem, wkeep = _buf(weight)
+    total = int(np.prod(sizes))
+    if _count(fkeep) != total or (wkeep is not None and _count(wkeep) != total):
+        raise ValueError("field and weight hold %d values each for sizes %r" % (total, sizes))
+    sz = (C.c_int * len(sizes))(*sizes)
+
+    def call(n, o, d, tp, pp, np_, sp, mem):
+        return _capi.lib().fi_field_raycast(f, w, len(sizes), sz, C.byref(opt), n, o, d, float(t_min), float(t_max), tp, pp, np_, sp, mem)
+    return _march_rays(call, len(sizes), origins, directions, positions, normals, [fmem, wmem])
+
+
+def render_field(field, sizes, camera, iso=0.0, step=1.0, refine=4, side="front", weight=None, min_weight=0.0, positions=False,
+                 normals=False, incidence=False):
+    """The depth image (height, width) float32 of the iso-level of a 3-D lattice field seen by `camera` (raycast_field along
+    the pixels' rays, over t >= 0), in the camera's own kind; +inf where a pixel's ray meets no crossing.  positions /
+    normals / incidence: as DepthVolume.render.  numpy in, numpy out; a torch CUDA field (and weight) in, tensors out
+    (include/fi_hip.h fi_field_render)."""
+    sizes = [int(s) for s in sizes]
+    if len(sizes) != 3:
+        raise ValueError("render_field needs a 3-D field")
+    opt = _march_options(iso, step, refine, side, min_weight)
+    f, fmem, fkeep = _buf(field)
+    w, wmem, wkeep = _buf(weight)
+    total = int(np.prod(sizes))
+    if _count(fkeep) != total or (wkeep is not None and _count(wkeep) != total):
+        raise ValueError("field and weight hold %d values each for sizes %r" % (total, sizes))
+    sz = (C.c_int * 3)(*sizes)
+    device = _same_memory(fmem, wmem) == FI_DEVICE
+
+    def call(cam, dp, pp, np_, ip, mem):
+        return _capi.lib().fi_field_render(f, w, sz, C.byref(opt), cam, dp, pp, np_, ip, mem)
+    return _march_image(call, camera, positions, normals, incidence, device, fkeep if device else None)
 
 
 def sdf_from_depth(sizes, weights, cameras, depths, truncation, incidences=None, min_incidence=0.5, max_weight=64.0, dtype="f32"):

@@ -25,6 +25,7 @@
 #include "fi_mls.h"
 #include "fi_feature.h"
 #include "fi_depth.h"
+#include "fi_march.h"
 
 #include <memory>
 
@@ -2268,6 +2269,135 @@ int fi_add_volume(fi_ctx* c, const fi_volume* v, float value_weight, int value_k
 	fi::add_points_device(c, static_cast<long>(n), pos.as<float>(), nrm, wgt.as<float>(), val.as<float>(), value_weight, value_kernel, 0.0f,
 	                      FI_GRADIENT_NEAREST_NEIGHBOR);
 	c->assembled = false;
+	FI_API_END
+}
+
+// ---- rays and pinhole images of a lattice field or a depth volume (fi_march.hip) ---------------------
+namespace {
+void check_march_rays(const fi_march_options* options, long n, const float* origins, const float* directions, float t_min, float t_max,
+                      const float* t, const float* positions, const float* normals, const signed char* side, int memory)
+{
+	fi::check_march_options(options);
+	FI_REQUIRE(n >= 0, FI_ERR_INVALID, "n = %ld", n);
+	FI_REQUIRE(n == 0 || (origins != nullptr && directions != nullptr), FI_ERR_INVALID, "null origins or directions");
+	FI_REQUIRE(t || positions || normals || side, FI_ERR_INVALID, "every output is null");
+	FI_REQUIRE(t_min <= t_max, FI_ERR_INVALID, "t_min = %g, t_max = %g", static_cast<double>(t_min), static_cast<double>(t_max));  // (NaN fails)
+	fi::check_memory(memory);
+	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld rays in one call", n);
+}
+
+void check_march_image(const fi_march_options* options, const fi_camera* camera, const float* depth, int memory)
+{
+	fi::check_march_options(options);
+	FI_REQUIRE(camera != nullptr && depth != nullptr, FI_ERR_INVALID, "null camera or depth");
+	fi::check_memory(memory);
+	check_cameras(1, camera);
+}
+
+fi::MarchField march_field(const float* f, const float* w, int ndim, const int* sizes)
+{
+	fi::MarchField m{f, w, ndim, {1, 1, 1}};
+	for (int d = 0; d < ndim; ++d) { m.n[d] = sizes[d]; }
+	return m;
+}
+
+// the lattice field of an undivided context on its device: the caller's values, or its last solution (buf: an fp32 copy)
+fi::MarchField march_ctx_field(fi_ctx* c, const float* field, int memory, fi::DevBuf& buf)
+{
+	FI_REQUIRE(c->nranks == 1, FI_ERR_UNSUPPORTED, "rays against the field of a slab context are not supported");
+	fi::check_march_field(c->g.ndim, c->g.gn);
+	FI_REQUIRE(field || c->vectors_ready, FI_ERR_STATE, "no solution yet");
+	return march_field(fi::field_f32(c, field, memory, buf), nullptr, c->g.ndim, c->g.gn);
+}
+}  // namespace
+
+int fi_march_default_options(fi_march_options* options)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(options != nullptr, FI_ERR_INVALID, "options is null");
+	*options = fi_march_options{0.0f, 1.0f, 0.0f, 4, FI_MARCH_FRONT};
+	FI_API_END
+}
+
+int fi_field_raycast(const float* field, const float* weight, int ndim, const int* sizes, const fi_march_options* options, long n,
+                     const float* origins, const float* directions, float t_min, float t_max, float* t, float* positions,
+                     float* normals, signed char* side, int memory)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(field != nullptr, FI_ERR_INVALID, "field is null");
+	check_march_rays(options, n, origins, directions, t_min, t_max, t, positions, normals, side, memory);
+	const int64_t total = fi::check_march_field(ndim, sizes);
+	if (n == 0) { return FI_OK; }
+	fi::stage::In<float> f(field, total, memory, nullptr), w(weight, total, memory, nullptr);
+	fi::march_rays(march_field(f, w, ndim, sizes), *options, n, origins, directions, t_min, t_max, t, positions, normals, side, memory,
+	               nullptr);
+	FI_API_END
+}
+
+int fi_field_render(const float* field, const float* weight, const int* sizes, const fi_march_options* options,
+                    const fi_camera* camera, float* depth, float* positions, float* normals, float* incidence, int memory)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(field != nullptr, FI_ERR_INVALID, "field is null");
+	check_march_image(options, camera, depth, memory);
+	const int64_t total = fi::check_march_field(3, sizes);
+	fi::stage::In<float> f(field, total, memory, nullptr), w(weight, total, memory, nullptr);
+	fi::march_image(march_field(f, w, 3, sizes), *options, *camera, depth, positions, normals, incidence, memory, nullptr);
+	FI_API_END
+}
+
+int fi_raycast_field(fi_ctx* c, const float* field, const fi_march_options* options, long n, const float* origins,
+                     const float* directions, float t_min, float t_max, float* t, float* positions, float* normals, signed char* side,
+                     int memory)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	check_march_rays(options, n, origins, directions, t_min, t_max, t, positions, normals, side, memory);
+	fi::AllocStream      alloc_on(c->stream);
+	fi::DevBuf           buf;
+	const fi::MarchField f = march_ctx_field(c, field, memory, buf);
+	fi::march_rays(f, *options, n, origins, directions, t_min, t_max, t, positions, normals, side, memory, c->stream);
+	FI_HIP_TRY(hipStreamSynchronize(c->stream));  // (n = 0: the copy into buf ends before buf goes)
+	FI_API_END
+}
+
+int fi_render_field(fi_ctx* c, const float* field, const fi_march_options* options, const fi_camera* camera, float* depth,
+                    float* positions, float* normals, float* incidence, int memory)
+{
+	FI_API_BEGIN
+	fi::check_ctx(c);
+	fi::bind_device(c);
+	check_march_image(options, camera, depth, memory);
+	FI_REQUIRE(c->g.ndim != 2, FI_ERR_UNSUPPORTED, "an image of a 2-D field is not supported");
+	fi::AllocStream      alloc_on(c->stream);
+	fi::DevBuf           buf;
+	const fi::MarchField f = march_ctx_field(c, field, memory, buf);
+	fi::march_image(f, *options, *camera, depth, positions, normals, incidence, memory, c->stream);
+	FI_API_END
+}
+
+int fi_volume_raycast(const fi_volume* v, const fi_march_options* options, long n, const float* origins, const float* directions,
+                      float t_min, float t_max, float* t, float* positions, float* normals, signed char* side, int memory)
+{
+	FI_API_BEGIN
+	check_volume(v);
+	check_march_rays(options, n, origins, directions, t_min, t_max, t, positions, normals, side, memory);
+	fi::check_march_field(3, v->n);
+	fi::march_rays(march_field(v->tsdf.as<float>(), v->weight.as<float>(), 3, v->n), *options, n, origins, directions, t_min, t_max, t,
+	               positions, normals, side, memory, nullptr);
+	FI_API_END
+}
+
+int fi_volume_render(const fi_volume* v, const fi_march_options* options, const fi_camera* camera, float* depth, float* positions,
+                     float* normals, float* incidence, int memory)
+{
+	FI_API_BEGIN
+	check_volume(v);
+	check_march_image(options, camera, depth, memory);
+	fi::check_march_field(3, v->n);
+	fi::march_image(march_field(v->tsdf.as<float>(), v->weight.as<float>(), 3, v->n), *options, *camera, depth, positions, normals,
+	                incidence, memory, nullptr);
 	FI_API_END
 }
 

@@ -764,6 +764,99 @@ bool DepthVolume::constraints(std::vector<float>* positions, std::vector<float>*
 	return true;
 }
 
+namespace {
+fi_march_options to_c(const MarchOptions& o)
+{
+	return fi_march_options{o.iso, o.step, o.min_weight, o.refine, static_cast<int>(o.side)};
+}
+
+// the outputs of a ray march sized for n rays of D dimensions; false: no t, or origins and directions do not pair up
+bool size_rays(size_t D, const std::vector<float>& origins, const std::vector<float>& directions, std::vector<float>* t,
+               std::vector<float>* positions, std::vector<float>* normals, std::vector<signed char>* side, size_t* n)
+{
+	if (!t || origins.size() != directions.size() || origins.size() % D != 0) { return false; }
+	*n = origins.size() / D;
+	t->resize(*n);
+	if (positions) { positions->resize(D * *n); }
+	if (normals) { normals->resize(D * *n); }
+	if (side) { side->resize(*n); }
+	return true;
+}
+
+// the outputs of a render sized for the camera's image; false: no depth, or an empty image
+bool size_image(const DepthCamera& camera, std::vector<float>* depth, std::vector<float>* positions, std::vector<float>* normals,
+                std::vector<float>* incidence)
+{
+	if (!depth || camera.width <= 0 || camera.height <= 0) { return false; }
+	const size_t n = static_cast<size_t>(camera.width) * static_cast<size_t>(camera.height);
+	depth->resize(n);
+	if (positions) { positions->resize(3 * n); }
+	if (normals) { normals->resize(3 * n); }
+	if (incidence) { incidence->resize(n); }
+	return true;
+}
+
+float* data_or_null(std::vector<float>* v) { return v ? v->data() : nullptr; }
+}  // namespace
+
+bool DepthVolume::raycast(const std::vector<float>& origins, const std::vector<float>& directions, std::vector<float>* t,
+                          const MarchOptions& options, std::vector<float>* positions, std::vector<float>* normals,
+                          std::vector<signed char>* side, float t_min, float t_max) const
+{
+	size_t                 n = 0;
+	const fi_march_options o = to_c(options);
+	if (!volume_ || !size_rays(3, origins, directions, t, positions, normals, side, &n) ||
+	    fi_volume_raycast(volume_, &o, static_cast<long>(n), origins.data(), directions.data(), t_min, t_max, t->data(), data_or_null(positions),
+	                      data_or_null(normals), side ? side->data() : nullptr, FI_HOST) != FI_OK) {
+		warn("DepthVolume::raycast");
+		return false;
+	}
+	return true;
+}
+
+bool DepthVolume::render(const DepthCamera& camera, std::vector<float>* depth, const MarchOptions& options, std::vector<float>* positions,
+                         std::vector<float>* normals, std::vector<float>* incidence) const
+{
+	const fi_camera        c = to_c(camera);
+	const fi_march_options o = to_c(options);
+	if (!volume_ || !size_image(camera, depth, positions, normals, incidence) ||
+	    fi_volume_render(volume_, &o, &c, depth->data(), data_or_null(positions), data_or_null(normals), data_or_null(incidence), FI_HOST) !=
+	        FI_OK) {
+		warn("DepthVolume::render");
+		return false;
+	}
+	return true;
+}
+
+bool GpuLatticeField::march(const std::vector<float>& origins, const std::vector<float>& directions, std::vector<float>* t,
+                            const MarchOptions& options, std::vector<float>* positions, std::vector<float>* normals,
+                            std::vector<signed char>* side, float t_min, float t_max) const
+{
+	size_t                 n = 0;
+	const fi_march_options o = to_c(options);
+	if (!size_rays(sizes_.size(), origins, directions, t, positions, normals, side, &n) ||
+	    fi_raycast_field(ctx_, nullptr, &o, static_cast<long>(n), origins.data(), directions.data(), t_min, t_max, t->data(),
+	                     data_or_null(positions), data_or_null(normals), side ? side->data() : nullptr, FI_HOST) != FI_OK) {
+		warn("march");
+		return false;
+	}
+	return true;
+}
+
+bool GpuLatticeField::render(const DepthCamera& camera, std::vector<float>* depth, const MarchOptions& options,
+                             std::vector<float>* positions, std::vector<float>* normals, std::vector<float>* incidence) const
+{
+	const fi_camera        c = to_c(camera);
+	const fi_march_options o = to_c(options);
+	if (!size_image(camera, depth, positions, normals, incidence) ||
+	    fi_render_field(ctx_, nullptr, &o, &c, depth->data(), data_or_null(positions), data_or_null(normals), data_or_null(incidence),
+	                    FI_HOST) != FI_OK) {
+		warn("render");
+		return false;
+	}
+	return true;
+}
+
 bool GpuLatticeField::add_volume(const DepthVolume& volume, float value_weight, ValueKernel value_kernel, float min_weight)
 {
 	if (fi_add_volume(ctx_, volume.handle(), value_weight, static_cast<int>(value_kernel), min_weight) != FI_OK) {

@@ -1571,6 +1571,79 @@ int fi_volume_constraints(const fi_volume* volume, float min_weight, long* n, fl
                           int memory);
 int fi_add_volume(fi_ctx* ctx, const fi_volume* volume, float value_weight, int value_kernel, float min_weight);
 
+/* ---- rays and pinhole images of a lattice field or a depth volume --------------------------------------
+ * The contract (tests/march_reference.py is its definition in numpy).  A ray is marched through the trilinear
+ * (2-D: bilinear) interpolant of a field to the first crossing of `iso`.  All arithmetic is fp32, one rounding per operation,
+ * in the order written here with the parentheses given; min(a, b) is a < b ? a : b and max(a, b) is a > b ? a : b throughout.
+ * No atomics, results in input order, nothing depends on the launch: every output is defined bit for bit.
+ *
+ * The field: fp32, x fastest, ndim 2 or 3, every size >= 2; hi_j = (float)(size_j - 1).  A sample at position p (inside the
+ * box): cell c_j = min(floor(p_j), size_j - 2); f(p) = fi_sample's FI_SAMPLE_LINEAR value and g(p) its gradient, the same
+ * bits.  The sample is valid when f(p) is finite and, with a weight array (same shape), every corner of the cell has weight > 0
+ * and weight >= min_weight.  The unit normal n(p): len = sqrt((g_x g_x + g_y g_y) + g_z g_z) (2-D: sqrt(g_x g_x + g_y g_y)),
+ * n = g / len, or zero unless len > 0 and len is finite; it points towards increasing f.  inside(p): f(p) < iso, as
+ * fi_iso_extract decides it.
+ *
+ * A ray o + t d, t_min <= t <= t_max, d not normalised.  len_d = sqrt of the sum of d_j d_j in the order above.  The ray is none
+ * (t = NaN, NaN position, zero normal, side 0) where a component of o or d is not finite, or len_d is 0 or not finite.
+ *   1. t_enter = -inf, t_exit = +inf; for j = 0 .. ndim - 1: where d_j == 0 the ray is a miss unless 0 <= o_j <= hi_j; else
+ *      u = (0 - o_j) / d_j, v = (hi_j - o_j) / d_j, t_enter = max(t_enter, min(u, v)), t_exit = min(t_exit, max(u, v)).
+ *      t_a = max(t_enter, t_min), t_b = min(t_exit, t_max).  A miss if t_a > t_b or either is not finite.
+ *   2. dt = step / len_d; a miss unless dt > 0 and dt is finite.  Sample k = 0, 1, .. lies at t_k = min(t_a + (float)k dt, t_b);
+ *      the last one is the first with t_a + (float)k dt >= t_b, or sample FI_MARCH_MAX_SAMPLES - 1.
+ *   3. The sample at t: p_j = o_j + t d_j, then p_j = p_j > 0 ? (p_j > hi_j ? hi_j : p_j) : 0: inside the box
+ *      whatever the rounding at the faces did.
+ *   4. Two consecutive samples, both valid: a front bracket where the first is outside and the second inside, a back bracket
+ *      the other way round.  side: FI_MARCH_FRONT admits front brackets, FI_MARCH_BACK back ones, FI_MARCH_EITHER both.
+ *   5. The first admitted bracket (a, b) = (t_k-1, t_k) with values f_a, f_b is refined `refine` times: m = 0.5 (a + b);
+ *      the sample at m not valid: stop; inside(m) == inside(a): (a, f_a) = (m, f_m), else (b, f_b) = (m, f_m).  Then
+ *      t = a + ((f_a - iso) / (f_a - f_b)) (b - a); the hit's position is the sample position p at t (step 3), its normal
+ *      n(p), its side +1 (front) or -1 (back).
+ *   6. No admitted bracket, or a miss: t = +inf, NaN position, zero normal, side 0.
+ * It can miss two crossings inside one step and anything thinner than `step`.  Outputs t float[n], positions float[n ndim],
+ * normals float[n ndim], side signed char[n]; any may be NULL, not all four.
+ *
+ * An image (3-D only): pixel (row, col) of an fi_camera (above) casts the ray fi_depth_unproject assumes: px, py as there,
+ * e_a = 0 - t_a, o_j = (R_0j e_0 + R_1j e_1) + R_2j e_2, d_j = (R_0j px + R_1j py) + R_2j, over t_min = 0, t_max = +inf.
+ * depth = t (FI_DEPTH_Z) or t sqrt((px px + py py) + 1) (FI_DEPTH_RANGE); +inf where the ray is a miss or none, which
+ * fi_depth_unproject and fi_volume_integrate take as "no depth".  positions float[h w 3], normals float[h w 3], incidence
+ * float[h w] as fi_depth_unproject lays them out: s = (n_x (d_x / len_d) + n_y (d_y / len_d)) + n_z (d_z / len_d), q =
+ * min(-s, 1); unless q > 0 (a back hit, a zero normal) the normal and the incidence are zero.  A pixel without a hit: NaN
+ * position, zero normal, zero incidence.  depth is required, the others may be NULL.
+ *
+ * fi_raycast_field / fi_render_field: the field of the context's lattice; NULL: its last solution where it lives, an FI_F64
+ * one rounded to fp32 once as fi_iso_extract does (FI_ERR_STATE before the first solve).  fi_volume_raycast / fi_volume_render:
+ * the field is the volume's tsdf, the weight its W, both read in place; iso 0 is the surface.
+ * FI_ERR_INVALID: a non-finite iso, step not > 0 and finite, refine outside 0 .. 16, a side other than the three, a NaN
+ * min_weight, t_min > t_max or a NaN bound, a NULL required pointer, every output NULL, a bad memory kind, a bad camera,
+ * n < 0.  n = 0 is fine.  FI_ERR_UNSUPPORTED: n, the pixels or the lattice points >= 2^31, ndim = 1, a 2-D field for an image,
+ * a slab context.  `memory` applies to every buffer of a call but the camera and a volume's own arrays.
+ * Not offered: sphere tracing, empty-space skipping, sorted rays, cubic interpolation, exact per-cell roots, slabs, colour. */
+#define FI_MARCH_FRONT 0
+#define FI_MARCH_BACK 1
+#define FI_MARCH_EITHER 2
+#define FI_MARCH_MAX_SAMPLES 1048576
+typedef struct fi_march_options {
+	float iso, step, min_weight;
+	int   refine, side;
+} fi_march_options;
+int fi_march_default_options(fi_march_options* options); /* iso 0, step 1, min_weight 0, refine 4, FI_MARCH_FRONT */
+int fi_field_raycast(const float* field, const float* weight, int ndim, const int* sizes, const fi_march_options* options, long n,
+                     const float* origins, const float* directions, float t_min, float t_max, float* t, float* positions,
+                     float* normals, signed char* side, int memory);
+int fi_field_render(const float* field, const float* weight, const int* sizes, const fi_march_options* options,
+                    const fi_camera* camera, float* depth, float* positions, float* normals, float* incidence, int memory);
+int fi_raycast_field(fi_ctx* ctx, const float* field, const fi_march_options* options, long n, const float* origins,
+                     const float* directions, float t_min, float t_max, float* t, float* positions, float* normals,
+                     signed char* side, int memory);
+int fi_render_field(fi_ctx* ctx, const float* field, const fi_march_options* options, const fi_camera* camera, float* depth,
+                    float* positions, float* normals, float* incidence, int memory);
+int fi_volume_raycast(const fi_volume* volume, const fi_march_options* options, long n, const float* origins,
+                      const float* directions, float t_min, float t_max, float* t, float* positions, float* normals,
+                      signed char* side, int memory);
+int fi_volume_render(const fi_volume* volume, const fi_march_options* options, const fi_camera* camera, float* depth,
+                     float* positions, float* normals, float* incidence, int memory);
+
 #ifdef __cplusplus
 }
 #endif

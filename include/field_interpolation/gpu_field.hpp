@@ -101,6 +101,18 @@ struct DepthCamera
 	bool  range = true;
 };
 
+// How a ray is marched through a lattice field to its first crossing of `iso` (include/fi_hip.h fi_march_options): a sample
+// every `step` lattice units, `refine` (0 .. 16) bisections of the first bracket, and which crossings count: kFront, from
+// outside (f >= iso) to inside (f < iso), kBack, the opposite ones, or kEither.  min_weight: with a weight array (a volume's), a
+// sample counts only where every corner of its cell has weight > 0 and >= min_weight.
+enum class MarchSide { kFront = 0, kBack = 1, kEither = 2 };
+struct MarchOptions
+{
+	float     iso = 0, step = 1, min_weight = 0;
+	int       refine = 4;
+	MarchSide side = MarchSide::kFront;
+};
+
 // A truncated signed distance volume over a 3-D lattice on the device: tsdf (1 at first, in units of `truncation`) and weight
 // (0 at first) for every lattice point, x fastest.  integrate() fuses depth images into it; constraints() and
 // GpuLatticeField::add_volume hand its band to the solve.  The contract is include/fi_hip.h fi_volume_integrate.  Every call
@@ -125,6 +137,17 @@ public:
 	// the voxels with weight >= min_weight, weight > 0 and |tsdf| < 1 in ascending index: positions (3 floats each), values
 	// tsdf * truncation, weights W / max_weight; any may be null
 	bool constraints(std::vector<float>* positions, std::vector<float>* values, std::vector<float>* weights, float min_weight = 0) const;
+	// Rays against the surface the volume holds (its tsdf under its weights, read in place; iso 0 is the surface): t per ray
+	// origins[i] + t directions[i] (3 floats each, t_min <= t <= t_max), +inf without a crossing, NaN for a ray that is none;
+	// optional hit positions and unit gradients (3 floats each) and sides (+1 front, -1 back, 0 none).  The contract is
+	// include/fi_hip.h fi_field_raycast.
+	bool raycast(const std::vector<float>& origins, const std::vector<float>& directions, std::vector<float>* t,
+	             const MarchOptions& options = MarchOptions(), std::vector<float>* positions = nullptr, std::vector<float>* normals = nullptr,
+	             std::vector<signed char>* side = nullptr, float t_min = 0, float t_max = std::numeric_limits<float>::infinity()) const;
+	// The depth image of that surface seen by `camera`, in the camera's kind, +inf where a pixel's ray meets none; optional
+	// positions, normals and incidences in depth_to_points' layout, so that integrate() can take the image as it is.
+	bool render(const DepthCamera& camera, std::vector<float>* depth, const MarchOptions& options = MarchOptions(),
+	            std::vector<float>* positions = nullptr, std::vector<float>* normals = nullptr, std::vector<float>* incidence = nullptr) const;
 	const fi_volume* handle() const { return volume_; }
 
 private:
@@ -321,6 +344,16 @@ public:
 	bool raycast(const std::vector<float>& origins, const std::vector<float>& directions, std::vector<float>* t, float iso = 0,
 	             bool dual = false, float t_max = std::numeric_limits<float>::infinity(),
 	             std::vector<long long>* primitives = nullptr) const;
+	// The same rays marched through the last solution itself (2-D or 3-D), no mesh in between: DepthVolume::raycast's outputs,
+	// ndim floats per position and normal.  The contract is include/fi_hip.h fi_raycast_field.  false: no solution yet, or the
+	// library refused the call.
+	bool march(const std::vector<float>& origins, const std::vector<float>& directions, std::vector<float>* t,
+	           const MarchOptions& options = MarchOptions(), std::vector<float>* positions = nullptr, std::vector<float>* normals = nullptr,
+	           std::vector<signed char>* side = nullptr, float t_min = 0, float t_max = std::numeric_limits<float>::infinity()) const;
+	// The depth image of the last solution's iso-level seen by `camera` (3-D): DepthVolume::render's outputs.  The contract is
+	// include/fi_hip.h fi_render_field.
+	bool render(const DepthCamera& camera, std::vector<float>* depth, const MarchOptions& options = MarchOptions(),
+	            std::vector<float>* positions = nullptr, std::vector<float>* normals = nullptr, std::vector<float>* incidence = nullptr) const;
 
 	// Iteratively reweighted least squares for data with gross errors: a plain solve, then up to options.rounds solves, each
 	// after the data points were reweighted by their residuals against the previous field (fi_solve_robust; every solve as
