@@ -263,32 +263,28 @@ def lib():
     L.fi_group_sample.argtypes = [vp, fp, C.c_long, fp, C.c_int, C.c_float, fp, fp]
     L.fi_sample.argtypes = [vp, fp, C.c_long, fp, C.c_int, C.c_float, fp, fp, C.c_int]
     L.fi_sample_field.argtypes = [fp, C.c_int, ip, C.c_long, fp, C.c_int, C.c_float, fp, fp, C.c_int]
-    L.fi_nearest.argtypes = [vp, C.c_long, fp, C.c_float, fp, vp, C.c_int]
-    L.fi_distance_field.argtypes = [vp, C.c_float, fp, vp, C.c_int]
     L.fi_points_create.argtypes = [C.POINTER(vp), C.c_int, C.c_long, fp, C.c_int]
-    L.fi_points_nearest.argtypes = [vp, C.c_long, fp, C.c_float, fp, vp, C.c_int]
-    L.fi_points_distance_field.argtypes = [vp, ip, C.c_float, fp, vp, C.c_int]
+    # the operations on a point set: fi_<op> over a context's data points and fi_points_<op> over a set of its own take the
+    # same arguments after the handle (fi_points_distance_field: a lattice first, which a context brings along)
+    POINT_OPS = {
+        "nearest": [C.c_long, fp, C.c_float, fp, vp, C.c_int],
+        "distance_field": [C.c_float, fp, vp, C.c_int],
+        "knn": [C.c_long, fp, C.c_int, C.c_float, fp, vp, C.c_int],
+        "estimate_normals": [C.c_int, C.c_float, C.c_int, fp, C.c_long, fp, fp, C.c_int],
+        "orient_normals": [C.c_int, C.c_float, C.c_int, fp, C.c_long, fp, vp, C.c_int],
+        "radius_count": [C.c_long, fp, C.c_float, C.c_int, vp, C.c_int],
+        "neighbour_distances": [C.c_int, C.c_float, fp, fp, vp, C.c_int],
+        "outliers_statistical": [C.c_int, C.c_float, C.c_float, vp, C.POINTER(FiOutlierStats), C.c_int],
+        "outliers_radius": [C.c_float, C.c_int, vp, C.POINTER(C.c_long), C.c_int],
+        "mls_project": [C.c_long, fp, C.c_int, C.c_float, C.c_int, C.c_float, fp, fp, fp, fp, vp, C.c_int],
+        "cluster": [C.c_float, C.c_int, vp, vp, C.POINTER(FiClusterStats), C.c_int],
+    }
+    for op, args in POINT_OPS.items():
+        getattr(L, "fi_" + op).argtypes = [vp] + args
+        getattr(L, "fi_points_" + op).argtypes = [vp] + ([ip] if op == "distance_field" else []) + args
     L.fi_points_destroy.argtypes = [vp]
-    L.fi_knn.argtypes = [vp, C.c_long, fp, C.c_int, C.c_float, fp, vp, C.c_int]
-    L.fi_points_knn.argtypes = [vp, C.c_long, fp, C.c_int, C.c_float, fp, vp, C.c_int]
-    L.fi_estimate_normals.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, C.c_long, fp, fp, C.c_int]
-    L.fi_points_estimate_normals.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, C.c_long, fp, fp, C.c_int]
-    L.fi_orient_normals.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, C.c_long, fp, vp, C.c_int]
-    L.fi_points_orient_normals.argtypes = [vp, C.c_int, C.c_float, C.c_int, fp, C.c_long, fp, vp, C.c_int]
-    L.fi_radius_count.argtypes = [vp, C.c_long, fp, C.c_float, C.c_int, vp, C.c_int]
-    L.fi_points_radius_count.argtypes = [vp, C.c_long, fp, C.c_float, C.c_int, vp, C.c_int]
-    L.fi_neighbour_distances.argtypes = [vp, C.c_int, C.c_float, fp, fp, vp, C.c_int]
-    L.fi_points_neighbour_distances.argtypes = [vp, C.c_int, C.c_float, fp, fp, vp, C.c_int]
-    L.fi_outliers_statistical.argtypes = [vp, C.c_int, C.c_float, C.c_float, vp, C.POINTER(FiOutlierStats), C.c_int]
-    L.fi_points_outliers_statistical.argtypes = [vp, C.c_int, C.c_float, C.c_float, vp, C.POINTER(FiOutlierStats), C.c_int]
-    L.fi_outliers_radius.argtypes = [vp, C.c_float, C.c_int, vp, C.POINTER(C.c_long), C.c_int]
-    L.fi_points_outliers_radius.argtypes = [vp, C.c_float, C.c_int, vp, C.POINTER(C.c_long), C.c_int]
     L.fi_cloud_thin.argtypes = [C.c_int, C.c_long, fp, fp, fp, C.c_float, C.POINTER(C.c_float), C.c_int, fp, fp, fp, vp, vp, vp,
                                 C.POINTER(C.c_long), C.c_int]
-    L.fi_mls_project.argtypes = [vp, C.c_long, fp, C.c_int, C.c_float, C.c_int, C.c_float, fp, fp, fp, fp, vp, C.c_int]
-    L.fi_points_mls_project.argtypes = [vp, C.c_long, fp, C.c_int, C.c_float, C.c_int, C.c_float, fp, fp, fp, fp, vp, C.c_int]
-    L.fi_cluster.argtypes = [vp, C.c_float, C.c_int, vp, vp, C.POINTER(FiClusterStats), C.c_int]
-    L.fi_points_cluster.argtypes = [vp, C.c_float, C.c_int, vp, vp, C.POINTER(FiClusterStats), C.c_int]
     L.fi_cluster_measure.argtypes = [C.c_int, C.c_long, fp, vp, vp, C.c_long, C.POINTER(FiClusterRow), C.c_int]
     L.fi_plane_fit.argtypes = [C.c_int, C.c_long, fp, vp, C.POINTER(FiPlaneOptions), C.POINTER(FiPlaneModel), vp, C.c_int]
     L.fi_planes_segment.argtypes = [C.c_int, C.c_long, fp, vp, C.POINTER(FiPlaneOptions), C.c_int, C.c_long, vp,

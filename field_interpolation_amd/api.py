@@ -13,6 +13,7 @@ Buffers may be numpy arrays (host) or torch CUDA tensors (device pointers are pa
 import collections
 import ctypes as C
 import enum
+import functools
 import math
 
 import numpy as np
@@ -541,15 +542,6 @@ def _cluster(call, n, eps, min_points, core, stats, device):
     return out if len(out) > 1 else labels
 
 
-_CLUSTER_DOC = """Labels (num_points,) int32 of the clusters of the set's own points (include/fi_hip.h fi_cluster): a point
-        is CORE when at least min_points points of the set, itself included, lie within eps of it (a point exactly at eps
-        counts); core points within eps of each other share a cluster, and clusters are numbered by their lowest core point; a
-        point that is not core takes the cluster of its nearest core point within eps (ties: the lower index), and -1 (noise)
-        without one; a non-finite point gets -1.  min_points = 1: plain Euclidean clustering, every finite point in a cluster.
-        core=True adds the core mask (bool), stats=True a dict: clusters, core, border, noise, non_finite.  numpy arrays, or
-        torch tensors on the GPU with device=True.  An eps that spans the cloud makes every point visit every other: slow."""
-
-
 def _estimate_normals(call, ndim, n, k, max_distance, viewpoints, directions, variation, device):
     """Shared body of the normal estimation: call(k, max_distance, orient, guides, num_guides, normals, variation, memory)
     is the C entry point.  Outputs are numpy arrays, or torch tensors on the GPU when the guides are device tensors or with
@@ -708,7 +700,111 @@ def _distance_field(call, total, indices, device):
     return (dist, idx) if indices else dist
 
 
-class PointIndex:
+class _PointQueries:
+    """The operations on a point set, once for the two classes that have one.  "The set" is, on a PointIndex, its own rows;
+    on a LatticeField, the data points of the context: every add_points batch in the order they were added, the border
+    prior's rows left out.  num_points below is their number (PointIndex.num_points, LatticeField.point_count()), and a
+    point's index is its place in that order.  A context's search structure is built at the first call that needs it and
+    kept until the next add_points / clear_points; slab contexts refuse (a rank sees only its own points).
+
+    A class supplies _point_op(op) -- the C function fi_<op> or fi_points_<op> bound to its handle -- _point_ndim() and
+    _point_count()."""
+
+    def nearest(self, queries, max_distance=math.inf, indices=False):
+        """Distances (n,) float32 -- and with indices=True also the indices (n,) int64 -- of the nearest point of the set to
+        each of `queries` (n x ndim): +inf / -1 beyond max_distance or with no finite point, NaN / -1 for a non-finite query
+        (include/fi_hip.h fi_nearest)."""
+        return _nearest(self._point_op("nearest"), self._point_ndim(), queries, max_distance, indices)
+
+    def knn(self, queries, k, max_distance=math.inf, indices=True):
+        """Distances (n, k) float32 and, with indices=True, indices (n, k) int64 of the k nearest points of the set to each
+        of `queries` (n x ndim), nearest first, equal distances by ascending index; 1 <= k <= 32.  Entries that do not exist
+        (fewer than k finite points, beyond max_distance) are +inf / -1 at the end; a non-finite query gets NaN / -1.  A
+        point of the set finds itself (include/fi_hip.h fi_knn)."""
+        return _knn(self._point_op("knn"), self._point_ndim(), queries, k, max_distance, indices)
+
+    def estimate_normals(self, k=16, max_distance=math.inf, viewpoints=None, directions=None, variation=False, device=False,
+                         propagate=False):
+        """Normals (num_points, ndim) float32 of the set's points, each fitted to its k nearest points (itself included)
+        within max_distance by a local PCA in fp64 on the device; with variation=True also the surface variation
+        lambda_min / sum(lambda) (num_points,).  viewpoints: one sensor position (ndim,) or one per point -- normals look
+        at it (outward: the sign sdf_from_points wants); directions: rough normals, one per point, to agree with; neither:
+        each normal's largest component is positive, which is NOT a consistent orientation.  Points that are non-finite or
+        have fewer than ndim neighbours get a zero normal and a NaN variation (include/fi_hip.h fi_estimate_normals).
+        propagate=True: the canonical normals, then orient_normals(k, max_distance) over them -- a consistent orientation
+        without guides; viewpoints / directions then only vote for each component's sign."""
+        args = (self._point_op("estimate_normals"), self._point_ndim(), self._point_count(), k, max_distance, viewpoints, directions,
+                variation, device)
+        return _propagated(self, *args) if propagate else _estimate_normals(*args)
+
+    def orient_normals(self, normals, k=16, max_distance=math.inf, viewpoints=None, directions=None, components=False,
+                       device=False):
+        """`normals` (num_points, ndim) with one consistent sign per connected component of the set's k-nearest-neighbour
+        graph: signs spread along the minimum spanning forest that prefers parallel normal lines (Hoppe et al.), found on
+        the device; with components=True also each point's component (its smallest point index; -1 for a point that is
+        non-finite or has a zero or non-finite normal, which stays as it is).  Without guides a component's highest point
+        on the last axis looks up that axis; viewpoints / directions (as for estimate_normals) vote per component instead,
+        so one sensor position serves a whole closed object (include/fi_hip.h fi_orient_normals)."""
+        return _orient_normals(self._point_op("orient_normals"), self._point_ndim(), self._point_count(), normals, k, max_distance,
+                               viewpoints, directions, components, device)
+
+    def radius_count(self, queries, radius, limit=2 ** 31 - 1):
+        """How many finite points of the set lie within `radius` of each of `queries` (n x ndim), a point exactly on the
+        radius included: (n,) int32 where `queries` lives, -1 for a non-finite query.  The search of a query stops at `limit`
+        points and reports `limit`: pass the number you need to know about (include/fi_hip.h fi_radius_count)."""
+        return _radius_count(self._point_op("radius_count"), self._point_ndim(), queries, radius, limit)
+
+    def neighbour_distances(self, k=8, max_distance=math.inf, device=False):
+        """(mean, kth, counts), each (num_points,): the mean distance of every point of the set to its k nearest OTHER points
+        within max_distance (the point itself is left out by its index; a duplicate of it is a neighbour at distance 0), the
+        distance to the last of them, and how many they are.  No neighbour: +inf, +inf, 0; a non-finite point: NaN, NaN, 0.
+        1 <= k <= 32.  This is also the density weight: mean ** ndim or kth ** ndim is what a caller passes on as
+        `point_weights` so that an over-sampled patch does not outweigh the rest of the fit.  numpy arrays, or torch tensors
+        on the GPU with device=True (include/fi_hip.h fi_neighbour_distances)."""
+        return _neighbour_distances(self._point_op("neighbour_distances"), self._point_count(), k, max_distance, device)
+
+    def smooth(self, k=32, radius=None, degree=2, max_move=math.inf, normals=None, curvature=False, order=False, device=False):
+        if radius is None:
+            raise ValueError("smooth needs a radius")
+        return _mls_project(self._point_op("mls_project"), self._point_ndim(), self._point_count(), None, k, radius, degree, max_move,
+                            normals, curvature, order, device)
+    smooth.__doc__ = _MLS_DOC % ("the set's points (num_points of them, a point being its own neighbour)",
+                                 "when `normals` is a device tensor or with device=True")
+
+    def project(self, queries, k=32, radius=None, degree=2, max_move=math.inf, normals=None, curvature=False, order=False,
+                device=False):
+        if radius is None:
+            raise ValueError("project needs a radius")
+        return _mls_project(self._point_op("mls_project"), self._point_ndim(), self._point_count(), queries, k, radius, degree,
+                            max_move, normals, curvature, order, device)
+    project.__doc__ = _MLS_DOC % ("`queries` (n x ndim: any points -- a grid to resample a scan on, or more points than it has)",
+                                  "when `queries` or `normals` is a device tensor or with device=True")
+
+    def statistical_outliers(self, k=8, std_ratio=2.0, max_distance=math.inf, device=False):
+        """The statistical outlier rule of PCL and Open3D: a point is kept when its mean distance to its k nearest other
+        points (neighbour_distances) is at most mean + std_ratio * standard deviation of that figure over the cloud, the two
+        summed in a fixed order.  -> (keep (num_points,) bool, stats: counted, kept, mean, stddev, threshold); points that are
+        non-finite or have no neighbour within max_distance are neither counted nor kept (include/fi_hip.h
+        fi_outliers_statistical)."""
+        return _statistical_outliers(self._point_op("outliers_statistical"), self._point_count(), k, std_ratio, max_distance, device)
+
+    def radius_outliers(self, radius, min_neighbours=2, device=False):
+        """-> (keep (num_points,) bool, how many are kept): a point is kept when it is finite and at least min_neighbours
+        other finite points lie within `radius` of it (include/fi_hip.h fi_outliers_radius)."""
+        return _radius_outliers(self._point_op("outliers_radius"), self._point_count(), radius, min_neighbours, device)
+
+    def cluster(self, eps, min_points=1, core=False, stats=False, device=False):
+        """Labels (num_points,) int32 of the clusters of the set's points (include/fi_hip.h fi_cluster): a point
+        is CORE when at least min_points points of the set, itself included, lie within eps of it (a point exactly at eps
+        counts); core points within eps of each other share a cluster, and clusters are numbered by their lowest core point; a
+        point that is not core takes the cluster of its nearest core point within eps (ties: the lower index), and -1 (noise)
+        without one; a non-finite point gets -1.  min_points = 1: plain Euclidean clustering, every finite point in a cluster.
+        core=True adds the core mask (bool), stats=True a dict: clusters, core, border, noise, non_finite.  numpy arrays, or
+        torch tensors on the GPU with device=True.  An eps that spans the cloud makes every point visit every other: slow."""
+        return _cluster(self._point_op("cluster"), self._point_count(), eps, min_points, core, stats, device)
+
+
+class PointIndex(_PointQueries):
     """Exact nearest points of a point set of its own, searched on the device (include/fi_hip.h fi_points_create; the
     contract is fi_nearest's).  positions: (n, ndim) -- or (n,) in 1-D -- numpy array or torch tensor, x fastest; a point's
     index is its row."""
@@ -730,89 +826,14 @@ class PointIndex:
             _capi._LIB.fi_points_destroy(h)
         self._h = None
 
-    def nearest(self, queries, max_distance=math.inf, indices=False):
-        """Distances (n,) float32 -- and with indices=True also the indices (n,) int64 -- of the nearest point of the set to
-        each of `queries` (n x ndim): +inf / -1 beyond max_distance or with no finite point, NaN / -1 for a non-finite query."""
-        def call(n, q, md, d, i, mem):
-            return _capi.lib().fi_points_nearest(self._h, n, q, md, d, i, mem)
-        return _nearest(call, self.ndim, queries, max_distance, indices)
+    def _point_op(self, op):
+        return functools.partial(getattr(_capi.lib(), "fi_points_" + op), self._h)
 
-    def knn(self, queries, k, max_distance=math.inf, indices=True):
-        """Distances (n, k) float32 and, with indices=True, indices (n, k) int64 of the k nearest points of the set to each
-        of `queries` (n x ndim), nearest first, equal distances by ascending index; 1 <= k <= 32.  Entries that do not exist
-        (fewer than k finite points, beyond max_distance) are +inf / -1 at the end; a non-finite query gets NaN / -1.  A
-        point of the set finds itself (include/fi_hip.h fi_knn)."""
-        def call(n, q, kk, md, d, i, mem):
-            return _capi.lib().fi_points_knn(self._h, n, q, kk, md, d, i, mem)
-        return _knn(call, self.ndim, queries, k, max_distance, indices)
+    def _point_ndim(self):
+        return self.ndim
 
-    def estimate_normals(self, k=16, max_distance=math.inf, viewpoints=None, directions=None, variation=False, device=False,
-                         propagate=False):
-        """Normals (num_points, ndim) float32 of the set's own points, each fitted to its k nearest points (itself included)
-        within max_distance by a local PCA in fp64 on the device; with variation=True also the surface variation
-        lambda_min / sum(lambda) (num_points,).  viewpoints: one sensor position (ndim,) or one per point -- normals look
-        at it (outward: the sign sdf_from_points wants); directions: rough normals, one per point, to agree with; neither:
-        each normal's largest component is positive, which is NOT a consistent orientation.  Points that are non-finite or
-        have fewer than ndim neighbours get a zero normal and a NaN variation (include/fi_hip.h fi_estimate_normals).
-        propagate=True: the canonical normals, then orient_normals(k, max_distance) over them -- a consistent orientation
-        without guides; viewpoints / directions then only vote for each component's sign."""
-        def call(kk, md, orient, g, ng, nrm, var, mem):
-            return _capi.lib().fi_points_estimate_normals(self._h, kk, md, orient, g, ng, nrm, var, mem)
-        if not propagate:
-            return _estimate_normals(call, self.ndim, self.num_points, k, max_distance, viewpoints, directions, variation, device)
-        return _propagated(self, call, self.ndim, self.num_points, k, max_distance, viewpoints, directions, variation, device)
-
-    def orient_normals(self, normals, k=16, max_distance=math.inf, viewpoints=None, directions=None, components=False,
-                       device=False):
-        """`normals` (num_points, ndim) with one consistent sign per connected component of the set's k-nearest-neighbour
-        graph: signs spread along the minimum spanning forest that prefers parallel normal lines (Hoppe et al.), found on
-        the device; with components=True also each point's component (its smallest point index; -1 for a point that is
-        non-finite or has a zero or non-finite normal, which stays as it is).  Without guides a component's highest point
-        on the last axis looks up that axis; viewpoints / directions (as for estimate_normals) vote per component instead,
-        so one sensor position serves a whole closed object (include/fi_hip.h fi_orient_normals)."""
-        def call(kk, md, anchor, g, ng, nrm, comp, mem):
-            return _capi.lib().fi_points_orient_normals(self._h, kk, md, anchor, g, ng, nrm, comp, mem)
-        return _orient_normals(call, self.ndim, self.num_points, normals, k, max_distance, viewpoints, directions, components,
-                               device)
-
-    def radius_count(self, queries, radius, limit=2 ** 31 - 1):
-        """How many finite points of the set lie within `radius` of each of `queries` (n x ndim), a point exactly on the
-        radius included: (n,) int32 where `queries` lives, -1 for a non-finite query.  The search of a query stops at `limit`
-        points and reports `limit`: pass the number you need to know about (include/fi_hip.h fi_radius_count)."""
-        def call(n, q, r, lim, c, mem):
-            return _capi.lib().fi_points_radius_count(self._h, n, q, r, lim, c, mem)
-        return _radius_count(call, self.ndim, queries, radius, limit)
-
-    def neighbour_distances(self, k=8, max_distance=math.inf, device=False):
-        """(mean, kth, counts), each (num_points,): the mean distance of every point of the set to its k nearest OTHER points
-        within max_distance (the point itself is left out by its index; a duplicate of it is a neighbour at distance 0), the
-        distance to the last of them, and how many they are.  No neighbour: +inf, +inf, 0; a non-finite point: NaN, NaN, 0.
-        1 <= k <= 32.  This is also the density weight: mean ** ndim or kth ** ndim is what a caller passes on as
-        `point_weights` so that an over-sampled patch does not outweigh the rest of the fit.  numpy arrays, or torch tensors
-        on the GPU with device=True (include/fi_hip.h fi_neighbour_distances)."""
-        def call(kk, md, m, kt, c, mem):
-            return _capi.lib().fi_points_neighbour_distances(self._h, kk, md, m, kt, c, mem)
-        return _neighbour_distances(call, self.num_points, k, max_distance, device)
-
-    def _mls_call(self, n, q, kk, r, deg, mm, g, pos, nrm, cur, odr, mem):
-        return _capi.lib().fi_points_mls_project(self._h, n, q, kk, r, deg, mm, g, pos, nrm, cur, odr, mem)
-
-    def smooth(self, k=32, radius=None, degree=2, max_move=math.inf, normals=None, curvature=False, order=False, device=False):
-        if radius is None:
-            raise ValueError("smooth needs a radius")
-        return _mls_project(self._mls_call, self.ndim, self.num_points, None, k, radius, degree, max_move, normals, curvature,
-                            order, device)
-    smooth.__doc__ = _MLS_DOC % ("the set's own points (num_points of them, a point being its own neighbour)",
-                                 "when `normals` is a device tensor or with device=True")
-
-    def project(self, queries, k=32, radius=None, degree=2, max_move=math.inf, normals=None, curvature=False, order=False,
-                device=False):
-        if radius is None:
-            raise ValueError("project needs a radius")
-        return _mls_project(self._mls_call, self.ndim, self.num_points, queries, k, radius, degree, max_move, normals, curvature,
-                            order, device)
-    project.__doc__ = _MLS_DOC % ("`queries` (n x ndim: any points -- a grid to resample a scan on, or more points than it has)",
-                                  "when `queries` or `normals` is a device tensor or with device=True")
+    def _point_count(self):
+        return self.num_points
 
     def describe(self, normals, k=32, max_distance=math.inf, device=False):
         """(features (num_points, 33) float32, valid (num_points,) bool): what every point's neighbourhood looks like as a
@@ -838,29 +859,6 @@ class PointIndex:
         if n:
             check(_capi.lib().fi_points_describe(self._h, nrm, k, float(max_distance), pf, pv, FI_DEVICE if on_device else FI_HOST))
         return feat, _as_mask(valid)
-
-    def statistical_outliers(self, k=8, std_ratio=2.0, max_distance=math.inf, device=False):
-        """The statistical outlier rule of PCL and Open3D: a point is kept when its mean distance to its k nearest other
-        points (neighbour_distances) is at most mean + std_ratio * standard deviation of that figure over the cloud, the two
-        summed in a fixed order.  -> (keep (num_points,) bool, stats: counted, kept, mean, stddev, threshold); points that are
-        non-finite or have no neighbour within max_distance are neither counted nor kept (include/fi_hip.h
-        fi_outliers_statistical)."""
-        def call(kk, md, sr, kp, s, mem):
-            return _capi.lib().fi_points_outliers_statistical(self._h, kk, md, sr, kp, s, mem)
-        return _statistical_outliers(call, self.num_points, k, std_ratio, max_distance, device)
-
-    def radius_outliers(self, radius, min_neighbours=2, device=False):
-        """-> (keep (num_points,) bool, how many are kept): a point is kept when it is finite and at least min_neighbours
-        other finite points lie within `radius` of it (include/fi_hip.h fi_outliers_radius)."""
-        def call(r, mn, kp, nk, mem):
-            return _capi.lib().fi_points_outliers_radius(self._h, r, mn, kp, nk, mem)
-        return _radius_outliers(call, self.num_points, radius, min_neighbours, device)
-
-    def cluster(self, eps, min_points=1, core=False, stats=False, device=False):
-        def call(e, mp, lb, cr, st, mem):
-            return _capi.lib().fi_points_cluster(self._h, e, mp, lb, cr, st, mem)
-        return _cluster(call, self.num_points, eps, min_points, core, stats, device)
-    cluster.__doc__ = _CLUSTER_DOC
 
     def distance_field(self, sizes, max_distance=math.inf, indices=False, device=False):
         """PointIndex.nearest of every point of a lattice of `sizes` (x fastest), flat."""
@@ -1754,7 +1752,7 @@ def mesh_to_sdf(mesh, sizes, max_distance=math.inf):
     return SurfaceIndex.from_mesh(mesh).signed_distance_field(sizes, max_distance)
 
 
-class LatticeField:
+class LatticeField(_PointQueries):
     """field_interpolation.hpp:97-114 `LatticeField{sizes}`: sizes[0] (x) is the fastest axis.
 
     dtype: "f32" (vectors fp32, reductions fp64) or "f64".  rank/nranks select a slab of the slowest
@@ -2104,105 +2102,13 @@ class LatticeField:
             return _capi.lib().fi_render_field(self._h, s, C.byref(opt), cam, dp, pp, np_, ip, mem)
         return _march_image(call, camera, positions, normals, incidence, device)
 
-    def nearest(self, queries, max_distance=math.inf, indices=False):
-        """PointIndex.nearest over the data points of this context: every add_points batch in call order, the border prior's
-        rows left out (include/fi_hip.h fi_nearest).  The search structure is built at the first query and kept until the
-        next add_points / clear_points."""
-        def call(n, q, md, d, i, mem):
-            return _capi.lib().fi_nearest(self._h, n, q, md, d, i, mem)
-        return _nearest(call, len(self.sizes), queries, max_distance, indices)
+    def _point_op(self, op):
+        return functools.partial(getattr(_capi.lib(), "fi_" + op), self._h)
 
-    def knn(self, queries, k, max_distance=math.inf, indices=True):
-        """PointIndex.knn over the data points of this context (include/fi_hip.h fi_knn): the set and the search structure
-        are nearest()'s."""
-        def call(n, q, kk, md, d, i, mem):
-            return _capi.lib().fi_knn(self._h, n, q, kk, md, d, i, mem)
-        return _knn(call, len(self.sizes), queries, k, max_distance, indices)
+    def _point_ndim(self):
+        return len(self.sizes)
 
-    def estimate_normals(self, k=16, max_distance=math.inf, viewpoints=None, directions=None, variation=False, device=False,
-                         propagate=False):
-        """PointIndex.estimate_normals of the data points of this context, in the order they were added
-        (include/fi_hip.h fi_estimate_normals)."""
-        n = C.c_long(0)
-        check(_capi.lib().fi_point_count(self._h, C.byref(n)))
-
-        def call(kk, md, orient, g, ng, nrm, var, mem):
-            return _capi.lib().fi_estimate_normals(self._h, kk, md, orient, g, ng, nrm, var, mem)
-        if not propagate:
-            return _estimate_normals(call, len(self.sizes), n.value, k, max_distance, viewpoints, directions, variation, device)
-        return _propagated(self, call, len(self.sizes), n.value, k, max_distance, viewpoints, directions, variation, device)
-
-    def orient_normals(self, normals, k=16, max_distance=math.inf, viewpoints=None, directions=None, components=False,
-                       device=False):
-        """PointIndex.orient_normals over the data points of this context, in the order they were added
-        (include/fi_hip.h fi_orient_normals)."""
-        n = C.c_long(0)
-        check(_capi.lib().fi_point_count(self._h, C.byref(n)))
-
-        def call(kk, md, anchor, g, ng, nrm, comp, mem):
-            return _capi.lib().fi_orient_normals(self._h, kk, md, anchor, g, ng, nrm, comp, mem)
-        return _orient_normals(call, len(self.sizes), n.value, normals, k, max_distance, viewpoints, directions, components,
-                               device)
-
-    def _point_count(self):
-        n = C.c_long(0)
-        check(_capi.lib().fi_point_count(self._h, C.byref(n)))
-        return n.value
-
-    def radius_count(self, queries, radius, limit=2 ** 31 - 1):
-        """PointIndex.radius_count over the data points of this context (include/fi_hip.h fi_radius_count): the set and the
-        search structure are nearest()'s."""
-        def call(n, q, r, lim, c, mem):
-            return _capi.lib().fi_radius_count(self._h, n, q, r, lim, c, mem)
-        return _radius_count(call, len(self.sizes), queries, radius, limit)
-
-    def neighbour_distances(self, k=8, max_distance=math.inf, device=False):
-        """PointIndex.neighbour_distances of the data points of this context, in the order they were added
-        (include/fi_hip.h fi_neighbour_distances)."""
-        def call(kk, md, m, kt, c, mem):
-            return _capi.lib().fi_neighbour_distances(self._h, kk, md, m, kt, c, mem)
-        return _neighbour_distances(call, self._point_count(), k, max_distance, device)
-
-    def _mls_call(self, n, q, kk, r, deg, mm, g, pos, nrm, cur, odr, mem):
-        return _capi.lib().fi_mls_project(self._h, n, q, kk, r, deg, mm, g, pos, nrm, cur, odr, mem)
-
-    def smooth(self, k=32, radius=None, degree=2, max_move=math.inf, normals=None, curvature=False, order=False, device=False):
-        """PointIndex.smooth of the data points of this context, in the order they were added (include/fi_hip.h
-        fi_mls_project).  The context's points stay as they are."""
-        if radius is None:
-            raise ValueError("smooth needs a radius")
-        return _mls_project(self._mls_call, len(self.sizes), self._point_count(), None, k, radius, degree, max_move, normals,
-                            curvature, order, device)
-
-    def project(self, queries, k=32, radius=None, degree=2, max_move=math.inf, normals=None, curvature=False, order=False,
-                device=False):
-        """PointIndex.project over the data points of this context (include/fi_hip.h fi_mls_project): the set and the search
-        structure are nearest()'s."""
-        if radius is None:
-            raise ValueError("project needs a radius")
-        return _mls_project(self._mls_call, len(self.sizes), self._point_count(), queries, k, radius, degree, max_move, normals,
-                            curvature, order, device)
-
-    def statistical_outliers(self, k=8, std_ratio=2.0, max_distance=math.inf, device=False):
-        """PointIndex.statistical_outliers of the data points of this context, in the order they were added
-        (include/fi_hip.h fi_outliers_statistical)."""
-        def call(kk, md, sr, kp, s, mem):
-            return _capi.lib().fi_outliers_statistical(self._h, kk, md, sr, kp, s, mem)
-        return _statistical_outliers(call, self._point_count(), k, std_ratio, max_distance, device)
-
-    def radius_outliers(self, radius, min_neighbours=2, device=False):
-        """PointIndex.radius_outliers of the data points of this context, in the order they were added
-        (include/fi_hip.h fi_outliers_radius)."""
-        def call(r, mn, kp, nk, mem):
-            return _capi.lib().fi_outliers_radius(self._h, r, mn, kp, nk, mem)
-        return _radius_outliers(call, self._point_count(), radius, min_neighbours, device)
-
-    def cluster(self, eps, min_points=1, core=False, stats=False, device=False):
-        """PointIndex.cluster of the data points of this context, in the order they were added (include/fi_hip.h
-        fi_cluster)."""
-        def call(e, mp, lb, cr, st, mem):
-            return _capi.lib().fi_cluster(self._h, e, mp, lb, cr, st, mem)
-        return _cluster(call, self._point_count(), eps, min_points, core, stats, device)
+    _point_count = point_count
 
     def distance_field(self, max_distance=math.inf, indices=False, device=False):
         """LatticeField.nearest of every lattice point (x fastest), flat: numpy arrays, or torch tensors with device=True."""

@@ -1376,40 +1376,89 @@ void check_field_out(float max_distance, const float* out, int memory)
 	fi::check_memory(memory);
 }
 
-// the border prior's reason: a slab context holds only the points near its slab
-void check_undivided(const fi_ctx* c)
-{
-	FI_REQUIRE(c->nranks == 1, FI_ERR_UNSUPPORTED, "nearest points on a slab context: a rank sees only its own points");
-}
-
 void check_points(const fi_points* h)
 {
 	FI_REQUIRE(h != nullptr, FI_ERR_INVALID, "point set is null");
 	FI_HIP_TRY(hipSetDevice(h->device));
 }
+
+// The point set of a call: the data points of a context (fi_<op>) or a set of its own (fi_points_<op>).  Every operation
+// on a point set is written once below, over this; its two exported names only say which handle they were given.  A body
+// goes: bind(), the operation's own argument checks, whole(), index().
+struct PointSet {
+	fi_ctx*          c = nullptr;
+	const fi_points* h = nullptr;
+	const bool       of_ctx;
+	PointSet(fi_ctx* c_) : c(c_), of_ctx(true) {}
+	PointSet(const fi_points* h_) : h(h_), of_ctx(false) {}
+
+	// a null handle refused; the handle's device current
+	void bind() const
+	{
+		if (!of_ctx) { return check_points(h); }
+		fi::check_ctx(c);
+		fi::bind_device(c);
+	}
+	int         ndim() const { return of_ctx ? c->g.ndim : h->t.D; }
+	hipStream_t stream() const { return of_ctx ? c->stream : nullptr; }
+	// the border prior's reason: a slab context holds only the points near its slab
+	void whole() const
+	{
+		FI_REQUIRE(!of_ctx || c->nranks == 1, FI_ERR_UNSUPPORTED, "nearest points on a slab context: a rank sees only its own points");
+	}
+	// (a context's is built here, at the first call that comes this far)
+	const fi::NearestIndex& index() const { return of_ctx ? fi::nearest_of(c) : h->t; }
+};
+
+int points_nearest(PointSet s, long n, const float* queries, float max_distance, float* distances, long long* indices, int memory)
+{
+	FI_API_BEGIN
+	s.bind();
+	check_nearest(n, queries, max_distance, distances, memory);
+	s.whole();
+	// before a context builds its index; nothing changes for a set of its own: nearest_query's first line is this return
+	if (n == 0) { return FI_OK; }
+	fi::nearest_query(s.index(), n, queries, max_distance, distances, indices, memory, s.stream());
+	FI_API_END
+}
+
+// sizes: the lattice of a set of its own; a context brings its lattice
+int points_distance_field(PointSet s, const int* sizes, float max_distance, float* out, long long* indices, int memory)
+{
+	FI_API_BEGIN
+	s.bind();
+	if (s.of_ctx) {
+		sizes = s.c->g.gn;
+	} else {
+		FI_REQUIRE(sizes != nullptr, FI_ERR_INVALID, "sizes is null");
+		for (int d = 0; d < s.ndim(); ++d) { FI_REQUIRE(sizes[d] >= 1, FI_ERR_INVALID, "sizes[%d] = %d", d, sizes[d]); }
+	}
+	check_field_out(max_distance, out, memory);
+	s.whole();
+	fi::nearest_lattice(s.index(), sizes, max_distance, out, indices, memory, s.stream());
+	FI_API_END
+}
 }  // namespace
 
 int fi_nearest(fi_ctx* c, long n, const float* queries, float max_distance, float* distances, long long* indices, int memory)
 {
-	FI_API_BEGIN
-	fi::check_ctx(c);
-	fi::bind_device(c);
-	check_nearest(n, queries, max_distance, distances, memory);
-	check_undivided(c);
-	if (n == 0) { return FI_OK; }
-	fi::nearest_query(fi::nearest_of(c), n, queries, max_distance, distances, indices, memory, c->stream);
-	FI_API_END
+	return points_nearest(c, n, queries, max_distance, distances, indices, memory);
+}
+
+int fi_points_nearest(fi_points* h, long n, const float* queries, float max_distance, float* distances, long long* indices,
+                      int memory)
+{
+	return points_nearest(h, n, queries, max_distance, distances, indices, memory);
 }
 
 int fi_distance_field(fi_ctx* c, float max_distance, float* out, long long* indices, int memory)
 {
-	FI_API_BEGIN
-	fi::check_ctx(c);
-	fi::bind_device(c);
-	check_field_out(max_distance, out, memory);
-	check_undivided(c);
-	fi::nearest_lattice(fi::nearest_of(c), c->g.gn, max_distance, out, indices, memory, c->stream);
-	FI_API_END
+	return points_distance_field(c, nullptr, max_distance, out, indices, memory);
+}
+
+int fi_points_distance_field(fi_points* h, const int* sizes, float max_distance, float* out, long long* indices, int memory)
+{
+	return points_distance_field(h, sizes, max_distance, out, indices, memory);
 }
 
 int fi_points_create(fi_points** out, int ndim, long n, const float* positions, int memory)
@@ -1432,27 +1481,6 @@ int fi_points_create(fi_points** out, int ndim, long n, const float* positions, 
 	FI_API_END
 }
 
-int fi_points_nearest(fi_points* h, long n, const float* queries, float max_distance, float* distances, long long* indices,
-                      int memory)
-{
-	FI_API_BEGIN
-	check_points(h);
-	check_nearest(n, queries, max_distance, distances, memory);
-	fi::nearest_query(h->t, n, queries, max_distance, distances, indices, memory, nullptr);
-	FI_API_END
-}
-
-int fi_points_distance_field(fi_points* h, const int* sizes, float max_distance, float* out, long long* indices, int memory)
-{
-	FI_API_BEGIN
-	check_points(h);
-	FI_REQUIRE(sizes != nullptr, FI_ERR_INVALID, "sizes is null");
-	for (int d = 0; d < h->t.D; ++d) { FI_REQUIRE(sizes[d] >= 1, FI_ERR_INVALID, "sizes[%d] = %d", d, sizes[d]); }
-	check_field_out(max_distance, out, memory);
-	fi::nearest_lattice(h->t, sizes, max_distance, out, indices, memory, nullptr);
-	FI_API_END
-}
-
 int fi_points_destroy(fi_points* h) { return fi::destroy_handle(h); }
 
 
@@ -1463,70 +1491,76 @@ void check_k(int k)
 	FI_REQUIRE(1 <= k && k <= fi::kMaxNeighbours, FI_ERR_INVALID, "k must be 1..%d (got %d)", fi::kMaxNeighbours, k);
 }
 
-void check_normals(const fi::NearestIndex* t, int ndim, int k, float max_distance, int orient, const float* guides, long num_guides,
-                   const float* normals, int memory)
+// The arguments of fi_estimate_normals and fi_orient_normals that need no point set.  `mode` is the argument that says what the
+// guides are, under the name the operation's sentences give it; `fit`: a plane is fitted to the k neighbours.
+void check_normals(const char* mode_name, bool fit, int ndim, int k, float max_distance, int mode, const float* normals, int memory)
 {
 	FI_REQUIRE(ndim >= 2, FI_ERR_INVALID, "normals need 2 or 3 dimensions (got %d)", ndim);
 	check_k(k);
-	FI_REQUIRE(k >= ndim, FI_ERR_INVALID, "k = %d neighbours span no plane in %d dimensions", k, ndim);
+	FI_REQUIRE(!fit || k >= ndim, FI_ERR_INVALID, "k = %d neighbours span no plane in %d dimensions", k, ndim);
 	FI_REQUIRE(normals != nullptr, FI_ERR_INVALID, "normals is null");
 	FI_REQUIRE(max_distance >= 0.0f, FI_ERR_INVALID, "max_distance must be >= 0 (got %g)", static_cast<double>(max_distance));
 	fi::check_memory(memory);
-	FI_REQUIRE(orient == FI_ORIENT_NONE || orient == FI_ORIENT_VIEWPOINTS || orient == FI_ORIENT_DIRECTIONS, FI_ERR_INVALID,
-	           "bad orientation mode %d", orient);
-	if (orient == FI_ORIENT_NONE || !t) { return; }
-	FI_REQUIRE(guides != nullptr, FI_ERR_INVALID, "orientation mode %d without guides", orient);
-	FI_REQUIRE(num_guides == t->n || (orient == FI_ORIENT_VIEWPOINTS && num_guides == 1), FI_ERR_INVALID,
-	           "%ld guides for %lld points", num_guides, static_cast<long long>(t->n));
+	FI_REQUIRE(mode == FI_ORIENT_NONE || mode == FI_ORIENT_VIEWPOINTS || mode == FI_ORIENT_DIRECTIONS, FI_ERR_INVALID, "bad %s %d",
+	           mode_name, mode);
+}
+
+// ... and the guides against the set's size, once its index is there
+void check_guides(const char* mode_name, const fi::NearestIndex& t, int mode, const float* guides, long num_guides)
+{
+	if (mode == FI_ORIENT_NONE) { return; }
+	FI_REQUIRE(guides != nullptr, FI_ERR_INVALID, "%s %d without guides", mode_name, mode);
+	FI_REQUIRE(num_guides == t.n || (mode == FI_ORIENT_VIEWPOINTS && num_guides == 1), FI_ERR_INVALID, "%ld guides for %lld points",
+	           num_guides, static_cast<long long>(t.n));
+}
+
+int points_knn(PointSet s, long n, const float* queries, int k, float max_distance, float* distances, long long* indices, int memory)
+{
+	FI_API_BEGIN
+	s.bind();
+	check_nearest(n, queries, max_distance, distances, memory);
+	check_k(k);
+	s.whole();
+	if (n == 0) { return FI_OK; }  // (as in points_nearest: knn_query's first line)
+	fi::knn_query(s.index(), n, queries, k, max_distance, distances, indices, memory, s.stream());
+	FI_API_END
+}
+
+int points_estimate_normals(PointSet s, int k, float max_distance, int orient, const float* guides, long num_guides, float* normals,
+                            float* variation, int memory)
+{
+	FI_API_BEGIN
+	s.bind();
+	check_normals("orientation mode", true, s.ndim(), k, max_distance, orient, normals, memory);
+	s.whole();
+	const fi::NearestIndex& t = s.index();
+	check_guides("orientation mode", t, orient, guides, num_guides);
+	fi::estimate_normals(t, k, max_distance, orient, guides, num_guides, normals, variation, memory, s.stream());
+	FI_API_END
 }
 }  // namespace
 
 int fi_knn(fi_ctx* c, long n, const float* queries, int k, float max_distance, float* distances, long long* indices, int memory)
 {
-	FI_API_BEGIN
-	fi::check_ctx(c);
-	fi::bind_device(c);
-	check_nearest(n, queries, max_distance, distances, memory);
-	check_k(k);
-	check_undivided(c);
-	if (n == 0) { return FI_OK; }
-	fi::knn_query(fi::nearest_of(c), n, queries, k, max_distance, distances, indices, memory, c->stream);
-	FI_API_END
+	return points_knn(c, n, queries, k, max_distance, distances, indices, memory);
 }
 
 int fi_points_knn(fi_points* h, long n, const float* queries, int k, float max_distance, float* distances, long long* indices,
                   int memory)
 {
-	FI_API_BEGIN
-	check_points(h);
-	check_nearest(n, queries, max_distance, distances, memory);
-	check_k(k);
-	fi::knn_query(h->t, n, queries, k, max_distance, distances, indices, memory, nullptr);
-	FI_API_END
+	return points_knn(h, n, queries, k, max_distance, distances, indices, memory);
 }
 
 int fi_estimate_normals(fi_ctx* c, int k, float max_distance, int orient, const float* guides, long num_guides, float* normals,
                         float* variation, int memory)
 {
-	FI_API_BEGIN
-	fi::check_ctx(c);
-	fi::bind_device(c);
-	check_normals(nullptr, c->g.ndim, k, max_distance, orient, guides, num_guides, normals, memory);
-	check_undivided(c);
-	const fi::NearestIndex& t = fi::nearest_of(c);
-	check_normals(&t, c->g.ndim, k, max_distance, orient, guides, num_guides, normals, memory);
-	fi::estimate_normals(t, k, max_distance, orient, guides, num_guides, normals, variation, memory, c->stream);
-	FI_API_END
+	return points_estimate_normals(c, k, max_distance, orient, guides, num_guides, normals, variation, memory);
 }
 
 int fi_points_estimate_normals(fi_points* h, int k, float max_distance, int orient, const float* guides, long num_guides,
                                float* normals, float* variation, int memory)
 {
-	FI_API_BEGIN
-	check_points(h);
-	check_normals(&h->t, h->t.D, k, max_distance, orient, guides, num_guides, normals, memory);
-	fi::estimate_normals(h->t, k, max_distance, orient, guides, num_guides, normals, variation, memory, nullptr);
-	FI_API_END
+	return points_estimate_normals(h, k, max_distance, orient, guides, num_guides, normals, variation, memory);
 }
 
 
@@ -1546,29 +1580,29 @@ void check_mls(int ndim, long n, const float* queries, int k, float radius, int 
 	FI_REQUIRE(n >= 0, FI_ERR_INVALID, "n = %ld", n);
 	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld queries in one call", n);  // (one thread per query)
 }
+
+int points_mls_project(PointSet s, long n, const float* queries, int k, float radius, int degree, float max_move, const float* guide_normals,
+                       float* positions, float* normals, float* curvature, unsigned char* order, int memory)
+{
+	FI_API_BEGIN
+	s.bind();
+	check_mls(s.ndim(), n, queries, k, radius, degree, max_move, positions || normals || curvature || order, memory);
+	s.whole();
+	fi::mls_project(s.index(), n, queries, k, radius, degree, max_move, guide_normals, positions, normals, curvature, order, memory, s.stream());
+	FI_API_END
+}
 }  // namespace
 
 int fi_mls_project(fi_ctx* c, long n, const float* queries, int k, float radius, int degree, float max_move, const float* guide_normals,
                    float* positions, float* normals, float* curvature, unsigned char* order, int memory)
 {
-	FI_API_BEGIN
-	fi::check_ctx(c);
-	fi::bind_device(c);
-	check_mls(c->g.ndim, n, queries, k, radius, degree, max_move, positions || normals || curvature || order, memory);
-	check_undivided(c);
-	fi::mls_project(fi::nearest_of(c), n, queries, k, radius, degree, max_move, guide_normals, positions, normals, curvature, order, memory,
-	                c->stream);
-	FI_API_END
+	return points_mls_project(c, n, queries, k, radius, degree, max_move, guide_normals, positions, normals, curvature, order, memory);
 }
 
 int fi_points_mls_project(fi_points* h, long n, const float* queries, int k, float radius, int degree, float max_move,
                           const float* guide_normals, float* positions, float* normals, float* curvature, unsigned char* order, int memory)
 {
-	FI_API_BEGIN
-	check_points(h);
-	check_mls(h->t.D, n, queries, k, radius, degree, max_move, positions || normals || curvature || order, memory);
-	fi::mls_project(h->t, n, queries, k, radius, degree, max_move, guide_normals, positions, normals, curvature, order, memory, nullptr);
-	FI_API_END
+	return points_mls_project(h, n, queries, k, radius, degree, max_move, guide_normals, positions, normals, curvature, order, memory);
 }
 
 
@@ -1602,90 +1636,90 @@ void check_statistical(int k, float max_distance, float std_ratio, bool any_outp
 	check_neighbours(k, max_distance, any_output, memory);
 	FI_REQUIRE(std_ratio >= 0.0f, FI_ERR_INVALID, "std_ratio must be >= 0 (got %g)", static_cast<double>(std_ratio));
 }
+
+int points_radius_count(PointSet s, long n, const float* queries, float radius, int limit, int* counts, int memory)
+{
+	FI_API_BEGIN
+	s.bind();
+	check_radius_count(n, queries, radius, limit, counts, memory);
+	s.whole();
+	if (n == 0) { return FI_OK; }  // (as in points_nearest: cloud_radius_count's first line)
+	fi::cloud_radius_count(s.index(), n, queries, radius, limit, counts, memory, s.stream());
+	FI_API_END
+}
+
+int points_neighbour_distances(PointSet s, int k, float max_distance, float* mean, float* kth, int* counts, int memory)
+{
+	FI_API_BEGIN
+	s.bind();
+	check_neighbours(k, max_distance, mean || kth || counts, memory);
+	s.whole();
+	fi::cloud_neighbour_distances(s.index(), k, max_distance, mean, kth, counts, memory, s.stream());
+	FI_API_END
+}
+
+int points_outliers_statistical(PointSet s, int k, float max_distance, float std_ratio, unsigned char* keep, fi_outlier_stats* stats,
+                                int memory)
+{
+	FI_API_BEGIN
+	s.bind();
+	check_statistical(k, max_distance, std_ratio, keep || stats, memory);
+	s.whole();
+	fi::cloud_outliers_statistical(s.index(), k, max_distance, std_ratio, keep, stats, memory, s.stream());
+	FI_API_END
+}
+
+int points_outliers_radius(PointSet s, float radius, int min_neighbours, unsigned char* keep, long* num_kept, int memory)
+{
+	FI_API_BEGIN
+	s.bind();
+	check_radius(radius, min_neighbours, "min_neighbours", memory);
+	FI_REQUIRE(keep || num_kept, FI_ERR_INVALID, "every output is null");
+	s.whole();
+	fi::cloud_outliers_radius(s.index(), radius, min_neighbours, keep, num_kept, memory, s.stream());
+	FI_API_END
+}
 }  // namespace
 
 int fi_radius_count(fi_ctx* c, long n, const float* queries, float radius, int limit, int* counts, int memory)
 {
-	FI_API_BEGIN
-	fi::check_ctx(c);
-	fi::bind_device(c);
-	check_radius_count(n, queries, radius, limit, counts, memory);
-	check_undivided(c);
-	if (n == 0) { return FI_OK; }
-	fi::cloud_radius_count(fi::nearest_of(c), n, queries, radius, limit, counts, memory, c->stream);
-	FI_API_END
+	return points_radius_count(c, n, queries, radius, limit, counts, memory);
 }
 
 int fi_points_radius_count(fi_points* h, long n, const float* queries, float radius, int limit, int* counts, int memory)
 {
-	FI_API_BEGIN
-	check_points(h);
-	check_radius_count(n, queries, radius, limit, counts, memory);
-	fi::cloud_radius_count(h->t, n, queries, radius, limit, counts, memory, nullptr);
-	FI_API_END
+	return points_radius_count(h, n, queries, radius, limit, counts, memory);
 }
 
 int fi_neighbour_distances(fi_ctx* c, int k, float max_distance, float* mean, float* kth, int* counts, int memory)
 {
-	FI_API_BEGIN
-	fi::check_ctx(c);
-	fi::bind_device(c);
-	check_neighbours(k, max_distance, mean || kth || counts, memory);
-	check_undivided(c);
-	fi::cloud_neighbour_distances(fi::nearest_of(c), k, max_distance, mean, kth, counts, memory, c->stream);
-	FI_API_END
+	return points_neighbour_distances(c, k, max_distance, mean, kth, counts, memory);
 }
 
 int fi_points_neighbour_distances(fi_points* h, int k, float max_distance, float* mean, float* kth, int* counts, int memory)
 {
-	FI_API_BEGIN
-	check_points(h);
-	check_neighbours(k, max_distance, mean || kth || counts, memory);
-	fi::cloud_neighbour_distances(h->t, k, max_distance, mean, kth, counts, memory, nullptr);
-	FI_API_END
+	return points_neighbour_distances(h, k, max_distance, mean, kth, counts, memory);
 }
 
 int fi_outliers_statistical(fi_ctx* c, int k, float max_distance, float std_ratio, unsigned char* keep, fi_outlier_stats* stats, int memory)
 {
-	FI_API_BEGIN
-	fi::check_ctx(c);
-	fi::bind_device(c);
-	check_statistical(k, max_distance, std_ratio, keep || stats, memory);
-	check_undivided(c);
-	fi::cloud_outliers_statistical(fi::nearest_of(c), k, max_distance, std_ratio, keep, stats, memory, c->stream);
-	FI_API_END
+	return points_outliers_statistical(c, k, max_distance, std_ratio, keep, stats, memory);
 }
 
 int fi_points_outliers_statistical(fi_points* h, int k, float max_distance, float std_ratio, unsigned char* keep, fi_outlier_stats* stats,
                                    int memory)
 {
-	FI_API_BEGIN
-	check_points(h);
-	check_statistical(k, max_distance, std_ratio, keep || stats, memory);
-	fi::cloud_outliers_statistical(h->t, k, max_distance, std_ratio, keep, stats, memory, nullptr);
-	FI_API_END
+	return points_outliers_statistical(h, k, max_distance, std_ratio, keep, stats, memory);
 }
 
 int fi_outliers_radius(fi_ctx* c, float radius, int min_neighbours, unsigned char* keep, long* num_kept, int memory)
 {
-	FI_API_BEGIN
-	fi::check_ctx(c);
-	fi::bind_device(c);
-	check_radius(radius, min_neighbours, "min_neighbours", memory);
-	FI_REQUIRE(keep || num_kept, FI_ERR_INVALID, "every output is null");
-	check_undivided(c);
-	fi::cloud_outliers_radius(fi::nearest_of(c), radius, min_neighbours, keep, num_kept, memory, c->stream);
-	FI_API_END
+	return points_outliers_radius(c, radius, min_neighbours, keep, num_kept, memory);
 }
 
 int fi_points_outliers_radius(fi_points* h, float radius, int min_neighbours, unsigned char* keep, long* num_kept, int memory)
 {
-	FI_API_BEGIN
-	check_points(h);
-	check_radius(radius, min_neighbours, "min_neighbours", memory);
-	FI_REQUIRE(keep || num_kept, FI_ERR_INVALID, "every output is null");
-	fi::cloud_outliers_radius(h->t, radius, min_neighbours, keep, num_kept, memory, nullptr);
-	FI_API_END
+	return points_outliers_radius(h, radius, min_neighbours, keep, num_kept, memory);
 }
 
 int fi_cloud_thin(int ndim, long n, const float* positions, const float* normals, const float* values, float cell, const float* origin,
@@ -1719,26 +1753,26 @@ void check_cluster(float eps, int min_points, const int* labels, const fi_cluste
 	fi::check_memory(memory);
 	FI_REQUIRE(labels || stats, FI_ERR_INVALID, "every output is null");
 }
+
+int points_cluster(PointSet s, float eps, int min_points, int* labels, unsigned char* core, fi_cluster_stats* stats, int memory)
+{
+	FI_API_BEGIN
+	s.bind();
+	check_cluster(eps, min_points, labels, stats, memory);
+	s.whole();
+	fi::cluster_labels(s.index(), eps, min_points, labels, core, stats, memory, s.stream());
+	FI_API_END
+}
 }  // namespace
 
 int fi_cluster(fi_ctx* c, float eps, int min_points, int* labels, unsigned char* core, fi_cluster_stats* stats, int memory)
 {
-	FI_API_BEGIN
-	fi::check_ctx(c);
-	fi::bind_device(c);
-	check_cluster(eps, min_points, labels, stats, memory);
-	check_undivided(c);
-	fi::cluster_labels(fi::nearest_of(c), eps, min_points, labels, core, stats, memory, c->stream);
-	FI_API_END
+	return points_cluster(c, eps, min_points, labels, core, stats, memory);
 }
 
 int fi_points_cluster(fi_points* h, float eps, int min_points, int* labels, unsigned char* core, fi_cluster_stats* stats, int memory)
 {
-	FI_API_BEGIN
-	check_points(h);
-	check_cluster(eps, min_points, labels, stats, memory);
-	fi::cluster_labels(h->t, eps, min_points, labels, core, stats, memory, nullptr);
-	FI_API_END
+	return points_cluster(h, eps, min_points, labels, core, stats, memory);
 }
 
 int fi_cluster_measure(int ndim, long n, const float* positions, const int* labels, const unsigned char* core, long num_clusters,
@@ -1921,45 +1955,30 @@ int fi_feature_match(int dim, long n_a, const float* a, const unsigned char* val
 
 // ---- a consistent sign for normals (fi_orient.hip) ----------------------------------------------
 namespace {
-void check_orient(const fi::NearestIndex* t, int ndim, int k, float max_distance, int anchor, const float* guides, long num_guides,
-                  const float* normals, int memory)
+int points_orient_normals(PointSet s, int k, float max_distance, int anchor, const float* guides, long num_guides, float* normals,
+                          long long* components, int memory)
 {
-	FI_REQUIRE(ndim >= 2, FI_ERR_INVALID, "normals need 2 or 3 dimensions (got %d)", ndim);
-	check_k(k);
-	FI_REQUIRE(normals != nullptr, FI_ERR_INVALID, "normals is null");
-	FI_REQUIRE(max_distance >= 0.0f, FI_ERR_INVALID, "max_distance must be >= 0 (got %g)", static_cast<double>(max_distance));
-	fi::check_memory(memory);
-	FI_REQUIRE(anchor == FI_ORIENT_NONE || anchor == FI_ORIENT_VIEWPOINTS || anchor == FI_ORIENT_DIRECTIONS, FI_ERR_INVALID,
-	           "bad anchor %d", anchor);
-	if (anchor == FI_ORIENT_NONE || !t) { return; }
-	FI_REQUIRE(guides != nullptr, FI_ERR_INVALID, "anchor %d without guides", anchor);
-	FI_REQUIRE(num_guides == t->n || (anchor == FI_ORIENT_VIEWPOINTS && num_guides == 1), FI_ERR_INVALID,
-	           "%ld guides for %lld points", num_guides, static_cast<long long>(t->n));
+	FI_API_BEGIN
+	s.bind();
+	check_normals("anchor", false, s.ndim(), k, max_distance, anchor, normals, memory);
+	s.whole();
+	const fi::NearestIndex& t = s.index();
+	check_guides("anchor", t, anchor, guides, num_guides);
+	fi::orient_normals(t, k, max_distance, anchor, guides, num_guides, normals, components, memory, s.stream());
+	FI_API_END
 }
 }  // namespace
 
 int fi_orient_normals(fi_ctx* c, int k, float max_distance, int anchor, const float* guides, long num_guides, float* normals,
                       long long* components, int memory)
 {
-	FI_API_BEGIN
-	fi::check_ctx(c);
-	fi::bind_device(c);
-	check_orient(nullptr, c->g.ndim, k, max_distance, anchor, guides, num_guides, normals, memory);
-	check_undivided(c);
-	const fi::NearestIndex& t = fi::nearest_of(c);
-	check_orient(&t, c->g.ndim, k, max_distance, anchor, guides, num_guides, normals, memory);
-	fi::orient_normals(t, k, max_distance, anchor, guides, num_guides, normals, components, memory, c->stream);
-	FI_API_END
+	return points_orient_normals(c, k, max_distance, anchor, guides, num_guides, normals, components, memory);
 }
 
 int fi_points_orient_normals(fi_points* h, int k, float max_distance, int anchor, const float* guides, long num_guides,
                              float* normals, long long* components, int memory)
 {
-	FI_API_BEGIN
-	check_points(h);
-	check_orient(&h->t, h->t.D, k, max_distance, anchor, guides, num_guides, normals, memory);
-	fi::orient_normals(h->t, k, max_distance, anchor, guides, num_guides, normals, components, memory, nullptr);
-	FI_API_END
+	return points_orient_normals(h, k, max_distance, anchor, guides, num_guides, normals, components, memory);
 }
 
 
