@@ -44,6 +44,8 @@ SYMBOLS = [
     "fi_volume_constraints", "fi_add_volume",
     "fi_march_default_options", "fi_field_raycast", "fi_field_render", "fi_raycast_field", "fi_render_field", "fi_volume_raycast",
     "fi_volume_render",
+    "fi_volume_set_channels", "fi_volume_channels", "fi_volume_colour_load", "fi_volume_colour_copy", "fi_volume_integrate_colour",
+    "fi_volume_colour_sample", "fi_volume_render_colour", "fi_volume_colour_constraints",
 ]
 FI_LOSS = {"huber": 0, "cauchy": 1, "tukey": 2}
 FI_LOSS_NONE = -1
@@ -329,6 +331,14 @@ def lib():
     L.fi_render_field.argtypes = [vp, fp, mo, cam, fp, fp, fp, fp, C.c_int]
     L.fi_volume_raycast.argtypes = [vp, mo, C.c_long, fp, fp, C.c_float, C.c_float, fp, fp, fp, vp, C.c_int]
     L.fi_volume_render.argtypes = [vp, mo, cam, fp, fp, fp, fp, C.c_int]
+    L.fi_volume_set_channels.argtypes = [vp, C.c_int]
+    L.fi_volume_channels.argtypes = [vp, C.POINTER(C.c_int)]
+    L.fi_volume_colour_load.argtypes = [vp, fp, fp, C.c_int]
+    L.fi_volume_colour_copy.argtypes = [vp, fp, fp, C.c_int]
+    L.fi_volume_integrate_colour.argtypes = [vp, C.c_long, cam, fp, fp, fp, C.c_float, fp, C.c_float, C.c_int]
+    L.fi_volume_colour_sample.argtypes = [vp, C.c_float, C.c_long, fp, fp, vp, C.c_int]
+    L.fi_volume_render_colour.argtypes = [vp, mo, cam, C.c_float, fp, fp, fp, fp, fp, C.c_int]
+    L.fi_volume_colour_constraints.argtypes = [vp, C.c_float, C.POINTER(C.c_long), fp, fp, fp, C.c_int]
     for name in SYMBOLS:
         getattr(L, name)          # AttributeError if the .so lacks a declared symbol
     _LIB = L

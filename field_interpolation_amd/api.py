@@ -2533,14 +2533,23 @@ def _flat_images(images):
 class DepthVolume:
     """A truncated signed distance volume over a 3-D lattice on the device (include/fi_hip.h fi_volume_integrate): for every
     lattice point tsdf (fp32, 1 at first: free space, in units of `truncation`) and weight (fp32, 0 at first: never seen).
-    integrate() fuses depth images into it; constraints() / LatticeField.add_volume hand its band to the solve."""
+    integrate() fuses depth images into it; constraints() / LatticeField.add_volume hand its band to the solve.
 
-    def __init__(self, sizes, truncation, max_weight=64.0):
+    channels = 1 .. 4 adds colour (include/fi_hip.h fi_volume_integrate_colour): that many fp32 channels and one colour weight
+    per lattice point, 0 at first, which integrate(colours=...) averages over the views.  Two chains lead on from there:
+    vol.sample_colours(mesh.vertices) colours a mesh of iso_surface or dual_contour, and, with positions, colours, weights =
+    vol.colour_constraints(), field.add_points(w, ValueKernel.kLinearInterpolation, 0.0, GradientKernel.kNearestNeighbor,
+    positions, values=colours[:, k], point_weights=weights) completes channel k over the lattice by a solve."""
+
+    def __init__(self, sizes, truncation, max_weight=64.0, channels=0):
         self.sizes = [int(s) for s in sizes]
         self.truncation, self.max_weight = float(truncation), float(max_weight)
+        self.channels = int(channels)
         self._h = C.c_void_p()
         sz = (C.c_int * len(self.sizes))(*self.sizes)
         check(_capi.lib().fi_volume_create(C.byref(self._h), len(self.sizes), sz, self.truncation, self.max_weight))
+        if self.channels:
+            check(_capi.lib().fi_volume_set_channels(self._h, self.channels))
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -2552,28 +2561,38 @@ class DepthVolume:
     def num_voxels(self):
         return int(np.prod(self.sizes))
 
-    def integrate(self, cameras, depths, incidences=None, image_weights=None, min_incidence=0.5):
+    def integrate(self, cameras, depths, incidences=None, image_weights=None, min_incidence=0.5, colours=None, colour_band=1.0):
         """Fuses the depth images `depths` (a list of (height, width) arrays, or one array with the images back to back) seen
         by `cameras` into the volume, in that order.  incidences (optional, same layout; depth_to_points gives them) scale
         each sample's distance along the ray into one along the normal and weigh it; samples below min_incidence are left
-        out.  image_weights (optional): one factor per image.  numpy arrays, or torch tensors on the GPU."""
+        out.  image_weights (optional): one factor per image.  colours (optional, a volume with channels): a list of (height,
+        width, channels) images, or one flat array of them back to back, of any dtype, converted to float32 without scaling;
+        a voxel within colour_band * truncation of the surface averages its pixel's colour under the weight of the depth
+        sample, and tsdf and weight come out as without colours.  numpy arrays, or torch tensors on the GPU."""
         cameras = [cameras] if isinstance(cameras, Camera) else list(cameras)
         m = len(cameras)
         total = sum(c.width * c.height for c in cameras)
         d, dm, dk = _buf(_flat_images(depths))
         q, qm, qk = _buf(_flat_images(incidences))
         w, wm, wk = _buf(image_weights)
-        for name, keep, want in (("depths", dk, total), ("incidences", qk, total), ("image_weights", wk, m)):
+        c, cm, ck = _buf(_flat_images(colours))
+        for name, keep, want in (("depths", dk, total), ("incidences", qk, total), ("image_weights", wk, m),
+                                 ("colours", ck, total * self.channels)):
             if (keep is not None or name == "depths") and (0 if keep is None else _count(keep)) != want:
                 raise ValueError("%s: %d values, %d expected" % (name, 0 if keep is None else _count(keep), want))
         if dm == FI_DEVICE and wk is not None and wm != FI_DEVICE:       # a short host list beside device images
             import torch
             wk = torch.as_tensor(wk).to(dk.device)
             w, wm = C.c_void_p(wk.data_ptr()), FI_DEVICE
-        mem = _same_memory(dm, qm, wm)
-        cams = (_capi.FiCamera * max(m, 1))(*[c._c() for c in cameras])
-        check(_capi.lib().fi_volume_integrate(self._h, m, cams, d if total else None, q if total else None, w if m else None,
-                                              float(min_incidence), mem))
+        mem = _same_memory(dm, qm, wm, cm)
+        cams = (_capi.FiCamera * max(m, 1))(*[cam._c() for cam in cameras])
+        if colours is None:
+            check(_capi.lib().fi_volume_integrate(self._h, m, cams, d if total else None, q if total else None, w if m else None,
+                                                  float(min_incidence), mem))
+        else:
+            check(_capi.lib().fi_volume_integrate_colour(self._h, m, cams, d if total else None, q if total else None,
+                                                         w if m else None, float(min_incidence), c if total else None,
+                                                         float(colour_band), mem))
         return self
 
     def _read(self, which, device):
@@ -2598,6 +2617,60 @@ class DepthVolume:
             raise ValueError("tsdf and weight must hold %d values each" % self.num_voxels)
         check(_capi.lib().fi_volume_load(self._h, t, w, _same_memory(tm, wm)))
         return self
+
+    # ---- colour (include/fi_hip.h fi_volume_integrate_colour, fi_volume_colour_sample) ----
+    def colours(self, device=False):
+        """the colour channels, (channels, num_voxels) float32, x fastest within a channel"""
+        a, p = _cloud_out("cuda" if device else None, (self.channels, self.num_voxels), np.float32)
+        check(_capi.lib().fi_volume_colour_copy(self._h, p, None, FI_DEVICE if device else FI_HOST))
+        return a
+
+    def colour_weight(self, device=False):
+        """the colour weights, (num_voxels,) float32, x fastest"""
+        a, p = _cloud_out("cuda" if device else None, (self.num_voxels,), np.float32)
+        check(_capi.lib().fi_volume_colour_copy(self._h, None, p, FI_DEVICE if device else FI_HOST))
+        return a
+
+    def load_colours(self, colour, colour_weight):
+        """sets the channels ((channels, num_voxels) values) and the colour weights (num_voxels values): resumes a fusion"""
+        a, am, ak = _buf(colour)
+        w, wm, wk = _buf(colour_weight)
+        if _count(ak) != self.channels * self.num_voxels or _count(wk) != self.num_voxels:
+            raise ValueError("colour must hold %d x %d values and colour_weight %d" % (self.channels, self.num_voxels, self.num_voxels))
+        check(_capi.lib().fi_volume_colour_load(self._h, a, w, _same_memory(am, wm)))
+        return self
+
+    def sample_colours(self, positions, min_weight=0.0, valid=False):
+        """The colour (n, channels) float32 at `positions` (n, 3) in lattice coordinates: the average of the corners of the
+        point's cell that carry a colour (colour weight > 0 and >= min_weight) under the trilinear weights; NaN where none
+        does or the point lies outside the lattice.  valid=True: also the (n,) booleans of that.
+        vol.sample_colours(mesh.vertices) colours the vertices of iso_surface's or dual_contour's mesh.  numpy in, numpy out;
+        a torch tensor on the GPU in, tensors on that GPU out."""
+        p, mem, keep = _buf(positions)
+        if _count(keep) % 3:
+            raise ValueError("positions are (n, 3) (got %d values)" % _count(keep))
+        n = _count(keep) // 3
+        dev = keep.device if mem == FI_DEVICE else None
+        col, cp = _cloud_out(dev, (n, self.channels), np.float32)
+        val, vp = _cloud_out(dev, (n,), np.uint8) if valid else (None, None)
+        check(_capi.lib().fi_volume_colour_sample(self._h, float(min_weight), n, p if n else None, cp, vp, mem))
+        return (col, _as_mask(val)) if valid else col
+
+    def colour_constraints(self, min_weight=0.0, device=False):
+        """(positions (n, 3), colours (n, channels), weights (n,)) float32 of the voxels that carry a colour (colour weight > 0
+        and >= min_weight) in ascending index; weights are Wc / max_weight.  A channel completed over the lattice by a solve:
+        field.add_points(w, ValueKernel.kLinearInterpolation, 0.0, GradientKernel.kNearestNeighbor, positions,
+        values=colours[:, k], point_weights=weights)."""
+        n = C.c_long(0)
+        check(_capi.lib().fi_volume_colour_constraints(self._h, float(min_weight), C.byref(n), None, None, None, FI_HOST))
+        dev = "cuda" if device else None
+        pos, pp = _cloud_out(dev, (n.value, 3), np.float32)
+        col, pc = _cloud_out(dev, (n.value, self.channels), np.float32)
+        wgt, pw = _cloud_out(dev, (n.value,), np.float32)
+        if n.value:
+            check(_capi.lib().fi_volume_colour_constraints(self._h, float(min_weight), C.byref(n), pp, pc, pw,
+                                                           FI_DEVICE if device else FI_HOST))
+        return pos, col, wgt
 
     def constraints(self, min_weight=0.0, device=False):
         """(positions (n, 3), values (n,), weights (n,)) float32 of the band: the voxels with weight >= min_weight, weight > 0
@@ -2625,16 +2698,25 @@ class DepthVolume:
             return _capi.lib().fi_volume_raycast(self._h, C.byref(opt), n, o, d, float(t_min), float(t_max), tp, pp, np_, sp, mem)
         return _march_rays(call, 3, origins, directions, positions, normals)
 
-    def render(self, camera, step=1.0, refine=4, min_weight=0.0, positions=False, normals=False, incidence=False, device=False):
+    def render(self, camera, step=1.0, refine=4, min_weight=0.0, positions=False, normals=False, incidence=False, device=False,
+               colours=False, colour_min_weight=0.0):
         """The depth image (height, width) float32 of the volume's surface (tsdf = 0, front crossings) seen by `camera`, in
         the camera's own kind; +inf where a pixel's ray meets none.  With positions / normals / incidence also the hit points
         (h w, 3), the unit gradients (h w, 3) and the incidences (h w,) in depth_to_points' layout and conventions, so that
-        integrate() can take the image and its incidences as they are.  numpy arrays, or torch tensors with device=True."""
+        integrate() can take the image and its incidences as they are.  colours=True (a volume with channels) appends the
+        colour image (h w, channels): sample_colours(hit points, colour_min_weight), NaN where a pixel has no hit.  numpy
+        arrays, or torch tensors with device=True."""
         opt = _march_options(0.0, step, refine, "front", min_weight)
+        if not colours:
+            def call(cam, dp, pp, np_, ip, mem):
+                return _capi.lib().fi_volume_render(self._h, C.byref(opt), cam, dp, pp, np_, ip, mem)
+            return _march_image(call, camera, positions, normals, incidence, device)
+        col, cp = _cloud_out("cuda" if device else None, (camera.width * camera.height, self.channels), np.float32)
 
         def call(cam, dp, pp, np_, ip, mem):
-            return _capi.lib().fi_volume_render(self._h, C.byref(opt), cam, dp, pp, np_, ip, mem)
-        return _march_image(call, camera, positions, normals, incidence, device)
+            return _capi.lib().fi_volume_render_colour(self._h, C.byref(opt), cam, float(colour_min_weight), dp, pp, np_, ip, cp, mem)
+        out = _march_image(call, camera, positions, normals, incidence, device)
+        return (out if isinstance(out, tuple) else (out,)) + (col,)
 
     def track(self, camera, depth, rounds=2, max_jump=math.inf, max_distance=None, **register_keywords):
         """Refines the pose of `camera` from the depth image it took, against the surface the volume holds (frame-to-model

@@ -26,6 +26,7 @@
 #include "fi_feature.h"
 #include "fi_depth.h"
 #include "fi_march.h"
+#include "fi_colour.h"
 
 #include <memory>
 
@@ -2417,6 +2418,124 @@ int fi_volume_render(const fi_volume* v, const fi_march_options* options, const 
 	fi::check_march_field(3, v->n);
 	fi::march_image(march_field(v->tsdf.as<float>(), v->weight.as<float>(), 3, v->n), *options, *camera, depth, positions, normals,
 	                incidence, memory, nullptr);
+	FI_API_END
+}
+
+// ---- colour in a depth volume (fi_colour.hip) ---------------------------------------------------------
+namespace {
+void check_coloured(const fi_volume* v)
+{
+	check_volume(v);
+	FI_REQUIRE(v->channels > 0, FI_ERR_STATE, "the volume has no colour channels (fi_volume_set_channels)");
+}
+
+// sampling reads the eight corners of a cell
+void check_colour_cells(const fi_volume* v)
+{
+	FI_REQUIRE(v->n[0] >= 2 && v->n[1] >= 2 && v->n[2] >= 2, FI_ERR_UNSUPPORTED, "colour sampling needs sizes >= 2 (a %d x %d x %d volume)",
+	           v->n[0], v->n[1], v->n[2]);
+}
+}  // namespace
+
+int fi_volume_set_channels(fi_volume* v, int channels)
+{
+	FI_API_BEGIN
+	check_volume(v);
+	FI_REQUIRE(channels >= 1 && channels <= fi::kMaxChannels, FI_ERR_INVALID, "channels must be 1..%d (got %d)", fi::kMaxChannels, channels);
+	FI_REQUIRE(v->channels == 0, FI_ERR_STATE, "the volume has %d channels already", v->channels);
+	fi::volume_set_channels(v, channels, nullptr);
+	FI_API_END
+}
+
+int fi_volume_channels(const fi_volume* v, int* channels)
+{
+	FI_API_BEGIN
+	FI_REQUIRE(v != nullptr && channels != nullptr, FI_ERR_INVALID, "null argument");
+	*channels = v->channels;
+	FI_API_END
+}
+
+int fi_volume_colour_load(fi_volume* v, const float* colour, const float* colour_weight, int memory)
+{
+	FI_API_BEGIN
+	check_coloured(v);
+	FI_REQUIRE(colour != nullptr && colour_weight != nullptr, FI_ERR_INVALID, "null colour or colour_weight");
+	fi::check_memory(memory);
+	const hipMemcpyKind kind = memory == FI_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+	FI_HIP_TRY(hipMemcpyAsync(v->colour.p, colour, sizeof(float) * v->channels * v->nvox, kind, nullptr));
+	FI_HIP_TRY(hipMemcpyAsync(v->colour_weight.p, colour_weight, sizeof(float) * v->nvox, kind, nullptr));
+	FI_HIP_TRY(hipStreamSynchronize(nullptr));
+	FI_API_END
+}
+
+int fi_volume_colour_copy(const fi_volume* v, float* colour, float* colour_weight, int memory)
+{
+	FI_API_BEGIN
+	check_coloured(v);
+	FI_REQUIRE(colour != nullptr || colour_weight != nullptr, FI_ERR_INVALID, "null colour and colour_weight");
+	fi::check_memory(memory);
+	const hipMemcpyKind kind = memory == FI_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+	if (colour) { FI_HIP_TRY(hipMemcpyAsync(colour, v->colour.p, sizeof(float) * v->channels * v->nvox, kind, nullptr)); }
+	if (colour_weight) { FI_HIP_TRY(hipMemcpyAsync(colour_weight, v->colour_weight.p, sizeof(float) * v->nvox, kind, nullptr)); }
+	FI_HIP_TRY(hipStreamSynchronize(nullptr));
+	FI_API_END
+}
+
+int fi_volume_integrate_colour(fi_volume* v, long m, const fi_camera* cameras, const float* depths, const float* incidences,
+                               const float* image_weights, float min_incidence, const float* colours, float band, int memory)
+{
+	FI_API_BEGIN
+	check_coloured(v);
+	FI_REQUIRE(min_incidence == min_incidence, FI_ERR_INVALID, "min_incidence is NaN");
+	FI_REQUIRE(band > 0.0f && band <= 1.0f, FI_ERR_INVALID, "band must be in (0, 1] (got %g)", static_cast<double>(band));  // (NaN fails)
+	fi::check_memory(memory);
+	check_cameras(m, cameras);
+	FI_REQUIRE(m == 0 || depths != nullptr, FI_ERR_INVALID, "depths is null");
+	FI_REQUIRE(m == 0 || colours != nullptr, FI_ERR_INVALID, "colours is null");
+	fi::volume_integrate_colour(v, m, cameras, depths, incidences, image_weights, min_incidence, colours, band, memory, nullptr);
+	FI_API_END
+}
+
+int fi_volume_colour_sample(const fi_volume* v, float min_weight, long n, const float* positions, float* colours, unsigned char* valid,
+                            int memory)
+{
+	FI_API_BEGIN
+	check_coloured(v);
+	FI_REQUIRE(min_weight == min_weight, FI_ERR_INVALID, "min_weight is NaN");
+	FI_REQUIRE(n >= 0, FI_ERR_INVALID, "n = %ld", n);
+	FI_REQUIRE(n == 0 || positions != nullptr, FI_ERR_INVALID, "positions is null");
+	FI_REQUIRE(n == 0 || colours != nullptr, FI_ERR_INVALID, "colours is null");
+	fi::check_memory(memory);
+	FI_REQUIRE(n < (1L << 31), FI_ERR_UNSUPPORTED, "%ld points in one call", n);
+	check_colour_cells(v);
+	fi::volume_colour_sample(v, min_weight, n, positions, colours, valid, memory, nullptr);
+	FI_API_END
+}
+
+int fi_volume_render_colour(const fi_volume* v, const fi_march_options* options, const fi_camera* camera, float colour_min_weight,
+                            float* depth, float* positions, float* normals, float* incidence, float* colours, int memory)
+{
+	FI_API_BEGIN
+	check_coloured(v);
+	check_march_image(options, camera, depth, memory);
+	FI_REQUIRE(colour_min_weight == colour_min_weight, FI_ERR_INVALID, "colour_min_weight is NaN");
+	FI_REQUIRE(colours != nullptr, FI_ERR_INVALID, "colours is null");
+	check_colour_cells(v);
+	fi::check_march_field(3, v->n);
+	fi::volume_render_colour(v, *options, *camera, colour_min_weight, depth, positions, normals, incidence, colours, memory, nullptr);
+	FI_API_END
+}
+
+int fi_volume_colour_constraints(const fi_volume* v, float min_weight, long* n, float* positions, float* colours, float* weights, int memory)
+{
+	FI_API_BEGIN
+	check_coloured(v);
+	FI_REQUIRE(n != nullptr, FI_ERR_INVALID, "n is null");
+	FI_REQUIRE(min_weight == min_weight, FI_ERR_INVALID, "min_weight is NaN");
+	fi::check_memory(memory);
+	const bool fill = positions || colours || weights;
+	FI_REQUIRE(!fill || *n >= 0, FI_ERR_INVALID, "room for %ld points", *n);
+	*n = static_cast<long>(fi::volume_colour_constraints(v, min_weight, fill ? *n : 0, positions, colours, weights, memory, nullptr));
 	FI_API_END
 }
 

@@ -11,6 +11,9 @@ struct fi_volume {
 	int64_t    nvox   = 0;
 	float      truncation = 0, max_weight = 0;
 	fi::DevBuf tsdf, weight;  // float[nvox], x fastest
+	// the optional colour state (fi_colour.hip; fi_volume_set_channels): nothing in fi_depth.hip or fi_march.hip touches it
+	int        channels = 0;          // 0: none yet, else 1 .. 4
+	fi::DevBuf colour, colour_weight;  // float[channels nvox], planar (channel k of voxel i at k nvox + i), and float[nvox]
 };
 
 namespace fi {

@@ -12,46 +12,12 @@
 #include "fi_prim.h"
 #include "fi_solver_internal.h"
 #include "fi_stage.h"
+#include "fi_volume_pass.h"
 
 namespace fi {
 namespace {
 
-constexpr int kCams   = FI_DEPTH_CAMERAS;  // images one launch of k_volume_integrate applies
-constexpr int kPlanes = 5;                 // cull planes per image: behind, left, right, top, bottom
-static_assert(kCams * kPlanes <= 64, "a wave evaluates every cull plane of a launch at once, a lane each");
-
-struct CamRow {  // one image as the kernels read it
-	float     r[12];  // rows of [R | t]
-	float     fx, fy, cx, cy;
-	int       width, height, kind, pad;
-	long long off;    // the image's first pixel in the call's depths / incidences
-	long long index;  // the image's index in the call (image_weights)
-};
-
-// the images of one launch and their cull planes: plane (s, k) is (n, o) over voxel coordinates; image s is skipped by a wave
-// whose run of voxels has n . p + o < 0 everywhere for some k
-struct CamTable {
-	CamRow cam[kCams];
-	float4 plane[kCams * kPlanes];
-};
-
-CamRow row_of(const fi_camera& c, long long off, long long index)
-{
-	CamRow r{};
-	std::memcpy(r.r, c.pose, sizeof(r.r));
-	r.fx     = c.fx;
-	r.fy     = c.fy;
-	r.cx     = c.cx;
-	r.cy     = c.cy;
-	r.width  = c.width;
-	r.height = c.height;
-	r.kind   = c.kind;
-	r.off    = off;
-	r.index  = index;
-	return r;
-}
-
-__device__ __forceinline__ bool depth_ok(float d) { return d > 0.0f && d < INFINITY; }
+// (the camera row, the table of a launch, the cull planes and steps 1 - 8 of a voxel: fi_volume_pass.h, shared with fi_colour.hip)
 
 // ---- a depth image becomes oriented points ---------------------------------------------------------------------------------
 struct Vec3 {
@@ -148,13 +114,6 @@ __global__ __launch_bounds__(kThreads) void k_depth_unproject(CamRow c, int64_t 
 }
 
 // ---- the volume -------------------------------------------------------------------------------------------------------------
-struct VolArgs {
-	int      nx, ny, nz;
-	unsigned waves_x;  // waves along a row of x
-	unsigned nwaves;   // waves_x * ny * nz
-	float    truncation, max_weight;
-};
-
 __global__ __launch_bounds__(kThreads) void k_volume_fill(int64_t n, float* __restrict__ tsdf, float* __restrict__ weight)
 {
 	const int64_t i = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
@@ -166,10 +125,8 @@ __global__ __launch_bounds__(kThreads) void k_volume_fill(int64_t n, float* __re
 // Voxel-stationary fusion: a wave owns 64 consecutive x of one (y, z) row, a thread one voxel.  The voxel's tsdf and weight are
 // read once, up to kCams images are applied in image order, and both are written once.  The images' cameras come from a table
 // indexed by the (wave-uniform) loop counter: scalar loads into scalar registers.  Depth and incidence are gathered: a wave's
-// voxels project onto a short run of pixels.  The cull: before the loop, lane s * kPlanes + k evaluates plane k of image s over
-// the wave's run of voxels (a segment: the maximum of a linear form over it is its value at the middle plus |n_x| times the
-// half length); an image with a plane that excludes the whole run is skipped by the whole wave.  The planes carry a margin
-// (volume_integrate), so a skipped image is one every voxel of the run would have skipped by itself.  No LDS, no atomics.
+// voxels project onto a short run of pixels.  An image with a cull plane that excludes the wave's whole run is skipped by the
+// whole wave.  The run, the cull and the steps of one image are fi_volume_pass.h's.  No LDS, no atomics.
 __global__ __launch_bounds__(kThreads) void k_volume_integrate(VolArgs a, const CamTable* __restrict__ tab, int nc,
                                                                 const float* __restrict__ depth, const float* __restrict__ inc,
                                                                 const float* __restrict__ iw, float min_inc, float* __restrict__ tsdf,
@@ -179,57 +136,19 @@ __global__ __launch_bounds__(kThreads) void k_volume_integrate(VolArgs a, const 
 	const int      lane = threadIdx.x & 63;
 	const unsigned wid  = blockIdx.x * (kThreads / 64) + wave;
 	if (wid >= a.nwaves) { return; }
-	const unsigned wx   = wid % a.waves_x;
-	const unsigned rest = wid / a.waves_x;
-	const int      y = static_cast<int>(rest % static_cast<unsigned>(a.ny)), z = static_cast<int>(rest / static_cast<unsigned>(a.ny));
-	const int      x0 = static_cast<int>(wx) * 64;
-	const int      x1 = min(x0 + 63, a.nx - 1);
-	const float    Y = static_cast<float>(y), Z = static_cast<float>(z);
+	const WaveRun            r = run_of(a, wid);
+	const unsigned long long culled = culled_of(tab, nc, r, lane);
 
-	bool excluded = false;
-	if (lane < nc * kPlanes) {
-		const float  h = 0.5f * static_cast<float>(x1 - x0);
-		const float  mid = static_cast<float>(x0) + h;
-		const float4 p = tab->plane[lane];
-		excluded = (((p.x * mid + p.y * Y) + p.z * Z) + fabsf(p.x) * h) + p.w < 0.0f;
-	}
-	const unsigned long long culled = __ballot(excluded);
-
-	const int x = x0 + lane;
-	if (x > x1) { return; }
-	const int64_t idx = (static_cast<int64_t>(z) * a.ny + y) * a.nx + x;
-	const float   X   = static_cast<float>(x);
+	const int x = r.x0 + lane;
+	if (x > r.x1) { return; }
+	const int64_t idx = (static_cast<int64_t>(r.z) * a.ny + r.y) * a.nx + x;
+	const float   X = static_cast<float>(x), Y = static_cast<float>(r.y), Z = static_cast<float>(r.z);
 	float         t = tsdf[idx], W = weight[idx];
 	for (int s = 0; s < nc; ++s) {
-		if ((culled >> (s * kPlanes)) & ((1ull << kPlanes) - 1)) { continue; }
-		const CamRow& c  = tab->cam[s];
-		const float   cx = ((c.r[0] * X + c.r[1] * Y) + c.r[2] * Z) + c.r[3];
-		const float   cy = ((c.r[4] * X + c.r[5] * Y) + c.r[6] * Z) + c.r[7];
-		const float   cz = ((c.r[8] * X + c.r[9] * Y) + c.r[10] * Z) + c.r[11];
-		if (!(cz > 0.0f)) { continue; }
-		const float fu = floorf(c.fx * (cx / cz) + c.cx);
-		const float fv = floorf(c.fy * (cy / cz) + c.cy);
-		if (!(fu >= 0.0f && fu < 2147483648.0f && fv >= 0.0f && fv < 2147483648.0f)) { continue; }
-		const int col = static_cast<int>(fu), row = static_cast<int>(fv);
-		if (col >= c.width || row >= c.height) { continue; }
-		const int64_t pix = c.off + static_cast<int64_t>(row) * c.width + col;
-		const float   d   = depth[pix];
-		if (!depth_ok(d)) { continue; }
-		const float r = c.kind == FI_DEPTH_Z ? cz : sqrtf((cx * cx + cy * cy) + cz * cz);
-		const float e = d - r;
-		if (e < -a.truncation) { continue; }
-		float q = 1.0f;
-		if (inc) {
-			q = inc[pix];
-			if (!(q >= min_inc && fabsf(q) < INFINITY)) { continue; }
-		}
-		const float g = (e * q) / a.truncation;
-		const float f = g < 1.0f ? g : 1.0f;
-		const float w = q * (iw ? iw[c.index] : 1.0f);
-		if (!(w > 0.0f)) { continue; }
-		const float sum = W + w;
-		t = (t * W + f * w) / sum;
-		W = sum < a.max_weight ? sum : a.max_weight;
+		if (image_culled(culled, s)) { continue; }
+		VoxelSample v;
+		if (!voxel_sample(a, tab->cam[s], X, Y, Z, depth, inc, iw, min_inc, v)) { continue; }
+		voxel_fuse(a, v, t, W);
 	}
 	tsdf[idx]   = t;
 	weight[idx] = W;
@@ -268,53 +187,6 @@ __global__ __launch_bounds__(kThreads) void k_volume_gather(VolArgs a, int64_t n
 	}
 	if (values) { values[o] = tsdf[i] * a.truncation; }
 	if (weights) { weights[o] = weight[i] / a.max_weight; }
-}
-
-VolArgs args_of(const fi_volume* v)
-{
-	VolArgs a{};
-	a.nx = v->n[0];
-	a.ny = v->n[1];
-	a.nz = v->n[2];
-	const int64_t waves_x = (v->n[0] + 63) / 64;
-	const int64_t nwaves  = waves_x * v->n[1] * v->n[2];
-	FI_REQUIRE(nwaves < (1LL << 31), FI_ERR_UNSUPPORTED, "%lld rows of 64 voxels in one volume", static_cast<long long>(nwaves));
-	a.waves_x    = static_cast<unsigned>(waves_x);
-	a.nwaves     = static_cast<unsigned>(nwaves);
-	a.truncation = v->truncation;
-	a.max_weight = v->max_weight;
-	return a;
-}
-
-// The cull planes of one image over the voxels of v.  With c(p) = R p + t the camera point of voxel p, a form g = alpha . c(p)
-// is linear in p.  The five forms: c_z (behind the camera where negative), and the four sides of the image widened by a pixel:
-// fx c_x + (cx + 1) c_z < 0 is u < -1 for a voxel in front, and so on.  The kernel's own fp32 figures differ from the exact
-// ones by a few 2^-24 of M = sum |alpha_a| (sum |R_aj| (size_j - 1) + |t_a|); the plane's offset is raised by 1e-5 M, forty
-// times that, and the pixel of slack covers the rounding of u and v for pixel coordinates up to 2^16 (beyond: no cull).
-void planes_of(const fi_camera& c, const fi_volume* v, bool cull, float4* out)
-{
-	for (int k = 0; k < kPlanes; ++k) { out[k] = float4{0.0f, 0.0f, 0.0f, 1.0f}; }  // (never negative: no cull)
-	const double lim = 65536.0;
-	if (!cull || std::fabs(c.cx) > lim || std::fabs(c.cy) > lim || c.width > lim || c.height > lim) { return; }
-	const double alpha[kPlanes][3] = {{0.0, 0.0, 1.0},
-	                                  {c.fx, 0.0, static_cast<double>(c.cx) + 1.0},
-	                                  {-static_cast<double>(c.fx), 0.0, c.width + 1.0 - c.cx},
-	                                  {0.0, c.fy, static_cast<double>(c.cy) + 1.0},
-	                                  {0.0, -static_cast<double>(c.fy), c.height + 1.0 - c.cy}};
-	for (int k = 0; k < kPlanes; ++k) {
-		double n[3] = {0, 0, 0}, o = 0, M = 0;
-		for (int a = 0; a < 3; ++a) {
-			for (int j = 0; j < 3; ++j) {
-				n[j] += alpha[k][a] * c.pose[4 * a + j];
-				M += std::fabs(alpha[k][a] * c.pose[4 * a + j]) * (v->n[j] - 1);
-			}
-			o += alpha[k][a] * c.pose[4 * a + 3];
-			M += std::fabs(alpha[k][a] * c.pose[4 * a + 3]);
-		}
-		const float4 p{static_cast<float>(n[0]), static_cast<float>(n[1]), static_cast<float>(n[2]),
-		               std::nextafter(static_cast<float>(o + 1e-5 * M), INFINITY)};
-		if (std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z) && std::isfinite(p.w)) { out[k] = p; }
-	}
 }
 
 // flags and their exclusive sums over the volume's voxels, as pieces of `block`; returns the count
@@ -379,18 +251,10 @@ void volume_integrate(fi_volume* v, long m, const fi_camera* cameras, const floa
                       const float* image_weights, float min_incidence, int memory, hipStream_t st)
 {
 	if (m == 0) { return; }
-	const VolArgs         a = args_of(v);
-	const bool            cull = !test_switch("FI_NO_DEPTH_CULL");  // (the same bytes either way: tests/test_gpu_depth.py)
-	const long            launches = (m + kCams - 1) / kCams;
-	std::vector<CamTable> host(static_cast<size_t>(launches));
-	std::memset(host.data(), 0, host.size() * sizeof(CamTable));
-	int64_t pixels = 0;
-	for (long s = 0; s < m; ++s) {
-		CamTable& t = host[static_cast<size_t>(s / kCams)];
-		t.cam[s % kCams] = row_of(cameras[s], pixels, s);
-		planes_of(cameras[s], v, cull, t.plane + (s % kCams) * kPlanes);
-		pixels += camera_pixels(cameras[s]);
-	}
+	const VolArgs               a = args_of(v);
+	int64_t                     pixels = 0;
+	const std::vector<CamTable> host = tables_of(v, m, cameras, &pixels);
+	const long                  launches = static_cast<long>(host.size());
 	AllocStream     alloc_on(st);
 	const float *   d = nullptr, *q = nullptr, *iw = nullptr;
 	const CamTable* tab = nullptr;

@@ -828,6 +828,121 @@ bool DepthVolume::render(const DepthCamera& camera, std::vector<float>* depth, c
 	return true;
 }
 
+// ---- colour in a depth volume (include/fi_hip.h fi_volume_integrate_colour) ----
+bool DepthVolume::set_channels(int channels)
+{
+	if (!volume_ || fi_volume_set_channels(volume_, channels) != FI_OK) {
+		warn("DepthVolume::set_channels");
+		return false;
+	}
+	return true;
+}
+
+int DepthVolume::channels() const
+{
+	int c = 0;
+	return volume_ && fi_volume_channels(volume_, &c) == FI_OK ? c : 0;
+}
+
+bool DepthVolume::integrate_colour(const std::vector<DepthCamera>& cameras, const std::vector<float>& depths, const std::vector<float>& colours,
+                                   const std::vector<float>& incidences, const std::vector<float>& image_weights, float min_incidence,
+                                   float band)
+{
+	std::vector<fi_camera> cams;
+	size_t                 pixels = 0;
+	for (const DepthCamera& c : cameras) {
+		cams.push_back(to_c(c));
+		if (c.width > 0 && c.height > 0) { pixels += static_cast<size_t>(c.width) * static_cast<size_t>(c.height); }
+	}
+	if (!volume_ || depths.size() != pixels || colours.size() != pixels * static_cast<size_t>(channels()) ||
+	    (!incidences.empty() && incidences.size() != pixels) || (!image_weights.empty() && image_weights.size() != cameras.size()) ||
+	    fi_volume_integrate_colour(volume_, static_cast<long>(cams.size()), cams.data(), depths.data(),
+	                               incidences.empty() ? nullptr : incidences.data(), image_weights.empty() ? nullptr : image_weights.data(),
+	                               min_incidence, colours.data(), band, FI_HOST) != FI_OK) {
+		warn("DepthVolume::integrate_colour");
+		return false;
+	}
+	return true;
+}
+
+bool DepthVolume::copy_colours(std::vector<float>* colours, std::vector<float>* colour_weight) const
+{
+	if (colours) { colours->resize(voxels_ * static_cast<size_t>(channels())); }
+	if (colour_weight) { colour_weight->resize(voxels_); }
+	if (!volume_ || fi_volume_colour_copy(volume_, data_or_null(colours), data_or_null(colour_weight), FI_HOST) != FI_OK) {
+		warn("DepthVolume::copy_colours");
+		return false;
+	}
+	return true;
+}
+
+bool DepthVolume::load_colours(const std::vector<float>& colours, const std::vector<float>& colour_weight)
+{
+	if (!volume_ || colours.size() != voxels_ * static_cast<size_t>(channels()) || colour_weight.size() != voxels_ ||
+	    fi_volume_colour_load(volume_, colours.data(), colour_weight.data(), FI_HOST) != FI_OK) {
+		warn("DepthVolume::load_colours");
+		return false;
+	}
+	return true;
+}
+
+bool DepthVolume::sample_colours(const std::vector<float>& positions, std::vector<float>* colours, std::vector<unsigned char>* valid,
+                                 float min_weight) const
+{
+	const size_t n = positions.size() / 3;
+	if (!volume_ || !colours || positions.size() % 3 != 0) {
+		warn("DepthVolume::sample_colours");
+		return false;
+	}
+	colours->resize(n * static_cast<size_t>(channels()));
+	if (valid) { valid->resize(n); }
+	if (fi_volume_colour_sample(volume_, min_weight, static_cast<long>(n), positions.data(), colours->data(), valid ? valid->data() : nullptr,
+	                            FI_HOST) != FI_OK) {
+		warn("DepthVolume::sample_colours");
+		return false;
+	}
+	return true;
+}
+
+bool DepthVolume::render_colour(const DepthCamera& camera, std::vector<float>* depth, std::vector<float>* colours, const MarchOptions& options,
+                                float colour_min_weight, std::vector<float>* positions, std::vector<float>* normals,
+                                std::vector<float>* incidence) const
+{
+	const fi_camera        c = to_c(camera);
+	const fi_march_options o = to_c(options);
+	if (!volume_ || !colours || !size_image(camera, depth, positions, normals, incidence)) {
+		warn("DepthVolume::render_colour");
+		return false;
+	}
+	colours->resize(depth->size() * static_cast<size_t>(channels()));
+	if (fi_volume_render_colour(volume_, &o, &c, colour_min_weight, depth->data(), data_or_null(positions), data_or_null(normals),
+	                            data_or_null(incidence), colours->data(), FI_HOST) != FI_OK) {
+		warn("DepthVolume::render_colour");
+		return false;
+	}
+	return true;
+}
+
+bool DepthVolume::colour_constraints(std::vector<float>* positions, std::vector<float>* colours, std::vector<float>* weights,
+                                     float min_weight) const
+{
+	long n = 0;
+	if (!volume_ || fi_volume_colour_constraints(volume_, min_weight, &n, nullptr, nullptr, nullptr, FI_HOST) != FI_OK) {
+		warn("DepthVolume::colour_constraints");
+		return false;
+	}
+	if (positions) { positions->resize(3 * static_cast<size_t>(n)); }
+	if (colours) { colours->resize(static_cast<size_t>(channels()) * static_cast<size_t>(n)); }
+	if (weights) { weights->resize(static_cast<size_t>(n)); }
+	if (n == 0 || (!positions && !colours && !weights)) { return true; }
+	if (fi_volume_colour_constraints(volume_, min_weight, &n, data_or_null(positions), data_or_null(colours), data_or_null(weights), FI_HOST) !=
+	    FI_OK) {
+		warn("DepthVolume::colour_constraints");
+		return false;
+	}
+	return true;
+}
+
 bool GpuLatticeField::march(const std::vector<float>& origins, const std::vector<float>& directions, std::vector<float>* t,
                             const MarchOptions& options, std::vector<float>* positions, std::vector<float>* normals,
                             std::vector<signed char>* side, float t_min, float t_max) const

@@ -1548,8 +1548,8 @@ int fi_redistance_field(const float* field, int ndim, const int* sizes, float is
  * finite, a NULL required pointer, a bad memory kind, m < 0, sizes that differ from the lattice's.  m = 0 is fine.
  * FI_ERR_UNSUPPORTED: a 1-D or 2-D lattice, more than 2^31 - 1 voxels, or pixels in one call, a slab context.  `memory` applies
  * to every buffer of a call but the cameras.
- * Not offered: 2-D lattices, bilinear depth lookup, colour, free-space (tsdf = 1) constraints, space carving, sparse or hashed
- * volumes, lens distortion, slab groups. */
+ * Not offered: 2-D lattices, bilinear depth lookup, free-space (tsdf = 1) constraints, space carving, sparse or hashed
+ * volumes, lens distortion, slab groups.  Colour is fused beside the depth by fi_volume_integrate_colour (below). */
 #define FI_DEPTH_Z 0
 #define FI_DEPTH_RANGE 1
 #define FI_DEPTH_CAMERAS 8
@@ -1618,7 +1618,8 @@ int fi_add_volume(fi_ctx* ctx, const fi_volume* volume, float value_weight, int 
  * min_weight, t_min > t_max or a NaN bound, a NULL required pointer, every output NULL, a bad memory kind, a bad camera,
  * n < 0.  n = 0 is fine.  FI_ERR_UNSUPPORTED: n, the pixels or the lattice points >= 2^31, ndim = 1, a 2-D field for an image,
  * a slab context.  `memory` applies to every buffer of a call but the camera and a volume's own arrays.
- * Not offered: sphere tracing, empty-space skipping, sorted rays, cubic interpolation, exact per-cell roots, slabs, colour. */
+ * Not offered: sphere tracing, empty-space skipping, sorted rays, cubic interpolation, exact per-cell roots, slabs.  The colour
+ * image of a volume that carries colour: fi_volume_render_colour (below). */
 #define FI_MARCH_FRONT 0
 #define FI_MARCH_BACK 1
 #define FI_MARCH_EITHER 2
@@ -1643,6 +1644,66 @@ int fi_volume_raycast(const fi_volume* volume, const fi_march_options* options, 
                       signed char* side, int memory);
 int fi_volume_render(const fi_volume* volume, const fi_march_options* options, const fi_camera* camera, float* depth,
                      float* positions, float* normals, float* incidence, int memory);
+
+/* ---- colour in a depth volume --------------------------------------------------------------------------
+ * The contract (tests/colour_reference.py is its definition in numpy).  3-D only.  All arithmetic is fp32, one
+ * rounding per operation, in the order written here with the parentheses given; min(a, b) is a < b ? a : b.  No atomics:
+ * every output is defined bit for bit.
+ *
+ * A volume gets optional colour state: C = 1 .. 4 channels, fp32, planar (channel k of voxel i at k nvox + i, x fastest), and one
+ * colour weight Wc per voxel; channels and Wc are 0 at first.  fi_volume_set_channels allocates and zeroes them (FI_ERR_STATE
+ * if the volume has channels already, FI_ERR_INVALID outside 1 .. 4), fi_volume_channels reads C (0: none).
+ * fi_volume_colour_load sets float[C nvox] and float[nvox] (the values are taken as they are), fi_volume_colour_copy reads them
+ * (either output may be NULL).  fi_volume_load, fi_volume_copy, fi_volume_integrate, fi_volume_constraints, fi_add_volume,
+ * fi_volume_raycast and fi_volume_render never touch the colour state.
+ *
+ * fi_volume_integrate_colour: cameras, depths, incidences, image_weights and min_incidence as fi_volume_integrate takes them;
+ * colours holds the images' colours pixel-interleaved, float[h w C] per image, the images back to back like depths.  For
+ * image s and voxel p, steps 1 - 8 of fi_volume_integrate run unchanged, with the same e, q, g = (e q) / truncation, f and w:
+ * tsdf and W receive the bits fi_volume_integrate gives for the same images.  If the voxel passed step 7, then:
+ *   9.  skip the colour unless |g| < band: the voxel lies within band truncation of the surface along the normal (the far
+ *       side is cut at step 4 already);
+ *   10. skip the colour unless every channel c_k of pixel [row, col] is finite;
+ *   11. for k = 0 .. C - 1: a_k = (a_k Wc + c_k w) / (Wc + w); then Wc = min(Wc + w, max_weight).
+ * A colour skip never affects the geometry update.  The kernel applies FI_DEPTH_CAMERAS images per pass, further passes in
+ * image order for more; no result depends on that number, nor on the cull, nor on whether a pixel's channels are read by one
+ * wide load or by C narrow ones.
+ *
+ * fi_volume_colour_sample, a thread per point, positions float[n 3], hi_j = (float)(size_j - 1).  A point is valid input when
+ * it is finite and 0 <= p_j <= hi_j for every j (no clamping).  Cell c_j = min(floor(p_j), size_j - 2), t_j = p_j - c_j,
+ * w_0 = 1 - t, w_1 = t per axis.  The corners (a, b, c) of the cell run in ascending a + 2 b + 4 c with omega = (wx_a wy_b) wz_c;
+ * a corner counts when its Wc > 0 and Wc >= min_weight.  From S = 0 and N_k = 0, over the counting corners in that order:
+ * S = S + omega, N_k = N_k + omega a_k.  colour_k = N_k / S and valid = 1 when S > 0; else (and for a point that is no valid
+ * input) colour_k = NaN and valid = 0.  The sums are normalised over the observed corners on purpose: the colour band is thin,
+ * and a vertex of the iso-surface sits between a voxel inside it and one outside.  colours float[n C], valid unsigned char[n]
+ * or NULL.
+ *
+ * fi_volume_render_colour: depth, positions, normals and incidence are the bytes fi_volume_render writes for the same
+ * options and camera (depth is required, the three may be NULL); colours float[h w C] is fi_volume_colour_sample with
+ * colour_min_weight at each pixel's hit position, NaN where there is no hit.
+ *
+ * fi_volume_colour_constraints: the voxels with Wc > 0 and Wc >= min_weight in ascending linear index: positions (float)i, j,
+ * k; colours a_k, interleaved, float[n C]; weights Wc / max_weight.  The two calls of fi_volume_constraints.  Column k of
+ * colours is what fi_add_points takes as values (with weights as point weights) to complete channel k by a solve.
+ *
+ * FI_ERR_STATE: a volume without channels, in every call but the first two.  FI_ERR_INVALID: NULL colours, a band outside
+ * (0, 1] or not finite, a NaN min_weight or colour_min_weight, and what fi_volume_integrate and fi_volume_render refuse.
+ * m = 0 and n = 0 are fine.  FI_ERR_UNSUPPORTED: sampling or rendering a volume with a size below 2; n >= 2^31.
+ * Not offered: 2-D lattices, bilinear image lookup, uint8 storage, colour in pose tracking, colour on fi_mesh handles, slab
+ * contexts, gamma or exposure handling, a fused march-and-colour kernel. */
+int fi_volume_set_channels(fi_volume* volume, int channels);
+int fi_volume_channels(const fi_volume* volume, int* channels);
+int fi_volume_colour_load(fi_volume* volume, const float* colour, const float* colour_weight, int memory);
+int fi_volume_colour_copy(const fi_volume* volume, float* colour, float* colour_weight, int memory);
+int fi_volume_integrate_colour(fi_volume* volume, long m, const fi_camera* cameras, const float* depths, const float* incidences,
+                               const float* image_weights, float min_incidence, const float* colours, float band, int memory);
+int fi_volume_colour_sample(const fi_volume* volume, float min_weight, long n, const float* positions, float* colours,
+                            unsigned char* valid, int memory);
+int fi_volume_render_colour(const fi_volume* volume, const fi_march_options* options, const fi_camera* camera,
+                            float colour_min_weight, float* depth, float* positions, float* normals, float* incidence, float* colours,
+                            int memory);
+int fi_volume_colour_constraints(const fi_volume* volume, float min_weight, long* n, float* positions, float* colours, float* weights,
+                                 int memory);
 
 #ifdef __cplusplus
 }

@@ -148,6 +148,31 @@ public:
 	// positions, normals and incidences in depth_to_points' layout, so that integrate() can take the image as it is.
 	bool render(const DepthCamera& camera, std::vector<float>* depth, const MarchOptions& options = MarchOptions(),
 	            std::vector<float>* positions = nullptr, std::vector<float>* normals = nullptr, std::vector<float>* incidence = nullptr) const;
+	// Colour (include/fi_hip.h fi_volume_integrate_colour): set_channels(1 .. 4) once gives every lattice point that many fp32
+	// channels and a colour weight, 0 at first; channels() is 0 before.  integrate_colour is integrate() with the images'
+	// colours beside the depths: pixel-interleaved, height_s x width_s x channels floats per image, the images back to back; a
+	// voxel within band * truncation of the surface averages its pixel's colour under the depth sample's weight, and tsdf and
+	// weight come out as integrate() leaves them.
+	bool set_channels(int channels);
+	int  channels() const;
+	bool integrate_colour(const std::vector<DepthCamera>& cameras, const std::vector<float>& depths, const std::vector<float>& colours,
+	                      const std::vector<float>& incidences = std::vector<float>(),
+	                      const std::vector<float>& image_weights = std::vector<float>(), float min_incidence = 0.5f, float band = 1.0f);
+	// the channels, planar (channel k of voxel i at k num_voxels() + i), and the colour weights; either may be null
+	bool copy_colours(std::vector<float>* colours, std::vector<float>* colour_weight) const;
+	bool load_colours(const std::vector<float>& colours, const std::vector<float>& colour_weight);  // resumes a fusion
+	// the colour at positions (3 floats each): channels() floats per point, the average of the corners of the point's cell that
+	// carry a colour (colour weight > 0 and >= min_weight) under the trilinear weights; NaN and valid 0 where none does or the
+	// point lies outside the lattice.  The vertices of iso_surface's mesh are such positions.
+	bool sample_colours(const std::vector<float>& positions, std::vector<float>* colours, std::vector<unsigned char>* valid = nullptr,
+	                    float min_weight = 0) const;
+	// render() and the colour image beside it: sample_colours(hit positions, colour_min_weight), NaN where a pixel has no hit
+	bool render_colour(const DepthCamera& camera, std::vector<float>* depth, std::vector<float>* colours,
+	                   const MarchOptions& options = MarchOptions(), float colour_min_weight = 0, std::vector<float>* positions = nullptr,
+	                   std::vector<float>* normals = nullptr, std::vector<float>* incidence = nullptr) const;
+	// the voxels with colour weight > 0 and >= min_weight in ascending index: positions (3 floats each), colours (channels()
+	// floats each), weights Wc / max_weight; any may be null
+	bool colour_constraints(std::vector<float>* positions, std::vector<float>* colours, std::vector<float>* weights, float min_weight = 0) const;
 	const fi_volume* handle() const { return volume_; }
 
 private:
